@@ -20,7 +20,8 @@ Images shard over ranks (rank r takes images r, r+world, ...: weak scaling, per-
 one RCCL all_gather of the fixed-stride detection records at the end of the timed region.  `--config cfg5
 --ensemble-per-gpu` is BASELINE configs[4] in its 8-GPU topology instead: one ensemble member per rank, the dense
 pre-NMS tensors exchanged point-to-point onto a rotating merge rank (pod_compare_amd.ensemble_dist.MemberPipeline).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what rank 0's last timed step computed as DIR/<name>.npy (float32):
+with the same arguments the inputs are the same on every run, so two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -56,6 +57,7 @@ FRAME_HW = (720, 1280)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP32_MFMA_PEAK_TF = 157.3    # MI355X_MICROARCH.md: dense fp32 matrix peak (no xf32 / tf32 on gfx950)
 BF16_MFMA_PEAK_TF = 2500.0   # MI355X_MICROARCH.md: dense bf16 / f16 matrix peak (16 x the fp32 rate)
+DUMP_BUDGET = 64 << 20       # bytes, all files of --dump-outputs together
 SPLIT_PRODUCTS = 3           # 16-bit partial products per fp32 product of the split kernels (round 5: 2-way f16 splits; rounds 3-4: 6, 3-way bf16)
 
 
@@ -105,9 +107,56 @@ def parse_args():
     ap.add_argument("--cpu-images", type=int, default=256, help="upper bound; the CPU leg stops after ~12 s of CPU work")
     ap.add_argument("--k1-traffic-bytes", type=float, default=None,
                     help="HBM bytes per K1 launch from the rocprofv3 PMC passes (profiles/): 2*FETCH_SIZE + WRITE_SIZE")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed on rank 0 as DIR/<name>.npy (float32): the "
+                         "detections (det_*, the first det_count rows) and the conv net's head outputs (head<member>_<field>_p<level>; "
+                         "whole, or a fixed seeded sample of elements when the head outputs exceed the %d MB budget)" % (DUMP_BUDGET >> 20))
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.split_bf16 = not a.fp32_mfma
     return a
+
+
+def dump_outputs(dirname, dets, heads=(), cls_side_only=False):
+    """--dump-outputs: `dets` = {name: tensor} written whole; `heads` = the HeadOutputs of the step's conv net (one per ensemble member),
+    written whole when they fit in the budget, otherwise as the elements at a fixed seeded set of flat indices per tensor (sorted; the
+    same set for the same shape and name on every run).  Run N-1 of cls / cls_var / reg_var is left out when the net did not compute it
+    (skip_unused_last_run); cls_side_only: the sparse bbox tower's step, whose box planes are computed only where a candidate can be."""
+    import zlib
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().contiguous() for k, v in dets.items()}
+    big = {}
+    for j, ho in enumerate(heads):
+        for field in ("cls", "delta", "cls_var", "reg_var"):
+            planes = getattr(ho, field)
+            if planes is None or (cls_side_only and field in ("delta", "reg_var")):
+                continue
+            for lv, t in enumerate(planes):
+                if field != "delta" and not ho.last_run_valid:
+                    t = t[:-1]
+                big["head%d_%s_p%d" % (j, field, lv + 3)] = t
+    room = DUMP_BUDGET - sum(4 * v.numel() for v in arrays.values())
+    fits = 4 * sum(t.numel() for t in big.values()) <= room
+    cap = room // 4 // max(1, len(big))
+    for name, t in big.items():
+        flat = t.detach().reshape(-1)
+        if not fits and flat.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randperm(flat.numel(), generator=g)[:cap].sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[name] = flat.float().cpu()
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), v.numpy())
+    return sorted(arrays)
+
+
+def detection_arrays(det):
+    """The arrays a caller of the hot path receives for one image (hotpath.DeviceDetections), cut to its detection count."""
+    m = det.count()
+    return {"det_count": det.n_det.reshape(1), "det_boxes": det.boxes[:m], "det_cov": det.cov[:m], "det_scores": det.scores[:m],
+            "det_classes": det.classes[:m], "det_probs": det.probs[:m], "det_records": det.records[:m]}
 
 
 def relaunch(args):
@@ -353,7 +402,8 @@ def run_ensemble_per_gpu(args, spec, world, rank, dev):
         dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-    return dt, len(ids)
+    last = {"det_count": cnts[-1].reshape(1), "det_records": recs[-1][:int(cnts[-1].item())]} if ids else {}
+    return dt, len(ids), last
 
 
 def main():
@@ -412,7 +462,9 @@ def main():
             raise SystemExit("--ensemble-per-gpu is BASELINE configs[4]: --config cfg5 and --gpus >= %d" % spec["members"])
         # (backend nccl = RCCL moves the packed device buffers directly; any other backend stages rows through pinned host
         #  memory: the functional check on a single-GPU box, POD_BENCH_BACKEND=gloo POD_BENCH_SHARE_GPU=1)
-        dt, merged_here = run_ensemble_per_gpu(args, spec, world, rank, dev)
+        dt, merged_here, last = run_ensemble_per_gpu(args, spec, world, rank, dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
         t = stage(torch.tensor([dt], device=dev, dtype=torch.float64))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
@@ -462,6 +514,7 @@ def main():
     mc = N > 1 and spec["dropout"] > 0.0
 
     sparse_state = {"on": bool(args.sparse_bbox), "heads": heads}
+    dump_last = {"heads": []} if args.dump_outputs else None      # --dump-outputs: the conv net's outputs of the latest step
     if args.sparse_bbox and (len(members) > 1 or args.no_cnn):
         raise SystemExit("--sparse-bbox: single-model configurations with the conv net in the step")
 
@@ -478,7 +531,9 @@ def main():
             def hook(partial):
                 hps[s].select(h.cls, h.cls_var)
                 return sparse.LiveBlocks(hps[s])
-            model(modeling.resize_test_image(frames[i % n_img]), num_mc_dropout_runs=N, skip_unused_last_run=params.merge_quirk, sparse_bbox=hook)
+            ho = model(modeling.resize_test_image(frames[i % n_img]), num_mc_dropout_runs=N, skip_unused_last_run=params.merge_quirk, sparse_bbox=hook)
+            if dump_last is not None:
+                dump_last["heads"] = [ho]
             return hps[s].finish(spec["mode"], h.cls, h.delta, h.cls_var, h.reg_var, net_hw, FRAME_HW)
 
     def step(i):
@@ -491,10 +546,11 @@ def main():
                 # conv net: run and timed; output discarded (see docstring).  The hot path runs with the reference's merge
                 # quirk, which never reads the last run's cls / cls_var / reg_var, so the head does not compute them.
                 if len(members) > 1:
-                    for mm in members:                                 # PI:498-500: one full forward per ensemble member
-                        mm(img)
+                    hos = [mm(img) for mm in members]                  # PI:498-500: one full forward per ensemble member
                 else:
-                    model(img, num_mc_dropout_runs=N, skip_unused_last_run=params.merge_quirk)
+                    hos = [model(img, num_mc_dropout_runs=N, skip_unused_last_run=params.merge_quirk)]
+                if dump_last is not None:
+                    dump_last["heads"] = hos
             h = heads[i % n_img]
             # K1 .. K7 of the image, enqueued by one C call (pod_run_image); fresh Philox draws per image
             return hps[s].run(spec["mode"], h.cls, h.delta, h.cls_var, h.reg_var, image_size=net_hw, out_size=FRAME_HW)
@@ -546,6 +602,9 @@ def main():
         barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if dump_last is not None and rank == 0:
+            # before any later leg: a graph replay on the last step's stream would overwrite its head outputs
+            dump_outputs(args.dump_outputs, detection_arrays(dets[-1]), dump_last["heads"], cls_side_only=bool(args.sparse_bbox))
     per_rank = [args.steps / t_images]
     if multi:
         t = stage(torch.tensor([dt, flush_ms, t_images, host_enqueue_ms], device=dev, dtype=torch.float64))

@@ -150,6 +150,23 @@ def main_metrics():
     print(counts, avg, "->", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
+def main_preprocess():
+    """tests/golden/eval_preprocess.npz: EU:19-73 (eval_predictions_preprocess) on the JSON records of the cfg* predictor fixtures,
+    the input tests/test_eval_matching.py builds (its `_json_instances`)."""
+    from tests.test_eval_matching import _json_instances
+    eu, _ = load_reference_evaluation()
+    ref = eu.eval_predictions_preprocess(_json_instances(), min_allowed_score=0.3)
+    keys = sorted(ref["predicted_boxes"])
+    out = {"keys": np.array(keys, dtype=np.int64)}
+    for name in ("predicted_boxes", "predicted_cls_probs", "predicted_covar_mats"):
+        for k in keys:
+            out["%s__%d" % (name, k)] = ref[name][k].cpu().numpy()
+    path = os.path.join(ROOT, "tests", "golden", "eval_preprocess.npz")
+    np.savez_compressed(path, **out)
+    print(len(keys), "images ->", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     main()
     main_metrics()
+    main_preprocess()

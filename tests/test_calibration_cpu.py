@@ -35,18 +35,6 @@ def test_errors_equal_the_references_main_on_the_same_partitions():
     assert "0.4117" in format_table(res)
 
 
-def test_fixture_regenerates_from_the_reference():
-    from oracle.refimport import reference_available
-    if not reference_available():
-        import pytest
-        pytest.skip("reference tree absent")
-    from oracle import make_golden_calib as gen
-    z, _ = load()
-    cap = gen.run_reference(gen.seeded_matched_results(k=int(z["num_classes"])), int(z["num_classes"]))
-    assert cap["row"] == [str(s) for s in z["row"]]
-    assert np.array_equal(cap["cal_probs"], z["cal_probs"])
-
-
 def test_marginal_calibration_error_properties():
     """The restated package function: a calibrated score has (debiased) error ~0, a constant shift by d has error ~d, duplicated scores
     take the discrete path, bad labels are rejected."""

@@ -1,9 +1,10 @@
-"""BASELINE configs[4] in its 8-GPU topology, end to end on ONE GPU: 6 processes (5 ensemble members + 1 merge-only rank,
-all on cuda:0) run apply_net.EnsemblePerGpu -- member forward, packed rows exchanged through the pipelined point-to-point
+"""BASELINE configs[4] in its 8-GPU topology, end to end on ONE GPU: 6 ranks (5 ensemble members + 1 merge-only rank,
+all on cuda:0; rank 0 is the test process itself) run apply_net.EnsemblePerGpu -- member forward, packed rows exchanged through the pipelined point-to-point
 schedule (gloo, rows staged through pinned host memory because gloo cannot move device buffers; RCCL moves them directly),
 K1 streaming the received (5, packed) buffer in place as run-strided views, K2..K7 on the rotating merge rank.
 Members are deterministic stand-ins that return run s of the golden cfg5 fixture, so every image's detections must equal
 the REFERENCE's recorded output for that fixture (PI:483-505), whichever rank merged it."""
+import datetime
 import json
 import os
 
@@ -17,6 +18,7 @@ from tests.helpers import GOLDEN, Golden
 pytestmark = pytest.mark.gpu
 CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pod_compare_amd", "configs")
 FIXTURE = "cfg5_ensembles_pre_nms_s51"
+TIMEOUT = datetime.timedelta(minutes=5)      # a rank that died must not leave the others (the test process among them) waiting
 
 
 class _Member:
@@ -53,9 +55,9 @@ def _worker(rank, world, port, num_images, tmp, backend="gloo", own_gpu=False):
     dev_index = rank if own_gpu else 0
     torch.cuda.set_device(dev_index)
     if backend == "nccl":
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev_index))
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev_index), timeout=TIMEOUT)
     else:
-        dist.init_process_group(backend, rank=rank, world_size=world)
+        dist.init_process_group(backend, rank=rank, world_size=world, timeout=TIMEOUT)
     g = Golden(os.path.join(GOLDEN, FIXTURE + ".npz"))
     cfg = config.setup_config(CFG + "/BDD-Detection/retinanet/retinanet_R_50_FPN_1x_reg_cls_var.yaml", CFG + "/Inference/ensembles_pre_nms.yaml")
     cfg.MODEL.DEVICE = "cuda:%d" % dev_index
@@ -82,11 +84,34 @@ def _worker(rank, world, port, num_images, tmp, backend="gloo", own_gpu=False):
     dist.destroy_process_group()
 
 
+def _spawned_worker(i, *args):
+    _worker(i + 1, *args)
+
+
 def run_pipeline(tmp_path, backend="gloo", own_gpu=False):
+    """Rank 0 runs in this process, which already has the GPU open; only ranks 1 .. world-1 are started, so the pipeline adds
+    world - 1 processes to the device and never more than `world` processes hold it at once."""
     g = Golden(os.path.join(GOLDEN, FIXTURE + ".npz"))
     world, num_images = g.spec["runs"] + 1, 8
     port = 34500 + (os.getpid() % 2000)
-    mp.spawn(_worker, args=(world, port, num_images, str(tmp_path), backend, own_gpu), nprocs=world, join=True)
+    args = (world, port, num_images, str(tmp_path), backend, own_gpu)
+    saved = {k: os.environ.get(k) for k in ("MASTER_ADDR", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY")}
+    ctx = mp.spawn(_spawned_worker, args=args, nprocs=world - 1, join=False)
+    try:
+        _worker(0, *args)
+        while not ctx.join():
+            pass
+    finally:
+        if dist.is_initialized():          # rank 0 failed half-way: the test process must not keep its process group
+            dist.destroy_process_group()
+        for p in ctx.processes:
+            if p.is_alive():
+                p.terminate()
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     ref_b, ref_c, ref_s, ref_k = g.t("pred_boxes"), g.t("pred_boxes_covariance"), g.t("scores"), g.t("pred_classes")
     seen = []
     for r in range(world):

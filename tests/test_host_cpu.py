@@ -14,7 +14,6 @@ from pod_compare_amd.structures import Boxes, Instances
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CFG = os.path.join(os.path.dirname(HERE), "pod_compare_amd", "configs")
-REF_CFG = "/root/reference/src/configs"
 
 
 def test_baseline_geometry():
@@ -46,27 +45,23 @@ def test_configs_load_with_reference_keys():
     assert d.PROBABILISTIC_INFERENCE.ENSEMBLES.RANDOM_SEED_NUMS == [0, 1000, 2000, 3000, 4000]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present")
 def test_own_yamls_equal_reference_yamls():
-    """Every model x inference YAML pair gives the same MODEL / PROBABILISTIC_INFERENCE values as the reference's
-    own files (read in place; the `eval` tag of Base-RetinaNet.yaml:8 is replaced by literal sizes, never evaluated)."""
-    def flat(d, p=""):
-        out = {}
-        for k, v in d.items():
-            if isinstance(v, dict):
-                out.update(flat(v, p + k + "."))
-            else:
-                out[p + k] = [list(x) if isinstance(x, (list, tuple)) else x for x in v] if isinstance(v, (list, tuple)) else v
-        return out
+    """Every model x inference YAML pair gives the same MODEL / PROBABILISTIC_INFERENCE values as the reference's own files
+    (tests/golden/reference_configs.json: those files read by config.setup_config, oracle/make_golden_configs.py; the `eval` tag of
+    Base-RetinaNet.yaml:8 is replaced by literal sizes, never evaluated)."""
+    from oracle.make_golden_configs import SECTIONS, pair_values
+    with open(os.path.join(HERE, "golden", "reference_configs.json")) as f:
+        ref = json.load(f)
     n = 0
-    for m in glob.glob(REF_CFG + "/BDD-Detection/retinanet/retinanet*.yaml"):
-        for i in glob.glob(REF_CFG + "/Inference/*.yaml"):
-            a = config.setup_config(m, i)
-            b = config.setup_config(m.replace(REF_CFG, CFG), i.replace(REF_CFG, CFG))
-            for sect in ("MODEL", "PROBABILISTIC_INFERENCE"):
-                assert flat(a[sect]) == flat(b[sect]), (m, i)
+    for m in glob.glob(CFG + "/BDD-Detection/retinanet/retinanet*.yaml"):
+        for i in glob.glob(CFG + "/Inference/*.yaml"):
+            mr, ir = os.path.relpath(m, CFG), os.path.relpath(i, CFG)
+            want = ref[mr + " + " + ir]
+            got = json.loads(json.dumps(pair_values(CFG, mr, ir)))        # the golden's JSON types: tuples -> lists
+            for sect in SECTIONS:
+                assert got[sect] == want[sect], (mr, ir, sect)
             n += 1
-    assert n == 32
+    assert n == len(ref) == 32
 
 
 def test_unknown_meta_architecture_and_mode_raise():
