@@ -10,7 +10,7 @@
  *
  * Conventions
  *   - every pointer marked "dev" is a DEVICE pointer (HBM); everything else is host memory;
- *   - all floating point is fp32, anchor indices int32, class ids int32 (the Python
+ *   - all floating point is fp32 (the COCO evaluation entries, K17: fp64), anchor indices int32, class ids int32 (the Python
  *     boundary widens them to the reference's int64);
  *   - outputs and scratch are caller-allocated; the library never allocates device memory,
  *     never synchronises the device and holds no global state; distinct streams may be used
@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define POD_ABI_VERSION 14
+#define POD_ABI_VERSION 15
 #define POD_MAX_LEVELS 8
 #define POD_MAX_CLASSES 16       /* K: BDD = 7 (Base-BDD-RetinaNet.yaml:11-12) */
 #define POD_MAX_RUNS 64          /* MC-dropout runs / ensemble members */
@@ -50,6 +50,12 @@ extern "C" {
 #define POD_MAX_CLS_SAMPLES 64   /* CLS_VAR_LOSS.NUM_SAMPLES (10 in the reg_cls_var yamls) */
 #define POD_MAX_CANDIDATES 8192  /* n = sum over levels of kept top-k; 5 x 1000 at BASELINE */
 #define POD_MAX_DETECTIONS 128   /* model.max_detections_per_image (100) */
+#define POD_COCO_MAX_IOU 16      /* COCO evaluation: IoU thresholds (pycocotools Params: 10) */
+#define POD_COCO_MAX_REC 128     /*   recall thresholds (101) */
+#define POD_COCO_MAX_AREA 4      /*   area ranges (all / small / medium / large) */
+#define POD_COCO_MAX_MAXDET 4    /*   maxDets entries ([1, 10, 100]) */
+#define POD_COCO_MAX_KEEP 128    /*   detections kept per (image, category): maxDets[-1] (100) */
+#define POD_COCO_LDS_GT 64       /*   ground-truth boxes per (image, category) whose IoU matrix fits LDS; more use scratch */
 
 #define POD_OK 0
 #define POD_E_INVALID (-1)       /* bad argument / unsupported size */
@@ -485,6 +491,45 @@ int pod_match_groundtruth(const float* det_boxes, const float* det_probs, const 
  * Replaces: compute_reg_scores core/evaluation_tools/scoring_rules.py:68-74
  * (-MVN(mean, cov + 1e-2 I).log_prob(gt), the "NLL parity" half of the metric). */
 int pod_reg_nll(const float* means, const float* covs, const float* gt, int32_t n, float* nll, pod_stream_t stream);
+
+/* ---- K17  COCO bbox evaluation (offline average precision) -------------------------------------
+ * Replaces: pycocotools COCOeval.evaluate / evaluateImg (cocoeval.py, the per image x category x area-range greedy match) and
+ * COCOeval.accumulate (the per category x area x maxDets x IoU-threshold precision / recall / score tables), which
+ * compute_average_precision.py AP:41-43 runs for iouType 'bbox' with the default Params.  fp64 throughout, numpy's arithmetic:
+ * the results equal a numpy restatement bit for bit.  summarize() and the F-1 threshold (AP:43-59) stay on the host. */
+typedef struct PodCocoParams {
+    int32_t n_iou, n_rec, n_area, n_maxdet;   /* T <= 16 (T * A <= 64), R <= 128, A <= 4, M <= 4 */
+    int32_t n_cat;               /* K: evaluated category ids (params.catIds, AP:38) */
+    int32_t reserved;
+    double iou_thrs[POD_COCO_MAX_IOU];        /* np.linspace(.5, .95, 10), generated by the caller */
+    double rec_thrs[POD_COCO_MAX_REC];        /* np.linspace(0, 1, 101), ascending */
+    double area_rng[2 * POD_COCO_MAX_AREA];   /* [lo, hi] per range */
+    int32_t max_dets[POD_COCO_MAX_MAXDET];    /* ascending; the last one cuts every (image, category) */
+} PodCocoParams;
+
+/* evaluateImg for every (image, category) pair with a ground-truth box or a detection, one workgroup each.
+ * pairs   : dev int64[n_pairs][8] = {category index k, image position, gt_off, gt_n, dt_off, dt_n, out_off, scratch_off},
+ *           sorted by (k, image position in sorted imgIds); a pair's boxes are contiguous, in annotation / result-file order.
+ * dt_*    : dev, detections (xywh fp64 boxes, fp64 scores); gt_*: dev, ground truth (xywh, `area`, iscrowd, id).
+ * scratch : dev, pairs with gt_n > POD_COCO_LDS_GT keep their IoU matrix at scratch + scratch_off,
+ *           pod_coco_eval_scratch_bytes(min(dt_n, maxDets[-1]), gt_n) bytes (0 for the others).
+ * kept_*  : dev, min(dt_n, maxDets[-1]) entries per pair at out_off, in score order: score, rank, and bit (a * T + t) of
+ *           kept_match (matched to a ground-truth id != 0: pycocotools' dtm) and kept_ignore (dtIgnore).
+ * npig    : dev int32[K * A], non-ignored ground truth per (category, area); zeroed by this call. */
+size_t pod_coco_eval_scratch_bytes(int32_t n_keep, int32_t n_gt);
+int pod_coco_eval_images(const PodCocoParams* prm, const int64_t* pairs, int32_t n_pairs, const double* dt_boxes,
+                         const double* dt_score, const double* gt_boxes, const double* gt_area, const int32_t* gt_crowd,
+                         const int64_t* gt_id, void* scratch, double* kept_score, uint64_t* kept_match, uint64_t* kept_ignore,
+                         int32_t* kept_rank, int32_t* npig, pod_stream_t stream);
+
+/* accumulate over pod_coco_eval_images' outputs.  cat_off: dev int64[K + 1], category k's kept detections are
+ * [cat_off[k], cat_off[k+1]) (the pair order makes them contiguous); max_seg: the largest of those counts.
+ * workspace: dev, pod_coco_accumulate_workspace_bytes(n_kept) bytes, 256-byte aligned.
+ * precision, scores: dev fp64 [T][R][K][A][M]; recall: dev fp64 [T][K][A][M] (pycocotools' eval layouts, -1 where npig == 0). */
+size_t pod_coco_accumulate_workspace_bytes(int64_t n_kept);
+int pod_coco_accumulate(const PodCocoParams* prm, const int64_t* cat_off, int32_t max_seg, int64_t n_kept, const double* kept_score,
+                        const uint64_t* kept_match, const uint64_t* kept_ignore, const int32_t* kept_rank, const int32_t* npig,
+                        void* workspace, double* precision, double* recall, double* scores, pod_stream_t stream);
 
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */

@@ -150,9 +150,12 @@ def main(argv=None):
     ap.add_argument("--gt", required=True, help="COCO-format ground truth json (its `annotations`)")
     ap.add_argument("--iou-min", type=float, default=0.1)
     ap.add_argument("--iou-correct", type=float, default=0.7)
-    ap.add_argument("--min-allowed-score", type=float, default=0.0)
+    ap.add_argument("--min-allowed-score", type=float, default=None, help="score threshold of the detections (default: from --map-results, else 0.0)")
+    ap.add_argument("--map-results", default="", help="mAP_res.txt of compute_average_precision: its optimal-F1 score threshold, rounded to 4 decimals, is the min allowed score (CE:50-62)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
+    from .compute_average_precision import resolve_min_allowed_score
+    args.min_allowed_score = resolve_min_allowed_score(args.min_allowed_score, args.map_results)
     with open(args.results, "r") as f:
         predicted = json.load(f)
     with open(args.gt, "r") as f:
