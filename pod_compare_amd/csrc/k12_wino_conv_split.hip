@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
     const float sgn = a == 1 ? 1.0f : -1.0f;
     // Patch in LDS, one stage per SUPER-CHUNK of 32 input channels = the 128-byte line a pixel owns in the channels-last source:
     // [pixel slot][8 parts of 16 B], so that 8 consecutive lanes of an LDS-DMA instruction fetch ONE full line (measured,
-    // tools/mfma_fillers.hip: a pixel per lane -- 64 lines per instruction, each line fetched again by the next three 8-channel
+    // profiles/r03_experiments.md: a pixel per lane -- 64 lines per instruction, each line fetched again by the next three 8-channel
     // chunks -- stalls the in-order instruction streams by ~400 cycles per chunk once the lines come from HBM; full lines cost 55).
     // Pixel slot of patch pixel (py, px): 2 (rank(py) 18 + px) + ((py >> 2) & 1), rank = (py & 3) + 4 (py >> 3) (rows 0-3, 8-11, 16, 17
     // on the even slots, rows 4-7, 12-15 on the odd ones); part P of that pixel sits at sub-slot (P + rot) & 7,
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
                  "+v"(x[8]), "+v"(x[9]), "+v"(x[10]), "+v"(x[11]))
     // Row a of V = Bt4 d Bt6^T for the lane's tile and 4 channels -- the SAME operations in the same order as the fp32 kernel's
     // packed transform (fused multiply-adds where it has them), but as scalar instructions (this file is compiled with
-    // -fno-slp-vectorize): beside bf16 MFMAs a packed fp32 instruction costs ~40 cycles (tools/mfma_bf16_split.hip), an ordinary one
+    // -fno-slp-vectorize): beside bf16 MFMAs a packed fp32 instruction costs ~40 cycles (profiles/r04_experiments.md), an ordinary one
     // nothing --, then every value split into three bf16 terms by round-to-nearest (v = v0 + v1 + v2 to 2^-26 |v|; truncation would
     // make the dropped partial products one-signed: a bias the Winograd cancellation amplifies -- measured) and packed pairwise.
     //
@@ -747,7 +747,7 @@ static int wino_split_prepare() {        // the kernel's dynamic LDS size, once 
 extern "C" int pod_wino_conv3x3_split(const PodWinoConv* d, pod_stream_t stream) {
     if (!d || d->n_sets < 1 || d->n_sets > 4 || !d->blocks || d->n_blocks < 0 || d->C < 16 || (d->C & 15) != 0 || d->K < 64 || (d->K & 63) != 0 ||
         !(d->p >= 0.0f && d->p < 1.0f) || d->sets[0].first_block != 0 || (reinterpret_cast<uintptr_t>(d->blocks) & 15u) != 0 ||
-        (d->form != 0 && d->form != POD_WINO_FORM_4 && d->form != POD_WINO_FORM_8))
+        d->reserved != 0)
         return POD_E_INVALID;
     const int32_t C = d->C, K = d->K, KS = K / 64;
     if (KS != 1 && KS != 2 && KS != 4 && KS != 8) return POD_E_INVALID;
@@ -786,13 +786,6 @@ extern "C" int pod_wino_conv3x3_split(const PodWinoConv* d, pod_stream_t stream)
     P.live = d->live_blocks;
     const int64_t grid = pod::wino_grid(KS, d->n_blocks);
     if (grid > 0x7FFFFFFFLL) return POD_E_INVALID;
-    if (d->form == POD_WINO_FORM_8) {                   // round 6's experiment build only (tools/experiments/k16_wino_conv_split8.hip: measured 5 - 8 % slower)
-#ifdef POD_WITH_K16
-        return pod::wino_split8_launch(P, grid, partial ? (unsigned)d->n_splits : 1u, (hipStream_t)stream);
-#else
-        return POD_E_INVALID;
-#endif
-    }
     hipLaunchKernelGGL(pod::k_wino_conv3x3_split, dim3((unsigned)grid, partial ? (unsigned)d->n_splits : 1u), dim3(256), pod::WINO_LDS_BYTES, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     return POD_OK;

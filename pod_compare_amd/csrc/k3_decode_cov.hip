@@ -178,7 +178,7 @@ extern "C" int pod_gather_decode(const PodConfig* cfg, const PodLevel* levels, c
     Dp.seed = cfg->philox_seed; Dp.n_total = n_total; Dp.cand_delta = cand_delta; Dp.cand_reg_var = cand_reg_var;
     Dp.cand_anchor = cand_anchor; Dp.cand_run_delta = cand_run_delta; Dp.cand_anchor_idx = cand_anchor_idx;
     Dp.cand_level = cand_level; Dp.eps_prop = nullptr; Dp.boxes = boxes; Dp.cov = cov;
-    P.small_max = pod::K23_SMALL_MAX;   // swept 1024 / 2048 / 3072 / 8192 over n = 490 .. 4594 (tools/sweep_candidates.py): flat up to
+    P.small_max = pod::K23_SMALL_MAX;   // swept 1024 / 2048 / 3072 / 8192 over n = 490 .. 4594 (profiles/r02_candidate_sweep.md): flat up to
                                         // ~2000, above that the one-wavefront shape wins by up to 30 us
     hipLaunchKernelGGL(pod::k23_gather_decode, dim3(cfg->n_levels * cfg->topk), dim3(pod::K23_THREADS), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();

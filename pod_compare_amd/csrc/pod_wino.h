@@ -58,8 +58,9 @@ struct WinoParams {
     // dropout masks of a REPLAYED launch (HIP graph): the Philox key is seed ^ mix(*epoch), epoch a device word the graph itself bumps
     // at the start of every replay -- seed and offset are launch arguments, i.e. constants of a captured launch.  null: key = seed.
     const uint64_t* epoch;
-    // Sparse launch (round 5, k15_sparse_blocks.hip): null, or a device list {count, record indices ...} of the LIVE blocks: workgroup slot t
-    // takes record live[1 + t] and slots >= live[0] exit at once (the grid is sized for the whole table: the count never visits the host).
+    // Sparse launch (k15_sparse_blocks.hip): null, or pod_sparse_live_blocks' device list of the LIVE blocks: live[0] = count, then from
+    // word POD_SPARSE_LIVE_HEAD one entry of POD_SPARSE_LIVE_STRIDE words each, {record, 11 words of need bits} (include/pod_mi355x.h).
+    // Workgroup slot t takes entry t and slots >= live[0] exit at once (the grid is sized for the whole table: the count never visits the host).
     const int32_t* live;
     // the store pass writes `replicas` copies of the image (pod_wino_conv3x3_split_replicas: channels-last, one input image per record),
     // replica r as image r of the output canvas, each under its own dropout mask -- the mask pod_expand_dropout would draw for it.  1: off.
@@ -212,9 +213,6 @@ __device__ __forceinline__ float wino_reduce_amax(float v) {                    
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 __device__ __forceinline__ float wino_read_amax(const float* rec) { return wino_reduce_amax(wino_load_amax(rec)); }
-
-// the eight-wavefront form of pod_wino_conv3x3_split (tools/experiments/k16_wino_conv_split8.hip, -DPOD_WITH_K16 builds); P as k12's entry validated and filled it
-int wino_split8_launch(const WinoParams& P, int64_t grid, unsigned grid_y, hipStream_t stream);
 
 template <typename F, int... Js>
 __device__ __forceinline__ void wino_static_for(F&& f, std::integer_sequence<int, Js...>) {

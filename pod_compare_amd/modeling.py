@@ -179,21 +179,25 @@ def _weight_for(conv: nn.Conv2d, channels_last: bool) -> torch.Tensor:
 WINO_HEAD = True              # GPU only: the head subnets' 3x3 convs on pod_wino_conv3x3 (all levels, all runs per launch)
 WINO_BACKBONE = __import__("os").environ.get("POD_WINO_BACKBONE", "1") != "0"   # GPU only: the bottlenecks' and the FPN's 3x3 / stride-1 convs on pod_wino_conv3x3 too (batch 1: few
                               # workgroups per launch, but a third of MIOpen's CU-time per FLOP -- the other streams' images fill the idle CUs)
-WINO_BACKBONE_MIN_CELLS = int(__import__("os").environ.get("POD_WINO_MIN_CELLS", "0"))   # (experiment knob: smaller maps stay on MIOpen)
 NHWC_TRUNK_MIN_CELLS = 8192   # head trunks of maps at least this large run channels-last (p3 of a 768x1344 input: 16128)
+
+
+def _derived(conv: nn.Conv2d, attr: str, make, *extra_key):
+    """make(conv) -- a kernel's form of the conv's parameters -- cached on the conv as `attr`, rebuilt when the parameters (or extra_key) change."""
+    w, b = conv.weight, conv.bias
+    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) + extra_key
+    cached = getattr(conv, attr, None)
+    if cached is None or cached[0] != key:
+        cached = (key, make(conv))
+        torch.cuda.current_stream(w.device).synchronize()      # made once, then read from any stream
+        setattr(conv, attr, cached)
+    return cached[1]
 
 
 def wino_of(conv: nn.Conv2d):
     """The conv's Winograd-transformed filter (pod_wino_filter_transform), refreshed when the parameters change."""
     from . import wino
-    from .wino import WinoConv
-    key = (conv.weight.data_ptr(), conv.weight._version, None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version), wino.SPLIT_BF16)
-    cached = getattr(conv, "_pod_wino", None)
-    if cached is None or cached[0] != key:
-        cached = (key, WinoConv(conv.weight, conv.bias))
-        torch.cuda.current_stream(conv.weight.device).synchronize()      # made once, then read from any stream
-        conv._pod_wino = cached
-    return cached[1]
+    return _derived(conv, "_pod_wino", lambda c: wino.WinoConv(c.weight, c.bias), wino.SPLIT_BF16)
 
 
 def _wino_limits() -> int:
@@ -206,7 +210,7 @@ def wino_eligible(conv: Optional[nn.Conv2d], x: torch.Tensor) -> bool:
     return (WINO_BACKBONE and FUSE_CONV_TAIL and conv is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] == 1
             and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1) and conv.groups == 1
             and tuple(conv.dilation) == (1, 1) and conv.in_channels % 8 == 0 and conv.out_channels in (64, 128, 256, 512)
-            and x.shape[2] < 4096 and x.shape[3] < 4096 and x.shape[2] * x.shape[3] >= WINO_BACKBONE_MIN_CELLS
+            and x.shape[2] < 4096 and x.shape[3] < 4096
             and x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 4 <= _wino_limits())      # 32-bit offsets inside a canvas
 
 
@@ -225,87 +229,39 @@ def wino_conv_nchw(conv: nn.Conv2d, x: torch.Tensor, relu: bool, pre_bias: Optio
     return out
 
 
-_SIDE_STREAMS: Dict[Tuple[int, int], List["torch.cuda.Stream"]] = {}
-
-
-BRANCHES = set(x for x in __import__("os").environ.get("POD_GRAPH_BRANCHES", "").split(",") if x)    # which forks are taken: head, pred, fpn, shortcut
-
-
-def branches(fns, kind=""):
-    """Runs independent pieces of a forward: one after the other on the current stream -- or, for the kinds named in
-    POD_GRAPH_BRANCHES and while the forward is being CAPTURED into a HIP graph, each on its own stream, forked from and joined back
-    into the capturing stream, so that the graph holds them as parallel branches (a single-run head layer is 372 workgroups for 256
-    CUs, a predictor 93, an FPN output conv of p5 24: side by side they would fill the chip).  MEASURED (round 4, cfg2, images/s): no
-    branches 398; cls / bbox trunks 393; the four predictors 241; FPN output convs 277; bottleneck shortcuts 351 -- and 1.0 - 1.6 ms
-    of host time per replay instead of 0.13: ROCm's graph executor pays more for every fork / join than the idle CUs were worth.
-    Off by default; kept as the switch that reproduces the measurement."""
-    if len(fns) < 2 or kind not in BRANCHES or not torch.cuda.is_available() or not torch.cuda.is_current_stream_capturing():
-        return [f() for f in fns]
-    cur = torch.cuda.current_stream()
-    key = (cur.device.index or 0, cur.cuda_stream)
-    side = _SIDE_STREAMS.setdefault(key, [])
-    while len(side) < len(fns) - 1:
-        side.append(torch.cuda.Stream(device=cur.device))
-    outs = [None] * len(fns)
-    for st in side[:len(fns) - 1]:
-        st.wait_stream(cur)
-    for i, f in enumerate(fns[1:]):
-        with torch.cuda.stream(side[i]):
-            outs[i + 1] = f()
-    outs[0] = fns[0]()
-    for st in side[:len(fns) - 1]:
-        cur.wait_stream(st)
-    return outs
-
-
 # ---- channels-last backbone (round 4) ---------------------------------------------------------------------------------------
 # With the 3x3 convolutions on pod_wino_conv3x3[_split] (channels-last in and out) the 1x1 convolutions were what kept the backbone in
 # NCHW: MIOpen GEMM + one element-wise pass each for bias / residual / ReLU, plus a layout pass in front of every 3x3.  On
 # pod_conv1x1_split (csrc/k13_conv1x1_split.hip: channels-last GEMM, bias + residual + ReLU in the store, same exact-split products as
 # the 3x3 kernel) a bottleneck is three launches on (pixels, C) buffers and the whole trunk stays channels-last from the max-pool on.
 GROUPED_HEAD = __import__("os").environ.get("POD_GROUPED_HEAD", "1") != "0"         # layer l of the cls and the bbox subnet, and the four predictors, in one launch each
-FUSED_REPLICAS = __import__("os").environ.get("POD_FUSED_REPLICAS", "1") != "0"     # the first conv of an MC-dropout subnet stores its masked replicas itself
 CL_BACKBONE = __import__("os").environ.get("POD_CL_BACKBONE", "1") != "0"
-FUSED_PREPROCESS = __import__("os").environ.get("POD_FUSED_PREPROCESS", "1") != "0"   # ... which then also normalises and pads the frame on load
 HIP_P6P7 = __import__("os").environ.get("POD_HIP_P6P7", "1") != "0"         # FPN's p6 / p7 (3x3 / stride 2) as pod_im2col3x3s2_cl + pod_conv1x1_split instead of MIOpen
-FUSED_TOPDOWN = __import__("os").environ.get("POD_FUSED_TOPDOWN", "1") != "0"   # FPN's top-down map read at half resolution by the lateral conv's store (POD_C1_RESIDUAL_UP2) instead of F.interpolate
 HIP_STEM = __import__("os").environ.get("POD_HIP_STEM", "1") != "0"         # the 7x7 stem + max-pool of the channels-last trunk on pod_stem7x7_split / pod_maxpool3x3s2_cl
+
+
+def kernel_selection() -> tuple:
+    """Every switch that selects the kernels of a forward (part of the HIP-graph key: a graph captured under one selection must not answer for another)."""
+    from . import wino
+    return (WINO_HEAD, WINO_BACKBONE, GROUPED_HEAD, CL_BACKBONE, HIP_STEM, HIP_P6P7, FUSE_CONV_TAIL, NHWC_TRUNK_MIN_CELLS, bool(wino.SPLIT_BF16))
 
 
 def c1_of(conv: nn.Conv2d):
     """The conv's pod_conv1x1_split form (weight split once), refreshed when the parameters change."""
     from .conv1x1 import Conv1x1
-    key = (conv.weight.data_ptr(), conv.weight._version, None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
-    cached = getattr(conv, "_pod_c1", None)
-    if cached is None or cached[0] != key:
-        cached = (key, Conv1x1(conv.weight, conv.bias, conv.stride[0]))
-        torch.cuda.current_stream(conv.weight.device).synchronize()      # made once, then read from any stream
-        conv._pod_c1 = cached
-    return cached[1]
+    return _derived(conv, "_pod_c1", lambda c: Conv1x1(c.weight, c.bias, c.stride[0]))
 
 
 def stem_of(conv: nn.Conv2d):
     """The stem conv's pod_stem7x7_split form (weight split once), refreshed when the parameters change."""
     from .conv1x1 import Stem7x7
-    key = (conv.weight.data_ptr(), conv.weight._version, None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
-    cached = getattr(conv, "_pod_stem", None)
-    if cached is None or cached[0] != key:
-        cached = (key, Stem7x7(conv.weight, conv.bias))
-        torch.cuda.current_stream(conv.weight.device).synchronize()      # made once, then read from any stream
-        conv._pod_stem = cached
-    return cached[1]
+    return _derived(conv, "_pod_stem", lambda c: Stem7x7(c.weight, c.bias))
 
 
 def s2_of(conv: nn.Conv2d):
     """The conv's im2col + pod_conv1x1_split form (3x3 / stride 2: FPN's p6 / p7; weight re-laid and split once), refreshed when the parameters change."""
     from .conv1x1 import Conv3x3S2
-    key = (conv.weight.data_ptr(), conv.weight._version, None if conv.bias is None else (conv.bias.data_ptr(), conv.bias._version))
-    cached = getattr(conv, "_pod_s2", None)
-    if cached is None or cached[0] != key:
-        cached = (key, Conv3x3S2(conv.weight, conv.bias))
-        torch.cuda.current_stream(conv.weight.device).synchronize()      # made once, then read from any stream
-        conv._pod_s2 = cached
-    return cached[1]
+    return _derived(conv, "_pod_s2", lambda c: Conv3x3S2(c.weight, c.bias))
 
 
 def _c1_ok(conv: Optional[nn.Conv2d]) -> bool:
@@ -377,7 +333,8 @@ class Bottleneck(_TracksStorage):
         rconv = _plain_conv(self.shortcut)
         if rconv is None or rconv.bias is None or not (FUSE_CONV_TAIL and x.is_cuda and x.dtype == torch.float32):
             return conv_bias_act(self.conv3, main(), relu=True, residual_module=self.shortcut, residual_input=x)
-        out, raw = branches([main, lambda: shortcut_raw(rconv, x)], "shortcut")           # (parallel graph branches when captured)
+        out = main()
+        raw = shortcut_raw(rconv, x)
         return conv_bias_act(self.conv3, out, relu=True, residual_module=self.shortcut, residual_input=x, residual_raw=raw)
 
 
@@ -473,13 +430,10 @@ class FPN(_TracksStorage):
         l5 = self.lateral[2](c5)
         l4 = self.lateral[1](c4) + F.interpolate(l5, size=c4.shape[-2:], mode="nearest")
         l3 = self.lateral[0](c3) + F.interpolate(l4, size=c3.shape[-2:], mode="nearest")
-        out = lambda m, l: (lambda: wino_conv_nchw(m, l, relu=False) if wino_eligible(m, l) else m(l))
-
-        def top():
-            p6 = self.p6(c5)
-            return p6, self.p7(F.relu(p6))
-        p3, p4, p5, (p6, p7) = branches([out(self.output[0], l3), out(self.output[1], l4), out(self.output[2], l5), top], "fpn")
-        return [p3, p4, p5, p6, p7]
+        out = lambda m, l: wino_conv_nchw(m, l, relu=False) if wino_eligible(m, l) else m(l)
+        p3, p4, p5 = out(self.output[0], l3), out(self.output[1], l4), out(self.output[2], l5)
+        p6 = self.p6(c5)
+        return [p3, p4, p5, p6, self.p7(F.relu(p6))]
 
     def cl_eligible(self) -> bool:
         return all(_c1_ok(m) for m in self.lateral) and all(_w3_ok(m) for m in self.output)
@@ -491,7 +445,7 @@ class FPN(_TracksStorage):
         (c3, h3, w3), (c4, h4, w4), (c5, h5, w5) = feats
         l5 = c1_of(self.lateral[2])(c5, h5, w5)
         def lateral(conv, c, h, w, top, ht, wt):               # lateral + nearest-upsampled top-down map in one store
-            if FUSED_TOPDOWN and (ht, wt) == ((h + 1) // 2, (w + 1) // 2):      # a factor of two (every ResNet stage): read at (y >> 1, x >> 1), never materialised
+            if (ht, wt) == ((h + 1) // 2, (w + 1) // 2):      # a factor of two (every ResNet stage): read at (y >> 1, x >> 1), never materialised
                 return c1_of(conv)(c, h, w, residual=top, residual_up2=True)
             return c1_of(conv)(c, h, w, residual=nchw_as_cl(F.interpolate(cl_as_nchw(top, ht, wt), size=(h, w), mode="nearest")))
         l4 = lateral(self.lateral[1], c4, h4, w4, l5, h5, w5)
@@ -646,7 +600,7 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         # Philox offset for the whole buffer: the mask of an element is keyed by its index in `a`.
         self._drop_calls += 1
         p_first = 0.0 if replay else float(self.dropout_rate)
-        if first.split and copies <= 127 and FUSED_REPLICAS:
+        if first.split and copies <= 127:
             # ... by the conv's own store pass (pod_wino_conv3x3_split_replicas)
             tr = block_table(levels, 1, x0.device, out_copies=copies)
             first.replicas(x0, a, tr, copies, relu=True, dropout_p=p_first, seed=self.dropout_seed, offset=self._drop_calls << 34, epoch=self._epoch,
@@ -680,7 +634,7 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
 
     def _grouped_ok(self, *copies) -> bool:
         """Both subnets' launches in one grid (pod_wino_conv3x3_split_grouped): the split kernel, the replicas in the store pass."""
-        return (GROUPED_HEAD and FUSED_REPLICAS and not BRANCHES and all(1 <= c <= 127 for c in copies)
+        return (GROUPED_HEAD and all(1 <= c <= 127 for c in copies)
                 and all(self._wino(c).split for c in list(self.cls_subnet) + list(self.bbox_subnet)))
 
     def _trunks_grouped(self, x0: torch.Tensor, levels, copies_c: int, copies_b: int, dropout: bool):
@@ -872,8 +826,8 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
             if grouped:
                 tc, nc, tb, nb = self._trunks_grouped(x0, levels, cls_copies, box_copies, dropout)
             else:
-                (tc, nc), (tb, nb) = branches([lambda: self._trunk_all_levels(self.cls_subnet, x0, levels, cls_copies, dropout),
-                                               lambda: self._trunk_all_levels(self.bbox_subnet, x0, levels, box_copies, dropout)], "head")
+                tc, nc = self._trunk_all_levels(self.cls_subnet, x0, levels, cls_copies, dropout)
+                tb, nb = self._trunk_all_levels(self.bbox_subnet, x0, levels, box_copies, dropout)
             preds = [c for c in (self.cls_score, self.bbox_pred, self.cls_var if self.compute_cls_var else None, self.bbox_cov if self.compute_bbox_cov else None)
                      if c is not None]
             if grouped and len({self._wino(c).Kpad for c in preds}) == 1 and all(self._wino(c).split for c in preds):
@@ -902,10 +856,12 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                     delta_covs = self._predict_all_levels(self.bbox_cov, tb, levels, nb, n, m, n)
             else:
                 ex = (lambda ts: [t.expand(n, -1, -1, -1).contiguous() for t in ts]) if n > 1 else (lambda ts: ts)
-                pred = lambda conv, buf: (lambda: None if conv is None else ex(self._predict_all_levels(conv, buf, levels, 1, 0, 1, 1)))
-                logits, deltas, logit_vars, delta_covs = branches([pred(self.cls_score, tc), pred(self.bbox_pred, tb),
-                                                                   pred(self.cls_var if self.compute_cls_var else None, tc),
-                                                                   pred(self.bbox_cov if self.compute_bbox_cov else None, tb)], "pred")
+                pred = lambda conv, buf: ex(self._predict_all_levels(conv, buf, levels, 1, 0, 1, 1))
+                logits, deltas = pred(self.cls_score, tc), pred(self.bbox_pred, tb)
+                if self.compute_cls_var:
+                    logit_vars = pred(self.cls_var, tc)
+                if self.compute_bbox_cov:
+                    delta_covs = pred(self.bbox_cov, tb)
             return logits, deltas, (logit_vars if self.compute_cls_var else None), (delta_covs if self.compute_bbox_cov else None)
         for level, f in enumerate(features):
             tc = self._trunk(self.cls_subnet, f, cls_copies, dropout, level)
@@ -1057,14 +1013,13 @@ class ProbabilisticRetinaNet(_TracksStorage):
     def _forward_graphed(self, image: torch.Tensor, n: int, dropout: bool, skip: bool, part: str = "all"):
         stream = torch.cuda.current_stream(image.device)
         run = self._forward_eager if part == "all" else self._cls_eager
-        from . import wino
         fp = self._param_fingerprint()
         if fp != self._graphs_fingerprint:
             self._drop_graphs()
             self._fingerprint_tensors = None                   # (module surgery -- fold_frozen_bn -- also changes WHICH tensors there are)
             self._graphs_fingerprint = self._param_fingerprint()
         # (the kernel selection is part of the key: a graph captured with one convolution kernel must not answer for the other)
-        key = (stream.cuda_stream, tuple(image.shape), image.dtype, n, dropout, skip, bool(wino.SPLIT_BF16), CL_BACKBONE, WINO_BACKBONE, part)
+        key = (stream.cuda_stream, tuple(image.shape), image.dtype, n, dropout, skip, kernel_selection(), part)
         ent = self._graphs.get(key)
         if ent is None:
             # graphs are for (stream, shape) pairs that come back: the first GRAPH_AFTER_SEEN forwards of a key run eagerly (a data set of
@@ -1159,7 +1114,7 @@ class ProbabilisticRetinaNet(_TracksStorage):
 
     def _trunk_eager(self, image: torch.Tensor):
         """Frame -> (the five FPN maps, padded (h, w)): everything ahead of the head."""
-        if (FUSED_PREPROCESS and image.is_cuda and image.device == self.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
+        if (image.is_cuda and image.device == self.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
                 and image.dtype in (torch.uint8, torch.float32) and self._cl_backbone(self.pixel_mean) and self.bottom_up.hip_stem_ok()):
             # the frame as the loader hands it over: pod_stem7x7_split normalises ((x - mean) / std, PR:96) and pads on load
             padded = _anchors.padded_size(int(image.shape[1]), int(image.shape[2]))

@@ -186,6 +186,22 @@ def test_a_shape_is_captured_only_after_it_came_back():
     assert len(m._graphs) == 1
 
 
+def test_a_kernel_switch_flipped_between_forwards_gets_its_own_graph(monkeypatch):
+    """The graph key holds every kernel-selecting switch (modeling.kernel_selection): after HIP_STEM flips, the next forward of the same
+    frame is captured anew and equals the eager forward of the new selection, not a replay of the graph captured for the old one."""
+    m = build().enable_graphs()
+    f = torch.randint(0, 256, (3, 128, 160), dtype=torch.uint8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7))
+    m(f)
+    m(f)
+    assert len(m._graphs) == 1
+    monkeypatch.setattr(modeling, "HIP_STEM", not modeling.HIP_STEM)
+    got = [t.clone() for t in tensors(m(f))]
+    assert len(m._graphs) == 2
+    m.enable_graphs(False)
+    for x, y in zip(got, tensors(m(f))):                                # (one leg has the stem on MIOpen: agreement to rounding)
+        assert x.shape == y.shape and float((x - y).abs().max()) <= 2e-4 * max(1.0, float(y.abs().max()))
+
+
 def test_parity_mode_and_the_miopen_head_path_are_not_captured():
     m = build(dropout_rate=0.2).enable_graphs()
     f = torch.randint(0, 256, (3, 128, 160), dtype=torch.uint8, device="cuda")
