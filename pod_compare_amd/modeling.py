@@ -567,124 +567,95 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
     def _wino(self, conv: nn.Conv2d):
         return wino_of(conv)
 
-    def _trunk_all_levels(self, convs, x0: torch.Tensor, levels, copies: int, dropout: bool, live=None, bufs=None):
-        """`copies` evaluations of a subnet on ALL levels: one pod_wino_conv3x3 launch per conv layer (fp32 Winograd on the
-        matrix cores, bias + ReLU + dropout in its store) instead of one MIOpen call + one element-wise pass per level and
-        layer.  x0: (pixels of all levels, C) channels-last, level after level.  Returns (buffer, images per level): the last
-        activation as (pixels of all levels x images, C) channels-last, level after level -- `copies` images per level with
-        dropout, one without (every copy would be identical).
+    def _grouped_ok(self, *copies) -> bool:
+        """The subnets' launches in one grid (pod_wino_conv3x3_split_grouped): the split kernel, the replicas in the store pass."""
+        return (GROUPED_HEAD and all(1 <= c <= 127 for c in copies)
+                and all(self._wino(c).split for c in list(self.cls_subnet) + list(self.bbox_subnet)))
+
+    def _trunks(self, subnets, st: dict, live=None, bufs=None):
+        """Subnet evaluations on ALL levels, subnets: [(0 = cls / 1 = bbox, copies)].  One pod_wino_conv3x3 launch per conv layer (fp32
+        Winograd on the matrix cores, bias + ReLU + dropout in its store) instead of one MIOpen call + one element-wise pass per level and
+        layer; with st["grouped"] layer l of all the subnets in ONE launch (the kernel runs one workgroup per CU, so a launch costs whole
+        rounds of 256 workgroups: two launches of 1.5 rounds cost 4, one of 3.0 costs 3) -- the same buffers, tables, Philox offsets and
+        therefore the same bits as one launch per subnet.  st: `_plan`'s, x0 = the features as (pixels of all levels, C) channels-last,
+        level after level.  Returns per subnet (buffer, images per level): the last activation as (pixels of all levels x images, C)
+        channels-last, level after level -- `copies` images per level with dropout, one without (every copy would be identical).
         live (sparse bbox tower, pod_compare_amd/sparse.py): a LiveBlocks -- layer j is launched over the blocks of reach L - j only;
         bufs: `new(key, shape)` handing out the tower's re-used buffers (only live blocks are written; what dead blocks hold is never read)."""
         from . import hip
         from .sparse import DENSE_INPUT, reach_of_subnet_layer
-        from .wino import block_table, level_pixel_offsets
-        lib, C, L = hip.load(), x0.shape[1], len(convs)
-        t1 = block_table(levels, 1, x0.device)
-        off1 = level_pixel_offsets(levels, 1)
-        first = self._wino(convs[0])
-        # (keyword only when sparse: the convolution objects of the dense path -- a test's fp64 double among them -- need not know it)
-        # (layer 0 reads the FPN features, which are dense; layer j > 0 reads what layer j - 1 computed for THIS image and nothing else)
-        lv = (lambda table, layer: {}) if live is None else (
-            lambda table, layer: {"live": live(table, reach_of_subnet_layer(layer, L), DENSE_INPUT if layer == 0 else -1)})
-        new = (lambda key, shape: torch.empty(shape, dtype=x0.dtype, device=x0.device)) if bufs is None else bufs
-        if not dropout:
-            y = first(x0, new("t0", tuple(x0.shape)), t1, relu=True, **lv(t1, 0))
-            for j, conv in enumerate(convs[1:], 1):
-                y = self._wino(conv)(y, new("t%d" % (j & 1), tuple(y.shape)), t1, relu=True, **lv(t1, j))
-            return y, 1
-        offn = level_pixel_offsets(levels, copies)
-        a = new("a", (offn[-1], C))
-        replay = self.dropout_replay is not None
-        sid = 0 if convs is self.cls_subnet else 1
-        # The first activation is identical for every copy: computed once, stored `copies` times under the copies' dropout masks.  One
-        # Philox offset for the whole buffer: the mask of an element is keyed by its index in `a`.
-        self._drop_calls += 1
-        p_first = 0.0 if replay else float(self.dropout_rate)
-        if first.split and copies <= 127:
-            # ... by the conv's own store pass (pod_wino_conv3x3_split_replicas)
-            tr = block_table(levels, 1, x0.device, out_copies=copies)
-            first.replicas(x0, a, tr, copies, relu=True, dropout_p=p_first, seed=self.dropout_seed, offset=self._drop_calls << 34, epoch=self._epoch,
-                           **lv(tr, 0))
-        else:
-            assert live is None, "the sparse tower needs the split kernel's replica store"
-            # ... or by a pass of its own per level (the fp32-MFMA kernel; the same masks)
-            y = first(x0, torch.empty_like(x0), t1, relu=True)
-            for i, (h, w) in enumerate(levels):
-                hip.check(lib.pod_expand_dropout(y[off1[i]:].data_ptr(), a[offn[i]:].data_ptr(), h * w * C, copies, p_first, self.dropout_seed,
-                                                 (self._drop_calls << 34) + offn[i] * C // 8, self._epoch.data_ptr(), hip.current_stream()),
-                          "pod_expand_dropout")
-
-        def mask_in_place(buf, layer):              # parity mode: the recorded masks on the channels-last images of the buffer
-            for i, (h, w) in enumerate(levels):
-                v = buf[offn[i]:offn[i + 1]].view(copies, h, w, C)
-                v.copy_(self._replayed(v.permute(0, 3, 1, 2), sid, layer, i).permute(0, 2, 3, 1))
-
-        if replay:
-            mask_in_place(a, 0)
-        tn = block_table(levels, copies, x0.device)
-        b = new("b", tuple(a.shape))
-        for j, conv in enumerate(convs[1:], 1):
-            self._drop_calls += 1
-            self._wino(conv)(a, b, tn, relu=True, dropout_p=0.0 if replay else self.dropout_rate, seed=self.dropout_seed,
-                             offset=self._drop_calls << 34, epoch=self._epoch, **lv(tn, j))
-            if replay:
-                mask_in_place(b, j)
-            a, b = b, a
-        return a, copies
-
-    def _grouped_ok(self, *copies) -> bool:
-        """Both subnets' launches in one grid (pod_wino_conv3x3_split_grouped): the split kernel, the replicas in the store pass."""
-        return (GROUPED_HEAD and all(1 <= c <= 127 for c in copies)
-                and all(self._wino(c).split for c in list(self.cls_subnet) + list(self.bbox_subnet)))
-
-    def _trunks_grouped(self, x0: torch.Tensor, levels, copies_c: int, copies_b: int, dropout: bool):
-        """`_trunk_all_levels` of the cls and the bbox subnet with layer l of both in ONE launch (the kernel runs one workgroup per CU, so
-        a launch costs whole rounds of 256 workgroups: two launches of 1.5 rounds cost 4, one of 3.0 costs 3).  Same buffers, tables,
-        Philox offsets and therefore the same bits as the two separate trunks.  Returns (cls buffer, images, bbox buffer, images)."""
         from .wino import block_table, grouped_launch, level_pixel_offsets
-        subs, L, C, dev = (self.cls_subnet, self.bbox_subnet), len(self.cls_subnet), x0.shape[1], x0.device
-        if not dropout:
-            ys = [x0, x0]
-            t1 = block_table(levels, 1, dev)
-            for l in range(L):
-                outs = [torch.empty_like(x0), torch.empty_like(x0)]
-                grouped_launch([{"conv": self._wino(subs[i][l]), "src": ys[i], "dst": outs[i], "table": t1} for i in range(2)], relu=True)
-                ys = outs
-            return ys[0], 1, ys[1], 1
-        copies = (copies_c, copies_b)
-        replay = self.dropout_replay is not None
-        p = 0.0 if replay else float(self.dropout_rate)
-        ids = [[self._drop_calls + i * L + l + 1 for l in range(L)] for i in range(2)]       # the offsets the two separate trunks would draw
-        self._drop_calls += 2 * L
+        x0, levels, dropout, grouped = st["x0"], st["levels"], st["dropout"], st["grouped"]
+        L, C, dev = len(self.cls_subnet), x0.shape[1], x0.device
+        assert live is None or grouped, "the sparse tower needs the split kernel's grouped launches"
+        copies = [c if dropout else 1 for _, c in subnets]
         offn = [level_pixel_offsets(levels, c) for c in copies]
-        a = [torch.empty((offn[i][-1], C), dtype=x0.dtype, device=dev) for i in range(2)]
+        new = bufs or (lambda key, shape: torch.empty(shape, dtype=x0.dtype, device=dev))
+        a = [new("a%d" % i, (offs[-1], C)) for i, offs in enumerate(offn)]
+        b = [new("b%d" % i, (offs[-1], C)) for i, offs in enumerate(offn)]
+        tables = [block_table(levels, c, dev) for c in copies]
+        # With dropout the first activation is identical for every copy: computed once, stored `copies` times under the copies' dropout
+        # masks.  One Philox offset for the whole buffer: the mask of an element is keyed by its index in it.
+        firsts = [block_table(levels, 1, dev, out_copies=c) for c in copies] if dropout else tables
+        replay = dropout and self.dropout_replay is not None
+        kw = {"relu": True}
+        if dropout:
+            kw.update(dropout_p=0.0 if replay else float(self.dropout_rate), seed=self.dropout_seed, epoch=self._epoch)
+            base = self._drop_calls               # the offsets of the trunks one after the other: subnet i, layer l draws base + i L + l + 1
+            self._drop_calls += len(subnets) * L
+        for l in range(L):
+            sets = []
+            for i, (sid, c) in enumerate(subnets):
+                s = {"conv": self._wino((self.cls_subnet, self.bbox_subnet)[sid][l]), "src": a[i] if l else x0, "dst": b[i] if l else a[i],
+                     "table": tables[i] if l else firsts[i], "offset": (base + i * L + l + 1) << 34 if dropout else 0}
+                if dropout and l == 0:
+                    s["replicas"] = c
+                sets.append(s)
+            if grouped:
+                grouped_launch(sets, live=None if live is None else (lambda t: live(t, reach_of_subnet_layer(l, L), DENSE_INPUT if l == 0 else -1)), **kw)
+            else:
+                for i, s in enumerate(sets):
+                    conv = s["conv"]
+                    if "replicas" not in s:
+                        conv(s["src"], s["dst"], s["table"], offset=s["offset"], **kw)
+                    elif conv.split and s["replicas"] <= 127:     # the copies stored by the conv's own store pass (..._split_replicas)
+                        conv.replicas(s["src"], s["dst"], s["table"], s["replicas"], offset=s["offset"], **kw)
+                    else:                                          # or by a pass of their own per level (the fp32-MFMA kernel; the same masks)
+                        y = conv(x0, torch.empty_like(x0), block_table(levels, 1, dev), relu=True)
+                        off1 = level_pixel_offsets(levels, 1)
+                        for lv, (h, w) in enumerate(levels):
+                            hip.check(hip.load().pod_expand_dropout(y[off1[lv]:].data_ptr(), s["dst"][offn[i][lv]:].data_ptr(), h * w * C, s["replicas"],
+                                                                    kw["dropout_p"], self.dropout_seed, s["offset"] + offn[i][lv] * C // 8,
+                                                                    self._epoch.data_ptr(), hip.current_stream()), "pod_expand_dropout")
+            if replay:                                         # parity mode: the recorded masks on the channels-last images of the layer's output
+                for i, (sid, c) in enumerate(subnets):
+                    for lv, (h, w) in enumerate(levels):
+                        v = sets[i]["dst"][offn[i][lv]:offn[i][lv + 1]].view(c, h, w, C)
+                        v.copy_(self._replayed(v.permute(0, 3, 1, 2), sid, l, lv).permute(0, 2, 3, 1))
+            if l:
+                a, b = b, a
+        return [(a[i], c) for i, c in enumerate(copies)]
 
-        def mask_in_place(bufs, layer):             # parity mode: the recorded masks on the channels-last images of the buffers
-            for i in range(2):
-                for lv, (h, w) in enumerate(levels):
-                    v = bufs[i][offn[i][lv]:offn[i][lv + 1]].view(copies[i], h, w, C)
-                    v.copy_(self._replayed(v.permute(0, 3, 1, 2), i, layer, lv).permute(0, 2, 3, 1))
+    def _jobs(self, side: int, trunk, st: dict):
+        """The predictor jobs (`_predict`) of one side -- 0: cls_score (+ cls_var), 1: bbox_pred (+ bbox_cov) -- on its trunk (buffer, images
+        per level).  With dropout the mean branch reads the trunk's first images and the variance branch the m after them (an independent
+        dropout draw, Q2): cls [0, m) and [m, 2m), bbox [0, n) and [n, n + m).  Without, both read the one evaluation."""
+        buf, copies = trunk
+        mean, var = (self.cls_score, self.cls_var) if side == 0 else (self.bbox_pred, self.bbox_cov)
+        if not st["dropout"]:
+            return [(conv, buf, 1, 0, 1, 1) for conv in (mean, var) if conv is not None]
+        n, m = st["n"], st["m"]
+        first = m if side == 0 else n
+        return [(mean, buf, copies, 0, first, n)] + ([(var, buf, copies, first, m, n)] if var is not None else [])
 
-        grouped_launch([{"conv": self._wino(subs[i][0]), "src": x0, "dst": a[i], "table": block_table(levels, 1, dev, out_copies=copies[i]),
-                         "offset": ids[i][0] << 34, "replicas": copies[i]} for i in range(2)],
-                       relu=True, dropout_p=p, seed=self.dropout_seed, epoch=self._epoch)
-        if replay:
-            mask_in_place(a, 0)
-        tn = [block_table(levels, c, dev) for c in copies]
-        b = [torch.empty_like(t) for t in a]
-        for l in range(1, L):
-            grouped_launch([{"conv": self._wino(subs[i][l]), "src": a[i], "dst": b[i], "table": tn[i], "offset": ids[i][l] << 34} for i in range(2)],
-                           relu=True, dropout_p=p, seed=self.dropout_seed, epoch=self._epoch)
-            if replay:
-                mask_in_place(b, l)
-            a, b = b, a
-        return a[0], copies_c, a[1], copies_b
-
-    def _predict_grouped(self, jobs, levels, live=None, bufs=None):
-        """The predictor convs in ONE launch.  jobs: (conv, buffer, images in the buffer per level, first image, image count, output images)
-        as `_predict_all_levels` takes them; returns its result for each job.  live / bufs: the sparse bbox tower (`_trunk_all_levels`)."""
+    def _predict(self, jobs, st: dict, live=None, bufs=None):
+        """The predictor convs (cls_score / bbox_pred / cls_var / bbox_cov, PR:430-484).  jobs: (conv, trunk buffer, images in it per level,
+        first image, image count, output images).  Returns per job and level an (out_copies, K, H, W) NCHW tensor -- the planes K1 streams --
+        whose images past `count` are zero (never uninitialised memory: a consumer without the quirk merge would read them).  ONE launch when
+        the head's launches are grouped and the convs share a padded width, one launch each otherwise.  live / bufs: the sparse tower (`_trunks`)."""
         from .sparse import REACH_PREDICTOR
         from .wino import block_table, grouped_launch, level_pixel_offsets
+        levels = st["levels"]
         sets, outs = [], []
         for ji, (conv, buf, buf_copies, first, count, out_copies) in enumerate(jobs):
             K = conv.out_channels
@@ -696,20 +667,20 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
             sets.append({"conv": self._wino(conv), "src": buf, "dst": out, "planes": True,
                          "table": block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies)})
             outs.append([out[offs[i] * K:offs[i + 1] * K].view(out_copies, K, h, w) for i, (h, w) in enumerate(levels)])
-        grouped_launch(sets, live=None if live is None else (lambda table: live(table, REACH_PREDICTOR)))
+        lv = None if live is None else (lambda table: live(table, REACH_PREDICTOR))
+        if st["grouped"] and len({s["conv"].Kpad for s in sets}) == 1 and all(s["conv"].split for s in sets):
+            grouped_launch(sets, live=lv)
+        else:
+            for s in sets:
+                s["conv"](s["src"], s["dst"], s["table"], planes=True, **({} if lv is None else {"live": lv(s["table"])}))
         return outs
 
-    def _predict_all_levels(self, conv, buf: torch.Tensor, levels, buf_copies: int, first: int, count: int, out_copies: int):
-        """A predictor conv (cls_score / bbox_pred / cls_var / bbox_cov, PR:430-484) on images first .. first+count-1 of every level
-        of a trunk buffer, one launch; returns per level an (out_copies, K, H, W) NCHW tensor -- the planes K1 streams -- whose
-        images past `count` are zero (never uninitialised memory: a consumer without the quirk merge would read them)."""
-        from .wino import block_table, level_pixel_offsets
-        K = conv.out_channels
-        offs = level_pixel_offsets(levels, out_copies)
-        out = (torch.zeros if out_copies > count else torch.empty)(offs[-1] * K, dtype=buf.dtype, device=buf.device)
-        table = block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies)
-        self._wino(conv)(buf, out, table, planes=True)
-        return [out[offs[i] * K:offs[i + 1] * K].view(out_copies, K, h, w) for i, (h, w) in enumerate(levels)]
+    @staticmethod
+    def _expanded(res, st: dict):
+        """Eval mode: the one evaluation of each predictor as the n runs' images (every run would give the same)."""
+        if st["dropout"] or st["n"] == 1:
+            return res
+        return [[t.expand(st["n"], -1, -1, -1).contiguous() for t in ts] for ts in res]
 
     def takes_wino_path(self) -> bool:
         """Every conv of the head runs on pod_wino_conv3x3[_split] (GPU, fp32, one image): then all its dropout masks take the `_epoch` word."""
@@ -743,63 +714,59 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
             return t
         return new
 
-    def forward_cls(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False) -> dict:
-        """First half of the sparse evaluation (`forward`, sparse_bbox): the cls subnet + cls_score (+ cls_var) of all levels and runs.
-        Returns the state `forward_bbox` continues from (the level features as one channels-last buffer among it)."""
+    def _plan(self, features: List[torch.Tensor], num_runs: int, mc_dropout: bool, skip_unused_last_run: bool) -> dict:
+        """The run bookkeeping of a head evaluation: n runs, of which m = n - skip need cls / cls_var / reg_var, the copies each trunk
+        evaluates, and whether every conv takes pod_wino_conv3x3 ("wino"; then "grouped" (`_grouped_ok`), "levels" and "x0", the features
+        as one channels-last buffer, level after level)."""
         dropout = mc_dropout and self.dropout_rate > 0.0
         n = num_runs
         skip = 1 if (skip_unused_last_run and dropout and n > 1) else 0
-        m = n - skip
-        cls_copies = m * (2 if self.compute_cls_var else 1)
-        box_copies = n + (m if self.compute_bbox_cov else 0)
-        ok = (self.takes_wino_path() and features[0].is_cuda and features[0].dtype == torch.float32 and features[0].shape[0] == 1
-              and features[0].shape[1] == self.cls_subnet[0].in_channels and self._grouped_ok(cls_copies, box_copies))
-        if not ok:
+        m = n - skip                                               # runs whose cls / cls_var / reg_var are needed
+        st = {"n": n, "m": m, "skip": skip, "dropout": dropout,
+              "cls_copies": m * (2 if self.compute_cls_var else 1), "box_copies": n + (m if self.compute_bbox_cov else 0)}
+        f = features[0]
+        st["wino"] = (self.takes_wino_path() and f.is_cuda and f.dtype == torch.float32 and f.shape[0] == 1
+                      and f.shape[1] == self.cls_subnet[0].in_channels)
+        if st["wino"]:
+            st.update(grouped=self._grouped_ok(st["cls_copies"], st["box_copies"]), levels=[(int(f.shape[2]), int(f.shape[3])) for f in features],
+                      x0=levels_channels_last(features))
+        return st
+
+    def forward_cls(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False) -> dict:
+        """First half of the sparse evaluation (ProbabilisticRetinaNet.cls_part): the cls subnet + cls_score (+ cls_var) of all levels and
+        runs.  Returns the state `forward_bbox` continues from (the level features as one channels-last buffer among it)."""
+        st = self._plan(features, num_runs, mc_dropout, skip_unused_last_run)
+        if not (st["wino"] and st["grouped"]):
             raise RuntimeError("the sparse bbox tower needs the split kernels on the GPU (POD_WINO_SPLIT=1, one fp32 image, grouped head)")
-        levels = [(int(f.shape[2]), int(f.shape[3])) for f in features]
-        x0 = levels_channels_last(features)                                                    # channels-last, level after level
-        tc, nc = self._trunk_all_levels(self.cls_subnet, x0, levels, cls_copies, dropout)
-        cj = [(self.cls_score, tc, nc, 0, m, n)] if dropout else [(self.cls_score, tc, 1, 0, 1, 1)]
-        if self.compute_cls_var:
-            cj += [(self.cls_var, tc, nc, m, m, n)] if dropout else [(self.cls_var, tc, 1, 0, 1, 1)]
-        res = self._predict_grouped(cj, levels)
-        if not dropout and n > 1:
-            res = [[t.expand(n, -1, -1, -1).contiguous() for t in ts] for ts in res]
-        return {"x0": x0, "levels": levels, "n": n, "m": m, "dropout": dropout, "skip": skip, "box_copies": box_copies,
-                "logits": res[0], "logit_vars": res[1] if self.compute_cls_var else None}
+        (tc,) = self._trunks([(0, st["cls_copies"])], st)
+        res = self._expanded(self._predict(self._jobs(0, tc, st), st), st)
+        st.update(logits=res[0], logit_vars=res[1] if self.compute_cls_var else None)
+        return st
 
     def forward_bbox(self, st: dict, live):
         """Second half: bbox_subnet + bbox_pred (+ bbox_cov) over the blocks `live` (sparse.LiveBlocks) lists; None = all of them."""
-        x0, levels, n, m, dropout = st["x0"], st["levels"], st["n"], st["m"], st["dropout"]
-        bufs = None if live is None else self.sparse_buffers((torch.cuda.current_stream(x0.device).cuda_stream, tuple(levels), n, dropout, st["skip"]))
-        tb, nb = self._trunk_all_levels(self.bbox_subnet, x0, levels, st["box_copies"], dropout, live=live, bufs=bufs)
-        bj = [(self.bbox_pred, tb, nb, 0, n, n)] if dropout else [(self.bbox_pred, tb, 1, 0, 1, 1)]
-        if self.compute_bbox_cov:
-            bj += [(self.bbox_cov, tb, nb, n, m, n)] if dropout else [(self.bbox_cov, tb, 1, 0, 1, 1)]
-        res = self._predict_grouped(bj, levels, live=live, bufs=bufs)
-        if not dropout and n > 1:
-            res = [[t.expand(n, -1, -1, -1).contiguous() for t in ts] for ts in res]
+        bufs = None if live is None else self.sparse_buffers((torch.cuda.current_stream(st["x0"].device).cuda_stream, tuple(st["levels"]), st["n"],
+                                                              st["dropout"], st["skip"]))
+        (tb,) = self._trunks([(1, st["box_copies"])], st, live=live, bufs=bufs)
+        res = self._expanded(self._predict(self._jobs(1, tb, st), st, live=live, bufs=bufs), st)
         return res[0], (res[1] if self.compute_bbox_cov else None)
 
-    def forward(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False,
-                skip_unused_last_run: bool = False, sparse_bbox=None):
+    def forward(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False):
         """features: per-level (1, 256, H, W).  Returns per-level lists of (num_runs, A*C, H, W).
 
         skip_unused_last_run: the reference's merge (PI:216-222) never reads run N-1 of box_cls,
         box_cls_var and box_reg_var (only box_delta's last run is used, by the epistemic covariance PI:325-331).
         With the flag set those three evaluations of the last run are not computed (their slab in the returned
         tensors is zero): 3 of the 4N subnet evaluations, 7.5 % of the head at N = 10.  Only valid
-        together with `merge_quirk=True` in the hot path.
-
-        sparse_bbox (round 5): None, or a callable (logits, logit_vars) -> sparse.LiveBlocks.  The cls side is then evaluated FIRST, the
-        callable selects the image's candidates from it (K1f + K2 of the hot path, PI:283-308) and the bbox side -- bbox_subnet,
-        bbox_pred, bbox_cov: PR:518-537 evaluates them densely although PI:310-331 reads them at the candidates only -- runs over the
-        blocks that can reach a candidate.  Its outputs are defined at the candidates' cells and stale elsewhere; same Philox offsets, so
-        the same dropout masks as the dense evaluation."""
-        dropout = mc_dropout and self.dropout_rate > 0.0
-        n = num_runs
-        skip = 1 if (skip_unused_last_run and dropout and n > 1) else 0
-        m = n - skip                                               # runs whose cls / cls_var / reg_var are needed
+        together with `merge_quirk=True` in the hot path."""
+        st = self._plan(features, num_runs, mc_dropout, skip_unused_last_run)
+        if st["wino"]:
+            # every conv of the head on pod_wino_conv3x3: one launch per layer over all levels and all runs, both trunks, then the predictors
+            tc, tb = self._trunks([(0, st["cls_copies"]), (1, st["box_copies"])], st)
+            cj, bj = self._jobs(0, tc, st), self._jobs(1, tb, st)
+            res = self._expanded(self._predict(cj[:1] + bj[:1] + cj[1:] + bj[1:], st), st)       # cls_score, bbox_pred (, cls_var) (, bbox_cov)
+            return res[0], res[1], (res[2] if self.compute_cls_var else None), (res[-1] if self.compute_bbox_cov else None)
+        n, m, dropout = st["n"], st["m"], st["dropout"]
 
         def padded(t):                                            # (m, C, H, W) -> (n, C, H, W) NCHW planes (what K1 streams),
             if m == n:                                            # last slab untouched; a channels-last trunk output is
@@ -810,62 +777,9 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
             return out                                            # the quirk merge would read it); 1/n of one small tensor
 
         logits, deltas, logit_vars, delta_covs = [], [], [], []
-        cls_copies = m * (2 if self.compute_cls_var else 1)
-        box_copies = n + (m if self.compute_bbox_cov else 0)
-        wino = (self.takes_wino_path() and features[0].is_cuda and features[0].dtype == torch.float32 and features[0].shape[0] == 1
-                and features[0].shape[1] == self.cls_subnet[0].in_channels)
-        if wino:
-            # every conv of the head on pod_wino_conv3x3: one launch per layer over all levels and all runs
-            levels = [(int(f.shape[2]), int(f.shape[3])) for f in features]
-            x0 = levels_channels_last(features)                                                    # channels-last, level after level
-            grouped = self._grouped_ok(cls_copies, box_copies)
-            if sparse_bbox is not None:
-                st = self.forward_cls(features, num_runs, mc_dropout, skip_unused_last_run)
-                deltas, delta_covs = self.forward_bbox(st, sparse_bbox(st["logits"], st["logit_vars"]))
-                return st["logits"], deltas, st["logit_vars"], delta_covs
-            if grouped:
-                tc, nc, tb, nb = self._trunks_grouped(x0, levels, cls_copies, box_copies, dropout)
-            else:
-                tc, nc = self._trunk_all_levels(self.cls_subnet, x0, levels, cls_copies, dropout)
-                tb, nb = self._trunk_all_levels(self.bbox_subnet, x0, levels, box_copies, dropout)
-            preds = [c for c in (self.cls_score, self.bbox_pred, self.cls_var if self.compute_cls_var else None, self.bbox_cov if self.compute_bbox_cov else None)
-                     if c is not None]
-            if grouped and len({self._wino(c).Kpad for c in preds}) == 1 and all(self._wino(c).split for c in preds):
-                # the predictors in one launch too
-                if dropout:
-                    jobs = [(self.cls_score, tc, nc, 0, m, n), (self.bbox_pred, tb, nb, 0, n, n)]
-                    jobs += [(self.cls_var, tc, nc, m, m, n)] if self.compute_cls_var else []          # independent dropout draw (Q2)
-                    jobs += [(self.bbox_cov, tb, nb, n, m, n)] if self.compute_bbox_cov else []
-                    res = self._predict_grouped(jobs, levels)
-                else:
-                    jobs = [(self.cls_score, tc, 1, 0, 1, 1), (self.bbox_pred, tb, 1, 0, 1, 1)]
-                    jobs += [(self.cls_var, tc, 1, 0, 1, 1)] if self.compute_cls_var else []
-                    jobs += [(self.bbox_cov, tb, 1, 0, 1, 1)] if self.compute_bbox_cov else []
-                    res = self._predict_grouped(jobs, levels)
-                    if n > 1:
-                        res = [[t.expand(n, -1, -1, -1).contiguous() for t in ts] for ts in res]
-                logits, deltas = res[0], res[1]
-                logit_vars = res[2] if self.compute_cls_var else []
-                delta_covs = res[-1] if self.compute_bbox_cov else []
-            elif dropout:
-                logits = self._predict_all_levels(self.cls_score, tc, levels, nc, 0, m, n)
-                deltas = self._predict_all_levels(self.bbox_pred, tb, levels, nb, 0, n, n)
-                if self.compute_cls_var:
-                    logit_vars = self._predict_all_levels(self.cls_var, tc, levels, nc, m, m, n)   # independent dropout draw (Q2)
-                if self.compute_bbox_cov:
-                    delta_covs = self._predict_all_levels(self.bbox_cov, tb, levels, nb, n, m, n)
-            else:
-                ex = (lambda ts: [t.expand(n, -1, -1, -1).contiguous() for t in ts]) if n > 1 else (lambda ts: ts)
-                pred = lambda conv, buf: ex(self._predict_all_levels(conv, buf, levels, 1, 0, 1, 1))
-                logits, deltas = pred(self.cls_score, tc), pred(self.bbox_pred, tb)
-                if self.compute_cls_var:
-                    logit_vars = pred(self.cls_var, tc)
-                if self.compute_bbox_cov:
-                    delta_covs = pred(self.bbox_cov, tb)
-            return logits, deltas, (logit_vars if self.compute_cls_var else None), (delta_covs if self.compute_bbox_cov else None)
         for level, f in enumerate(features):
-            tc = self._trunk(self.cls_subnet, f, cls_copies, dropout, level)
-            tb = self._trunk(self.bbox_subnet, f, box_copies, dropout, level)
+            tc = self._trunk(self.cls_subnet, f, st["cls_copies"], dropout, level)
+            tb = self._trunk(self.bbox_subnet, f, st["box_copies"], dropout, level)
             if dropout:
                 # (a channels-last trunk hands its last activation over as NCHW planes: the A*K / A*4-channel predictor convs
                 #  are faster as NCHW Winograd calls than as NHWC implicit GEMMs)
@@ -1003,13 +917,6 @@ class ProbabilisticRetinaNet(_TracksStorage):
         delta, reg_var = self.head.forward_bbox(st, live)
         return self.partial_outputs(st, delta, reg_var)
 
-    def _bbox_eager(self, st: dict, sparse_bbox) -> HeadOutputs:
-        skipped = bool(st["skip"])
-        mk = lambda delta, reg_var: HeadOutputs(st["logits"], delta, st["logit_vars"], reg_var, self.anchors_for(st["padded"]), st["shapes"], self.num_anchors,
-                                                self.num_classes, st["image_hw"], last_run_valid=not skipped)
-        delta, reg_var = self.head.forward_bbox(st, sparse_bbox(mk(None, None)))
-        return mk(delta, reg_var)
-
     def _forward_graphed(self, image: torch.Tensor, n: int, dropout: bool, skip: bool, part: str = "all"):
         stream = torch.cuda.current_stream(image.device)
         run = self._forward_eager if part == "all" else self._cls_eager
@@ -1088,15 +995,19 @@ class ProbabilisticRetinaNet(_TracksStorage):
         num_mc_dropout_runs > 1 batches that many dropout-perturbed head evaluations (PR:103-108).
         mc_dropout: dropout active in the head subnets -- the reference's `model.train()` (PI:53-56), which it sets
         whenever MC_DROPOUT.ENABLE is true, also for a single run; default: active iff several runs are requested.
-        sparse_bbox: callable (partial HeadOutputs: cls / cls_var set, delta = reg_var = None) -> sparse.LiveBlocks: the bbox side of the
-        head is evaluated only where it can reach a candidate (ProbabilisticRetinaNetHead.forward).  The trunk + cls half is replayed as a HIP
-        graph (`cls_part`), the bbox half is enqueued eagerly (its live lists are made per image)."""
+        sparse_bbox: None, or a callable (partial HeadOutputs: cls / cls_var set, delta = reg_var = None) -> sparse.LiveBlocks.  The cls side
+        of the head is then evaluated FIRST, the callable selects the image's candidates from it (K1f + K2 of the hot path, PI:283-308) and
+        the bbox side -- bbox_subnet, bbox_pred, bbox_cov: PR:518-537 evaluates them densely although PI:310-331 reads them at the candidates
+        only -- runs over the blocks that can reach a candidate.  Its outputs are defined at the candidates' cells and stale elsewhere; same
+        Philox offsets, so the same dropout masks as the dense evaluation.  The trunk + cls half is replayed as a HIP graph (`cls_part`), the
+        bbox half is enqueued eagerly (its live lists are made per image)."""
         n = num_mc_dropout_runs if num_mc_dropout_runs > 1 else 1
         if mc_dropout is None:
             mc_dropout = n > 1
         dropout = bool(mc_dropout) and self.use_dropout
         if sparse_bbox is not None:
-            return self._bbox_eager(self.cls_part(image, num_mc_dropout_runs, skip_unused_last_run, mc_dropout), sparse_bbox)
+            st = self.cls_part(image, num_mc_dropout_runs, skip_unused_last_run, mc_dropout)
+            return self.bbox_part(st, sparse_bbox(self.partial_outputs(st)))
         if (self.use_graphs and image.is_cuda and self.device.type == "cuda" and self.head.dropout_replay is None
                 and (not dropout or self.head.takes_wino_path())):
             return self._forward_graphed(image, n, dropout, skip_unused_last_run)
@@ -1128,21 +1039,16 @@ class ProbabilisticRetinaNet(_TracksStorage):
             padded = tuple(x.shape[-2:])
         return feats, padded
 
-    def _head_eager(self, feats, padded, image_hw, n: int, mc_dropout: bool, skip_unused_last_run: bool, sparse_bbox=None) -> HeadOutputs:
+    def _head_eager(self, feats, padded, image_hw, n: int, mc_dropout: bool, skip_unused_last_run: bool) -> HeadOutputs:
         shapes = [tuple(f.shape[-2:]) for f in feats]
         skipped = skip_unused_last_run and n > 1 and bool(mc_dropout) and self.use_dropout
-        hook = None
-        if sparse_bbox is not None:
-            hook = lambda logits, logit_vars: sparse_bbox(HeadOutputs(logits, None, logit_vars, None, self.anchors_for(padded), shapes, self.num_anchors,
-                                                                      self.num_classes, tuple(image_hw), last_run_valid=not skipped))
-        cls, delta, cls_var, reg_var = self.head(feats, n, mc_dropout=bool(mc_dropout) and self.use_dropout,
-                                                 skip_unused_last_run=skip_unused_last_run, sparse_bbox=hook)
+        cls, delta, cls_var, reg_var = self.head(feats, n, mc_dropout=bool(mc_dropout) and self.use_dropout, skip_unused_last_run=skip_unused_last_run)
         return HeadOutputs(cls, delta, cls_var, reg_var, self.anchors_for(padded), shapes, self.num_anchors,
                            self.num_classes, tuple(image_hw), last_run_valid=not skipped)
 
-    def _forward_eager(self, image: torch.Tensor, n: int, mc_dropout: bool, skip_unused_last_run: bool, sparse_bbox=None) -> HeadOutputs:
+    def _forward_eager(self, image: torch.Tensor, n: int, mc_dropout: bool, skip_unused_last_run: bool) -> HeadOutputs:
         feats, padded = self._trunk_eager(image)
-        return self._head_eager(feats, padded, image.shape[-2:], n, mc_dropout, skip_unused_last_run, sparse_bbox)
+        return self._head_eager(feats, padded, image.shape[-2:], n, mc_dropout, skip_unused_last_run)
 
 
 def resize_test_image(image: torch.Tensor, min_size: int = 800, max_size: int = 1333) -> torch.Tensor:

@@ -254,7 +254,7 @@ def modeling_wino_split(head) -> bool:
     return modeling.wino_of(head.cls_subnet[1]).split
 
 
-def test_eval_mode_trunk_sharing_on_the_gpu():
+def test_eval_mode_evaluates_each_trunk_once_on_the_gpu():
     """SURVEY f-4 on the GPU: without dropout the mean and variance branches of a subnet see the same trunk activation, so
     the head evaluates each trunk once (PR:518-523 runs it twice); the outputs equal two separate evaluations."""
     from pod_compare_amd import modeling
@@ -272,24 +272,17 @@ def test_eval_mode_trunk_sharing_on_the_gpu():
         calls["n"] += 1
         return real(convs, feature, copies, dropout, level)
 
-    real_all = model.head._trunk_all_levels
+    real_all = model.head._trunks
 
-    def counting_all(convs, x0, levels, copies, dropout):
-        calls["n"] += len(levels)
-        return real_all(convs, x0, levels, copies, dropout)
-
-    real_grouped = model.head._trunks_grouped
-
-    def counting_grouped(x0, levels, copies_c, copies_b, dropout):          # (both subnets, layer by layer in one launch each)
-        calls["n"] += 2 * len(levels)
-        return real_grouped(x0, levels, copies_c, copies_b, dropout)
+    def counting_all(subnets, st, **kw):                          # (all levels, one launch per layer)
+        calls["n"] += len(subnets) * len(st["levels"])
+        return real_all(subnets, st, **kw)
 
     model.head._trunk = counting
-    model.head._trunk_all_levels = counting_all
-    model.head._trunks_grouped = counting_grouped
+    model.head._trunks = counting_all
     cls, delta, cls_var, reg_var = model.head(feats, 1, mc_dropout=False)
     assert calls["n"] == 2 * len(feats)                           # one cls trunk + one box trunk per level, not four
-    model.head._trunk, model.head._trunk_all_levels, model.head._trunks_grouped = real, real_all, real_grouped
+    model.head._trunk, model.head._trunks = real, real_all
     for l, f in enumerate(feats):
         tc, tb = f, f
         for conv in model.head.cls_subnet:

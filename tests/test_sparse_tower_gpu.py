@@ -94,19 +94,22 @@ def test_reach_map_and_live_lists_equal_a_brute_force_evaluation(mode, runs):
             assert lst[0] < 0.6 * len(recs)                    # a handful of objects: most blocks are dead
 
 
-@pytest.mark.parametrize("dropout,runs", [(0.2, 4), (0.0, 1)])
-def test_sparse_tower_gives_the_dense_towers_detections(dropout, runs):
+@pytest.mark.parametrize("dropout,runs,cov", [pytest.param(0.2, 4, "diagonal", id="0.2-4"), pytest.param(0.0, 1, "diagonal", id="0.0-1"),
+                                               pytest.param(0.2, 4, "full", id="0.2-4-full"), pytest.param(0.0, 1, "full", id="0.0-1-full")])
+def test_sparse_tower_gives_the_dense_towers_detections(dropout, runs, cov):
     """The whole model twice on one frame, dense and sparse, with the SAME planted class tensors selecting the candidates (a random-init
     head has none): identical candidates and masks, box deltas / variances at the candidates equal to the last bits (the abs-max record
-    of a sparse launch covers the live blocks only: another binade moves the f16 splits' roundings), identical detections."""
-    m = build(dropout_rate=dropout)
+    of a sparse launch covers the live blocks only: another binade moves the f16 splits' roundings), identical detections.  Also with a
+    full-covariance head (bbox_cov: 9 x 10 channels, padded to 128 against bbox_pred's 64: the two predictors cannot share a launch)."""
+    m = build(dropout_rate=dropout, bbox_cov_type=cov)
+    D = m.head.bbox_cov_dims
     frame = torch.randint(0, 256, (3, 256, 384), dtype=torch.uint8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     pl = planted((256, 384), runs, seed=9)
     mc = dropout > 0
     kw = dict(num_mc_dropout_runs=runs if mc else -1, mc_dropout=mc, skip_unused_last_run=mc)
     m.head._drop_calls = 0
     dense = m(frame, **kw)
-    hp = hotpath.HotPath(pl.shapes, pl.anchors, hotpath.PathParams(), n_runs=runs if mc else 1, has_cls_var=True, cov_dims=4, device="cuda:0")
+    hp = hotpath.HotPath(pl.shapes, pl.anchors, hotpath.PathParams(), n_runs=runs if mc else 1, has_cls_var=True, cov_dims=D, device="cuda:0")
     cls = pl.cls if mc else [t[:1] for t in pl.cls]
     cls_var = pl.cls_var if mc else [t[:1] for t in pl.cls_var]
     want = hp.run_image("bayes_od", cls, dense.delta, cls_var, dense.reg_var, (256, 384), (256, 384), draw_id=11)
