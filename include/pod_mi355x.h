@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define POD_ABI_VERSION 16
+#define POD_ABI_VERSION 17
 #define POD_MAX_LEVELS 8
 #define POD_MAX_CLASSES 16       /* K: BDD = 7 (Base-BDD-RetinaNet.yaml:11-12) */
 #define POD_MAX_RUNS 64          /* MC-dropout runs / ensemble members */
@@ -56,6 +56,8 @@ extern "C" {
 #define POD_COCO_MAX_MAXDET 4    /*   maxDets entries ([1, 10, 100]) */
 #define POD_COCO_MAX_KEEP 128    /*   detections kept per (image, category): maxDets[-1] (100) */
 #define POD_COCO_LDS_GT 64       /*   ground-truth boxes per (image, category) whose IoU matrix fits LDS; more use scratch */
+#define POD_CALIB_MAX_EDGES 15   /* calibration pass: regression cdf edges (torch.arange(0, 1 - 1/15, 1/15) + 1/15: 14) */
+#define POD_CALIB_BLOCK 1024     /*   sorted positions per block of the marginal-error bin counts */
 
 #define POD_OK 0
 #define POD_E_INVALID (-1)       /* bad argument / unsupported size */
@@ -526,6 +528,51 @@ size_t pod_coco_accumulate_workspace_bytes(int64_t n_kept);
 int pod_coco_accumulate(const PodCocoParams* prm, const int64_t* cat_off, int32_t max_seg, int64_t n_kept, const double* kept_score,
                         const uint64_t* kept_match, const uint64_t* kept_ignore, const int32_t* kept_rank, const int32_t* npig,
                         void* workspace, double* precision, double* recall, double* scores, pod_stream_t stream);
+
+/* ---- K18  calibration pass (offline calibration errors) ----------------------------------------
+ * Replaces the O(detections) work of compute_calibration_errors.py `calibration_errors` (CE:86-297).  Rows are the matched
+ * partitions concatenated: true positives, then duplicates (n_matched rows with a ground truth), then false positives.  Integer
+ * counts only cross workgroups; sums are in a fixed order: results are bit-identical run to run.  The O(classes x 4 x 14) tail
+ * stays on the host with the host function's expressions. */
+
+/* CE:86-103, CE:166-167, CE:263-276.  cls_probs dev (n, k1) fp32 (k1 - 1 classes + background), cov dev (n, 4, 4) fp32,
+ * gt_class dev int32[n_matched]: the converted (contiguous) ground-truth class of the matched rows.
+ * cls_entropy = -log(max of the first k1 - 1 columns); reg_entropy = entropy of MVN(0, cov + 1e-4 I) (4x4 Cholesky, fp32);
+ * det_class = gt_class for matched rows, the first arg-max of those columns for false positives; class_count dev int32[POD_MAX_CLASSES]
+ * rows per det_class, zeroed by this call. */
+int pod_calib_keys(const float* cls_probs, int32_t k1, const float* cov, const int32_t* gt_class, int32_t n_matched, int32_t n,
+                   float* cls_entropy, float* reg_entropy, int32_t* det_class, int32_t* class_count, pod_stream_t stream);
+
+/* CE:206-261: cdf = Normal(mean_d, sqrt(cov_dd)).cdf(gt_d) of the matched rows, fp32 as torch computes it.  edges: host fp32[n_edges]
+ * ascending (i + step).  counts dev int32[POD_MAX_CLASSES][4][n_edges + 1], zeroed by this call: bin j < n_edges counts the cdf values
+ * below edge j but not below edge j - 1, bin n_edges the rest (NaN included); "cdf < edge i" is the prefix sum up to i. */
+int pod_calib_reg_counts(const float* means, const float* cov, const float* gt, const int32_t* det_class, int32_t n_matched,
+                         const float* edges, int32_t n_edges, int32_t* counts, pod_stream_t stream);
+
+/* CE:160-178, CE:279-292: the minimum-uncertainty error of n_seg segments.  Segment s = [seg_off[s], seg_off[s + 1]) holds
+ * class c = seg_class[s] >> 1 (key: cls_entropy if bit 0 is clear, else reg_entropy); its rows are those of det_class c in row
+ * order, starting at class_off[c] (dev int32[POD_MAX_CLASSES], exclusive offsets of pod_calib_keys' counts).  perm: dev int64,
+ * the host's torch.randperm draws at seg_off.  Gathered by perm, sorted stably by key, prefix counts of true positives (rows
+ * < n_tp) and of the rest, errs = 0.5 (T - cumTP) / T + 0.5 cumFP / F in fp64; min_err dev fp64[n_seg]: the NaN-propagating min
+ * (NaN for an empty segment).  max_seg: the longest segment, n_pos = seg_off[n_seg]; workspace: pod_calib_min_uncertainty_workspace_bytes(n, n_pos). */
+size_t pod_calib_min_uncertainty_workspace_bytes(int32_t n, int64_t n_pos);
+int pod_calib_min_uncertainty(const float* cls_entropy, const float* reg_entropy, const int32_t* det_class, int32_t n, int32_t n_tp,
+                              const int32_t* class_off, const int64_t* seg_off, const int32_t* seg_class, int32_t n_seg, int32_t max_seg,
+                              int64_t n_pos, const int64_t* perm, void* workspace, double* min_err, pod_stream_t stream);
+
+/* CE:117-136 `calibration.get_calibration_error` as compute_calibration_errors.marginal_calibration_error restates it, in three calls
+ * with the host choosing the path in between.  1) sort: scores dev fp32[n] -> sorted dev fp64[n] ascending, order dev int32[n] (stable).
+ * 2) bin starts per block of POD_CALIB_BLOCK sorted positions, blk_cnt dev int32[ceil(n / POD_CALIB_BLOCK)]: edges == NULL, one bin per
+ * distinct value (their sum is the number of distinct scores); else the bins of searchsorted(edges, v, 'left'), edges host fp64[n_edges <= POD_CALIB_MAX_EDGES].
+ * 3) error: blk_off dev int64, exclusive offsets of blk_cnt, n_bins their total; labels dev int64[n] in {0, 1}; per bin fp64 sums of
+ * labels and scores, bins with n < 2 or past the last edge (scores > 1.0 on the discrete path) skipped, the debiased L2 terms added in
+ * bin order: total dev fp64[1] (the error is sqrt(max(total, 0))).  workspaces: pod_calib_marginal_*_workspace_bytes. */
+size_t pod_calib_marginal_sort_workspace_bytes(int32_t n);
+int pod_calib_marginal_sort(const float* scores, int32_t n, void* workspace, double* sorted, int32_t* order, pod_stream_t stream);
+int pod_calib_marginal_bins(const double* sorted, int32_t n, const double* edges, int32_t n_edges, int32_t* blk_cnt, pod_stream_t stream);
+size_t pod_calib_marginal_error_workspace_bytes(int32_t n_bins);
+int pod_calib_marginal_error(const double* sorted, const int32_t* order, const int64_t* labels, int32_t n, const double* edges,
+                             int32_t n_edges, const int64_t* blk_off, int32_t n_bins, void* workspace, double* total, pod_stream_t stream);
 
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */

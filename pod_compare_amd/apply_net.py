@@ -54,6 +54,26 @@ def category_mapping(train_dataset: str, test_dataset: str) -> Dict[int, int]:
 BDD_CAT_MAP = category_mapping("bdd_train", "bdd_val")   # contiguous id -> dataset id (ids 1..7)
 
 
+def evaluation_category_map(train_dataset: str, test_dataset: str) -> Dict[int, int]:
+    """EU:370-397 (get_thing_dataset_id_to_contiguous_id_dict): TEST data set's category id -> the model's (TRAIN data set's) contiguous id,
+    the map the evaluators convert ground-truth categories with.  Same classes (BDD -> BDD, BDD -> Lyft, KITTI -> KITTI): the test set's
+    own dataset id -> contiguous map.  BDD -> KITTI: each KITTI id to the BDD class of the same name ({1: 0, 2: 3}).  Any other pair raises
+    (the reference builds the ValueError without raising it; the COCO -> VOC branch is not carried, as in `category_mapping`)."""
+    train, test = _family(train_dataset), _family(test_dataset)
+    if THING_CLASSES[train] == THING_CLASSES[test]:
+        return {i + 1: i for i in range(len(THING_CLASSES[test]))}
+    if train == "bdd" and test == "kitti":
+        return {k + 1: THING_CLASSES["bdd"].index(c) for k, c in enumerate(THING_CLASSES["kitti"])}
+    raise ValueError("Cannot generate category mapping dictionary. Please check if training and inference datasets are compatible.")
+
+
+def add_dataset_arguments(ap: argparse.ArgumentParser) -> None:
+    """--train-dataset / --test-dataset of the offline evaluators: which category map the ground truth and the results are read with."""
+    ap.add_argument("--train-dataset", default="bdd_train", help="the model's training data set (cfg.DATASETS.TRAIN[0]): its classes are the model's")
+    ap.add_argument("--test-dataset", default="bdd_val", help="the data set of the results and the ground truth (EU:370-397: e.g. kitti_val "
+                                                              "maps KITTI's car / person to the BDD model's classes 0 / 3)")
+
+
 def shard_indices(num_images: int, rank: int, world: int) -> List[int]:
     """Images of rank `rank`: i = rank (mod world)."""
     return list(range(rank, num_images, world))
@@ -254,6 +274,58 @@ def _run_ensemble_per_gpu(cfg, args, rank, world):
     return recs, cnts
 
 
+def own_test_set(train_dataset: str) -> str:
+    """The test split of the model's own data family (bdd_train -> bdd_val): where the AP step's threshold applies to PM and CE."""
+    return _family(train_dataset) + "_val"
+
+
+def has_ground_truth(coco_json: str) -> bool:
+    if not coco_json:
+        return False
+    with open(coco_json, "r") as f:
+        return "annotations" in json.load(f)
+
+
+def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train", test_dataset: str = "bdd_val", binary: bool = False,
+                     min_allowed_score: Optional[float] = None, map_results: str = "", device: str = "cuda", seed: int = 0) -> dict:
+    """AN:104-106: the offline chain on a result file, in this process on `device`.  1) AP on K17 (compute_average_precision, its
+    default --cat-ids), mAP_res.txt written beside `results`; 2) PM; 3) CE with the calibration pass on the GPU (K18).  Prints the
+    three tables the modules print.  The PM / CE threshold: `min_allowed_score`, else `map_results`' (PM:50-65 / CE:47-63), else --
+    when the test set is the model's own (bdd_val for a BDD model) -- the threshold the AP step just wrote, else 0.0.  (The reference
+    reads the training family's file; its AN:104 has the AP call commented out.)  torch is seeded with `seed` before CE's randperm."""
+    from . import compute_average_precision as cap
+    from . import compute_calibration_errors as cce
+    from . import compute_probabilistic_metrics as cpm
+    torch.cuda.set_device(torch.device(device))
+    if binary:
+        from .inference_utils import binary_results_to_json
+        predicted = binary_results_to_json(results, category_mapping(train_dataset, test_dataset))
+    else:
+        with open(results, "r") as f:
+            predicted = json.load(f)
+    with open(gt_json, "r") as f:
+        gt = json.load(f)
+    ap = cap.coco_average_precision(predicted, gt, device=device)
+    print(cap.format_summary(ap["stats"]))
+    print("Classification Score at Optimal F-1 Score: {}".format(ap["optimal_score_threshold"]))
+    map_path = os.path.join(os.path.dirname(os.path.abspath(results)), "mAP_res.txt")
+    cap.write_map_results(map_path, ap["stats"], ap["optimal_score_threshold"])
+    if min_allowed_score is not None or map_results:
+        thr = cap.resolve_min_allowed_score(min_allowed_score, map_results)
+    elif test_dataset == own_test_set(train_dataset):
+        thr = cap.read_min_allowed_score(map_path)
+    else:
+        thr = 0.0
+    cmap = evaluation_category_map(train_dataset, test_dataset)
+    pm = cpm.probabilistic_metrics(predicted, gt["annotations"], cat_mapping_dict=cmap, min_allowed_score=thr, device=device)
+    print(cpm.format_table(pm))
+    torch.manual_seed(seed)
+    ce = cce.calibration_errors_of_results(predicted, gt["annotations"], cmap, thr, device=device)
+    print(cce.format_table(ce))
+    print("Cls Marginal Calibration Error computed by: " + ce["cls_marginal_calibration_error_source"])
+    return {"ap": ap, "pm": pm, "ce": ce, "min_allowed_score": thr, "map_results": map_path}
+
+
 def main(argv=None):
     from . import synthetic
     from .config import setup_config
@@ -274,7 +346,7 @@ def main(argv=None):
                          "(tests/test_sparse_tower_gpu.py), 1.3 x the images/s with MC dropout.  --ensemble-per-gpu (one member per GPU) is always dense")
     ap.add_argument("--sparse-bbox", action="store_true", help="(the default; kept for round-5 command lines)")
     ap.add_argument("--random-seed", type=int, default=0)
-    ap.add_argument("--output", default="coco_instances_results.json")
+    ap.add_argument("--output", default=None, help="the result file (default coco_instances_results.json)")
     ap.add_argument("--no-graphs", action="store_true", help="issue every launch of a forward from Python instead of replaying a HIP graph per (stream, frame shape)")
     ap.add_argument("--streams", type=int, default=0,
                     help="HIP streams per GPU; consecutive images of a rank go to different streams (batch 1 per stream, AN:35); 0 = 2 with "
@@ -295,8 +367,33 @@ def main(argv=None):
     ap.add_argument("--share-gpu", action="store_true", help="functional check only: every rank uses cuda:0")
     ap.add_argument("--random-init", action="store_true",
                     help="synthetic runs: clear MODEL.WEIGHTS / OUTPUT_DIR and keep the seeded random initialisation")
+    ap.add_argument("--eval", action="store_true",
+                    help="after writing --output, evaluate it as the reference's AN:104-106 does: AP (mAP_res.txt beside --output), PM and CE on "
+                         "this GPU (needs --coco-json with `annotations`).  The PM / CE threshold: --min-allowed-score, else --map-results, else "
+                         "the AP step's own when --test-dataset is the model's own test set (bdd_val for a BDD model), else 0.0 -- the reference "
+                         "reads the training family's mAP_res.txt instead (PM:50-65 / CE:47-63)")
+    ap.add_argument("--eval-only", action="store_true", help="build no model, run no inference: evaluate --output (or --binary-output if only "
+                                                             "that is given) as --eval does")
+    ap.add_argument("--min-allowed-score", type=float, default=None, help="--eval: the detections' score threshold of PM and CE")
+    ap.add_argument("--map-results", default="", help="--eval: take the PM / CE threshold from this mAP_res.txt (PM:50-65)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    evaluating = args.eval or args.eval_only
+    if evaluating:
+        if not has_ground_truth(args.coco_json):
+            raise SystemExit("--eval / --eval-only need ground truth: --coco-json with `annotations`")
+        if args.ensemble_per_gpu:
+            raise SystemExit("--ensemble-per-gpu runs on the synthetic frames only: it cannot be evaluated (--eval)")
+    if args.eval_only:
+        binary = bool(args.binary_output) and args.output is None
+        if int(os.environ.get("RANK", "0")) != 0:
+            return None
+        local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
+        return evaluate_results(args.binary_output if binary else (args.output or "coco_instances_results.json"), args.coco_json,
+                                args.train_dataset, args.test_dataset, binary=binary, min_allowed_score=args.min_allowed_score,
+                                map_results=args.map_results, device="cuda:%d" % local_rank, seed=args.random_seed)
+    if args.output is None:
+        args.output = "coco_instances_results.json"
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.share_gpu:
@@ -420,8 +517,13 @@ def main(argv=None):
             print("inference loop: %d images on %d rank(s) in %.2f s = %.1f images/s%s (%d stream(s) per GPU%s)" % (
                 len(ids), world, t_loop, len(ids) / t_loop, steady, n_streams,
                 ", %d loader thread(s)" % workers if dataset is not None else ", synthetic frames made on the device"))
+    res = None
+    if rank == 0 and args.eval:
+        res = evaluate_results(args.output, args.coco_json, args.train_dataset, args.test_dataset, min_allowed_score=args.min_allowed_score,
+                               map_results=args.map_results, device=dev, seed=args.random_seed)
     if world > 1:
         dist.destroy_process_group()
+    return res
 
 
 if __name__ == "__main__":

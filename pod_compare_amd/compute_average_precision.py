@@ -157,13 +157,14 @@ def main(argv=None):
     ap.add_argument("--cat-ids", default=",".join(str(c) for c in DEFAULT_CAT_IDS), help="evaluated category ids (AP:38: 1,3)")
     ap.add_argument("--output", default="", help="write mAP_res.txt here (AP:64-68)")
     ap.add_argument("--device", default="cuda")
+    from .apply_net import add_dataset_arguments, category_mapping
+    add_dataset_arguments(ap)
     args = ap.parse_args(argv)
     if bool(args.results) == bool(args.binary_results):
         ap.error("give exactly one of --results / --binary-results")
     if args.binary_results:
-        from .apply_net import BDD_CAT_MAP
         from .inference_utils import binary_results_to_json
-        predicted = binary_results_to_json(args.binary_results, BDD_CAT_MAP)
+        predicted = binary_results_to_json(args.binary_results, category_mapping(args.train_dataset, args.test_dataset))
     else:
         with open(args.results, "r") as f:
             predicted = json.load(f)

@@ -17,6 +17,10 @@ Everything else is pinned against the reference's own `main` run on seeded parti
 tests/golden/calib_errors.npz).  Host-side torch: this is offline evaluation, not the images/sec path.
 
     python -m pod_compare_amd.compute_calibration_errors --results coco_instances_results.json --gt val_coco_format.json
+    python -m pod_compare_amd.compute_calibration_errors --results kitti_results.json --gt kitti_val.json --test-dataset kitti_val
+
+`--device cuda` (the default) runs the calibration pass on the GPU (`calibration_errors_gpu`, csrc/k18_calibration.hip): the per-detection
+entropies, the regression cdf counts, the minimum-uncertainty sorts and the marginal error's bins; `--device cpu` keeps `calibration_errors`.
 """
 import argparse
 import json
@@ -142,9 +146,32 @@ def format_table(res: dict) -> str:
     return "\n".join([line, row(names), line, row(vals), line])
 
 
-def main(argv=None):
-    from .compute_probabilistic_metrics import BDD_DATASET_ID_TO_CONTIGUOUS
+def calibration_errors_gpu(matched: dict, cat_mapping_dict: Dict[int, int], marginal_fn=None) -> dict:
+    """`calibration_errors` with the calibration pass on the GPU (csrc/k18_calibration.hip): the same dict, `cls_marginal_inputs` included,
+    and the same randperm draws.  marginal_fn=None: the marginal error restated above, computed on the GPU."""
+    from .calibration_gpu import calibration_errors_gpu as run
+    return run(matched, cat_mapping_dict, marginal_fn=marginal_fn)
+
+
+def calibration_errors_of_results(predicted, gt, cat_mapping_dict: Dict[int, int], min_allowed_score: float, iou_min: float = 0.1,
+                                  iou_correct: float = 0.7, device="cuda") -> dict:
+    """CE:64-297 on a result list and ground-truth annotations: matching, then the calibration pass -- on the GPU for a cuda device,
+    else `calibration_errors` -- with the reference's marginal function when it is installed.  Prints nothing."""
     from . import evaluation_utils as ev
+    pred = ev.eval_predictions_preprocess(predicted, min_allowed_score, device=device)
+    g = ev.eval_gt_preprocess(gt, device=device)
+    matched = ev.match_predictions_to_groundtruth(pred["predicted_boxes"], pred["predicted_cls_probs"], pred["predicted_covar_mats"],
+                                                  g["gt_boxes"], g["gt_cat_idxs"], iou_min, iou_correct, device=device)
+    fn, which = default_marginal_fn()
+    if torch.device(device).type == "cuda":
+        res = calibration_errors_gpu(matched, cat_mapping_dict, marginal_fn=None if fn is marginal_calibration_error else fn)
+    else:
+        res = calibration_errors(matched, cat_mapping_dict, marginal_fn=fn)
+    res["cls_marginal_calibration_error_source"] = which
+    return res
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--results", required=True, help="coco_instances_results.json written by apply_net (AN:100-102)")
     ap.add_argument("--gt", required=True, help="COCO-format ground truth json (its `annotations`)")
@@ -152,7 +179,9 @@ def main(argv=None):
     ap.add_argument("--iou-correct", type=float, default=0.7)
     ap.add_argument("--min-allowed-score", type=float, default=None, help="score threshold of the detections (default: from --map-results, else 0.0)")
     ap.add_argument("--map-results", default="", help="mAP_res.txt of compute_average_precision: its optimal-F1 score threshold, rounded to 4 decimals, is the min allowed score (CE:50-62)")
-    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--device", default="cuda", help="cuda: the calibration pass on the GPU (csrc/k18_calibration.hip); cpu: `calibration_errors` on the host")
+    from .apply_net import add_dataset_arguments, evaluation_category_map
+    add_dataset_arguments(ap)
     args = ap.parse_args(argv)
     from .compute_average_precision import resolve_min_allowed_score
     args.min_allowed_score = resolve_min_allowed_score(args.min_allowed_score, args.map_results)
@@ -160,15 +189,10 @@ def main(argv=None):
         predicted = json.load(f)
     with open(args.gt, "r") as f:
         gt = json.load(f)["annotations"]
-    pred = ev.eval_predictions_preprocess(predicted, args.min_allowed_score, device=args.device)
-    g = ev.eval_gt_preprocess(gt, device=args.device)
-    matched = ev.match_predictions_to_groundtruth(pred["predicted_boxes"], pred["predicted_cls_probs"], pred["predicted_covar_mats"],
-                                                  g["gt_boxes"], g["gt_cat_idxs"], args.iou_min, args.iou_correct, device=args.device)
-    fn, which = default_marginal_fn()
-    res = calibration_errors(matched, BDD_DATASET_ID_TO_CONTIGUOUS, marginal_fn=fn)
+    res = calibration_errors_of_results(predicted, gt, evaluation_category_map(args.train_dataset, args.test_dataset), args.min_allowed_score,
+                                        args.iou_min, args.iou_correct, device=args.device)
     print(format_table(res))
-    print("Cls Marginal Calibration Error computed by: " + which)       # (say it in the table's output, not only in a docstring)
-    res["cls_marginal_calibration_error_source"] = which
+    print("Cls Marginal Calibration Error computed by: " + res["cls_marginal_calibration_error_source"])   # (say it in the table's output, not only in a docstring)
     return res
 
 

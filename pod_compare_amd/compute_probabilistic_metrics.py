@@ -8,6 +8,7 @@ reference's detectron2 plumbing (MetadataCatalog lookups, on-disk caches of the 
 
     python -m pod_compare_amd.compute_probabilistic_metrics --results coco_instances_results.json --gt val_coco_format.json
     python -m pod_compare_amd.compute_probabilistic_metrics --binary-results results.podr --gt val_coco_format.json
+    python -m pod_compare_amd.compute_probabilistic_metrics --results kitti_results.json --gt kitti_val.json --test-dataset kitti_val
 
 The matching and scoring functions come from `pod_compare_amd.evaluation_utils` (HIP); `ev=` lets a test substitute another
 implementation of the same five functions.
@@ -94,20 +95,21 @@ def main(argv=None):
     ap.add_argument("--min-allowed-score", type=float, default=None, help="score threshold of the detections (default: from --map-results, else 0.0)")
     ap.add_argument("--map-results", default="", help="mAP_res.txt of compute_average_precision: its optimal-F1 score threshold, rounded to 4 decimals, is the min allowed score (PM:50-65)")
     ap.add_argument("--device", default="cuda")
+    from .apply_net import add_dataset_arguments, category_mapping, evaluation_category_map
+    add_dataset_arguments(ap)
     args = ap.parse_args(argv)
     from .compute_average_precision import resolve_min_allowed_score
     args.min_allowed_score = resolve_min_allowed_score(args.min_allowed_score, args.map_results)
     if args.binary_results:
-        from .apply_net import BDD_CAT_MAP
         from .inference_utils import binary_results_to_json
-        predicted = binary_results_to_json(args.binary_results, BDD_CAT_MAP)
+        predicted = binary_results_to_json(args.binary_results, category_mapping(args.train_dataset, args.test_dataset))
     else:
         with open(args.results, "r") as f:
             predicted = json.load(f)
     with open(args.gt, "r") as f:
         gt = json.load(f)["annotations"]
-    res = probabilistic_metrics(predicted, gt, iou_min=args.iou_min, iou_correct=args.iou_correct, min_allowed_score=args.min_allowed_score,
-                                device=args.device)
+    res = probabilistic_metrics(predicted, gt, cat_mapping_dict=evaluation_category_map(args.train_dataset, args.test_dataset), iou_min=args.iou_min,
+                                iou_correct=args.iou_correct, min_allowed_score=args.min_allowed_score, device=args.device)
     print(format_table(res))
     return res
 

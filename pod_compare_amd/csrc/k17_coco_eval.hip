@@ -11,6 +11,7 @@
 //                        "unmatched" to the area-range test and to accumulate, as it does in pycocotools.
 //   k_coco_sort_tiles  : per category, 1024-element tiles of the kept detections sorted in LDS (bitonic) by (score desc, position).
 //   k_coco_merge       : merge passes of sorted runs (each element's output slot by binary search in the partner run).
+//                        The two are the library's stable segmented sort (pod_segsort.h: K18 sorts its own keys with them).
 //   k_coco_gather      : the kept arrays in that order.  Position = (image position in sorted imgIds, rank), so the order is the
 //                        one argsort(-concatenated scores, kind='mergesort') gives.
 //   k_coco_accumulate  : one workgroup per (category, area, maxDet, IoU threshold): prefix counts of tp / fp, rc, pr, the
@@ -18,6 +19,7 @@
 //                        pr: element i lies at or after searchsorted index j iff recThrs[j] <= rc[i], so the envelope at j is the
 //                        max of pr over the "buckets" >= j, and the score at j is the first element reaching bucket j.
 #include "pod_device.h"
+#include "pod_segsort.h"
 
 namespace pod {
 
@@ -188,7 +190,7 @@ __global__ void __launch_bounds__(512) k_coco_sort_tiles(const KCocoSort P) {
     if (base >= n) return;
     for (int i = tid; i < COCO_TILE; i += blockDim.x) {
         const int p = base + i;
-        sk[i] = p < n ? coco_desc_key(P.kept_score[c0 + p]) : ~0ull;
+        sk[i] = p < n ? (P.kept_score ? coco_desc_key(P.kept_score[c0 + p]) : P.key_in[c0 + p]) : ~0ull;
         si[i] = p < n ? (int32_t)(c0 + p) : 0x7fffffff;
     }
     for (int size = 2; size <= COCO_TILE; size <<= 1) {
@@ -386,6 +388,28 @@ static bool coco_params_ok(const PodCocoParams* p) {
 
 static size_t coco_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
+int segsort(const int64_t* seg_off, int32_t n_seg, int32_t max_seg, const double* desc_scores, uint64_t* key0, int32_t* idx0,
+            uint64_t* key1, int32_t* idx1, uint64_t** keys, int32_t** order, hipStream_t st) {
+    KCocoSort S;
+    S.cat_off = seg_off; S.kept_score = desc_scores; S.key_in = key0; S.idx_in = idx0; S.key_out = key0; S.idx_out = idx0; S.w = 0;
+    if (max_seg > 0 && n_seg > 0) {
+        hipLaunchKernelGGL(k_coco_sort_tiles, dim3((max_seg + COCO_TILE - 1) / COCO_TILE, n_seg), dim3(512), 0, st, S);
+        POD_CHECK_LAUNCH();
+        for (int w = COCO_TILE; w < max_seg; w *= 2) {
+            S.key_out = S.key_in == key0 ? key1 : key0;
+            S.idx_out = S.idx_in == idx0 ? idx1 : idx0;
+            S.w = w;
+            hipLaunchKernelGGL(k_coco_merge, dim3((max_seg + 255) / 256, n_seg), dim3(256), 0, st, S);
+            POD_CHECK_LAUNCH();
+            S.key_in = S.key_out;
+            S.idx_in = S.idx_out;
+        }
+    }
+    *keys = S.key_in;
+    *order = S.idx_in;
+    return POD_OK;
+}
+
 }  // namespace pod
 
 extern "C" size_t pod_coco_eval_scratch_bytes(int32_t n_keep, int32_t n_gt) {
@@ -447,20 +471,10 @@ extern "C" int pod_coco_accumulate(const PodCocoParams* prm, const int64_t* cat_
     P.kept_rank = kept_rank; P.s_score = s_score; P.s_match = s_match; P.s_ignore = s_ignore; P.s_rank = s_rank; P.npig = npig;
     P.precision = precision; P.recall = recall; P.scores = scores; P.n_kept = n_kept;
     if (max_seg > 0) {
-        pod::KCocoSort S;
-        S.cat_off = cat_off; S.kept_score = kept_score; S.key_in = key0; S.idx_in = idx0; S.key_out = key0; S.idx_out = idx0; S.w = 0;
-        hipLaunchKernelGGL(pod::k_coco_sort_tiles, dim3((max_seg + pod::COCO_TILE - 1) / pod::COCO_TILE, K), dim3(512), 0, st, S);
-        POD_CHECK_LAUNCH();
-        for (int w = pod::COCO_TILE; w < max_seg; w *= 2) {
-            S.key_out = S.key_in == key0 ? key1 : key0;
-            S.idx_out = S.idx_in == idx0 ? idx1 : idx0;
-            S.w = w;
-            hipLaunchKernelGGL(pod::k_coco_merge, dim3((max_seg + 255) / 256, K), dim3(256), 0, st, S);
-            POD_CHECK_LAUNCH();
-            S.key_in = S.key_out;
-            S.idx_in = S.idx_out;
-        }
-        P.order = S.idx_in;
+        uint64_t* keys;
+        int32_t* order;
+        if (pod::segsort(cat_off, K, max_seg, kept_score, key0, idx0, key1, idx1, &keys, &order, st) != POD_OK) return POD_E_LAUNCH;
+        P.order = order;
         const int64_t blocks = (n_kept + 255) / 256;
         hipLaunchKernelGGL(pod::k_coco_gather, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, P);
         POD_CHECK_LAUNCH();

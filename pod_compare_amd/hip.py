@@ -14,7 +14,7 @@ import torch
 
 from .build import LIB
 
-POD_ABI_VERSION = 16
+POD_ABI_VERSION = 17
 POD_MAX_LEVELS = 8
 POD_MAX_CLASSES = 16
 POD_MAX_RUNS = 64
@@ -24,13 +24,20 @@ POD_MAX_CLS_SAMPLES = 64
 POD_MAX_CANDIDATES = 8192
 POD_MAX_DETECTIONS = 128
 POD_COCO_MAX_IOU, POD_COCO_MAX_REC, POD_COCO_MAX_AREA, POD_COCO_MAX_MAXDET, POD_COCO_MAX_KEEP, POD_COCO_LDS_GT = 16, 128, 4, 4, 128, 64
+POD_CALIB_MAX_EDGES, POD_CALIB_BLOCK = 15, 1024
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
            "pod_ensemble_append", "pod_ensemble_merge",
            "pod_finalize", "pod_reg_nll", "pod_relu_dropout", "pod_bias_act", "pod_bias_act_to_nchw", "pod_bias_act_to_nhwc", "pod_expand_dropout", "pod_match_groundtruth", "pod_run_image", "pod_run_image_part",
            "pod_absmax", "pod_wino_filter_transform", "pod_wino_conv3x3", "pod_wino_filter_split_bytes", "pod_wino_filter_transform_split", "pod_wino_conv3x3_split", "pod_sparse_reach", "pod_sparse_live_blocks", "pod_wino_reduce", "pod_conv1x1_filter_split_bytes", "pod_conv1x1_filter_split", "pod_conv1x1_split", "pod_reduce_partials", "pod_stem7x7_filter_split", "pod_stem7x7_split", "pod_maxpool3x3s2_cl", "pod_im2col3x3s2_cl",
-           "pod_coco_eval_scratch_bytes", "pod_coco_eval_images", "pod_coco_accumulate_workspace_bytes", "pod_coco_accumulate")
+           "pod_coco_eval_scratch_bytes", "pod_coco_eval_images", "pod_coco_accumulate_workspace_bytes", "pod_coco_accumulate",
+           "pod_calib_keys", "pod_calib_reg_counts", "pod_calib_min_uncertainty_workspace_bytes", "pod_calib_min_uncertainty",
+           "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_sort", "pod_calib_marginal_bins", "pod_calib_marginal_error_workspace_bytes",
+           "pod_calib_marginal_error")
+_SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
+                 "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
+                 "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws and of the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -167,8 +174,20 @@ def load() -> ctypes.CDLL:
     lib.pod_coco_accumulate_workspace_bytes.argtypes = [c_int64]
     lib.pod_coco_accumulate_workspace_bytes.restype = c_size_t
     lib.pod_coco_accumulate.argtypes = [POINTER(PodCocoParams), P, c_int32, c_int64] + [P] * 9 + [P]
+    lib.pod_calib_keys.argtypes = [P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P]
+    lib.pod_calib_reg_counts.argtypes = [P, P, P, P, c_int32, P, c_int32, P, P]
+    lib.pod_calib_min_uncertainty_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.pod_calib_min_uncertainty_workspace_bytes.restype = c_size_t
+    lib.pod_calib_min_uncertainty.argtypes = [P, P, P, c_int32, c_int32, P, P, P, c_int32, c_int32, c_int64, P, P, P, P]
+    lib.pod_calib_marginal_sort_workspace_bytes.argtypes = [c_int32]
+    lib.pod_calib_marginal_sort_workspace_bytes.restype = c_size_t
+    lib.pod_calib_marginal_sort.argtypes = [P, c_int32, P, P, P, P]
+    lib.pod_calib_marginal_bins.argtypes = [P, c_int32, P, c_int32, P, P]
+    lib.pod_calib_marginal_error_workspace_bytes.argtypes = [c_int32]
+    lib.pod_calib_marginal_error_workspace_bytes.restype = c_size_t
+    lib.pod_calib_marginal_error.argtypes = [P, P, P, c_int32, P, c_int32, P, c_int32, P, P, P]
     for name in EXPORTS + TEST_EXPORTS:
-        if name not in ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words", "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes"):
+        if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int
     if lib.pod_abi_version() != POD_ABI_VERSION:
         raise PodError("ABI version mismatch: library {} vs binding {}".format(lib.pod_abi_version(), POD_ABI_VERSION))
