@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define POD_ABI_VERSION 17
+#define POD_ABI_VERSION 18
 #define POD_MAX_LEVELS 8
 #define POD_MAX_CLASSES 16       /* K: BDD = 7 (Base-BDD-RetinaNet.yaml:11-12) */
 #define POD_MAX_RUNS 64          /* MC-dropout runs / ensemble members */
@@ -573,6 +573,77 @@ int pod_calib_marginal_bins(const double* sorted, int32_t n, const double* edges
 size_t pod_calib_marginal_error_workspace_bytes(int32_t n_bins);
 int pod_calib_marginal_error(const double* sorted, const int32_t* order, const int64_t* labels, int32_t n, const double* edges,
                              int32_t n_edges, const int64_t* blk_off, int32_t n_bins, void* workspace, double* total, pod_stream_t stream);
+
+/* ---- K19  visualisation (annotated frames) ----------------------------------------------------
+ * Replaces: ProbabilisticVisualizer.overlay_covariance_instances / draw_ellipse / cov_ellipse
+ * (core/visualization_tools/probabilistic_visualizer.py PV:22-125, PV:127-195, PV:322-354) with detectron2's Visualizer.draw_box /
+ * draw_text / VisImage underneath, as visualize_predictions.py (VP:62-142) and ProbabilisticPredictor.visualize_inference (PI:113-146)
+ * drive them; matplotlib's rasteriser is replaced by the library's own.  Two calls:
+ *
+ * pod_vis_layout: one workgroup per list (one overlay_covariance_instances call), n = min(*count, max_n) instances (count NULL: max_n).
+ *   out (dev, max_n rows of POD_VIS_INST_WORDS 4-byte words) receives them in DRAW ORDER: descending box area, ties by input index
+ *   (PV:66-75), NaN areas last.  Words (i = int32, f = fp32):
+ *     0 i input index | 1-4 f x0 y0 x1 y1 (frame pixels) | 5-7 f colour rgb | 8 f alpha
+ *     9-12 i ellipse at (x0, y0): drawn (0 = a NaN, PV:155), width, height, rotation (int32-truncated, + 180: PV:156-158)
+ *     13-16 i ellipse at (x1, y1): the same from cov[2:4, 2:4] | 17-20 f cos, sin of the two rotations
+ *     21-22 f label anchor (frame pixels, PV:89-106) | 23 f font size in points before the scale (PV:108-116) | 24-26 f text colour
+ *     27 f area | 28-31 zero.
+ *   Colours: POD_VIS_COLOUR_ENTROPY = cm.autumn(binary entropy of the top probability, base 2) (VP:99-107); FIXED = colour[0..2];
+ *   PALETTE = a fixed deterministic palette by input index (the reference's random_color is not reproducible); ARRAY = colours[input index].
+ *   Ellipses: PV:70-86 sorts boxes, labels and colours by area but NOT covariance_matrices, so the box drawn k-th gets covariance k:
+ *   POD_VIS_COV_BY_RANK reproduces that pairing, POD_VIS_COV_OWN gives every box its own covariance (cov[input index]).
+ * pod_vis_render: one launch per POD_VIS_LAUNCH_FRAMES frames, one 16 x 16-pixel tile per workgroup.  The canvas (out_h, out_w, 3)
+ *   uint8 RGB is the frame at `scale` (nearest, VisImage's imshow), or -- bilinear != 0 -- the source resampled to (frame_h, frame_w)
+ *   first (cv2.resize of PI:135, fp32, rounded to uint8), then every instance of inst[0] and inst[1] (box, ellipse, ellipse; in that
+ *   order), then the n_labels host-built label primitives (POD_VIS_PRIM_WORDS fp32 words each: kind (POD_VIS_LABEL_BOX: filled
+ *   rectangle | POD_VIS_LABEL_GLYPH: atlas quad), X0 Y0 X1 Y1 in canvas pixels, r g b, alpha, atlas byte offset, glyph row length, 0),
+ *   composited with dst += (colour - dst) alpha coverage.  Source pixel (y, x) channel c: src[y sy + x sx + c sc]; bgr: channel 0 is blue.
+ *   stroke: line width in canvas pixels.  The layout's outputs must be complete (same stream) before the render reads them. */
+#define POD_VIS_MAX_INSTANCES 256
+#define POD_VIS_INST_WORDS 32
+#define POD_VIS_PRIM_WORDS 12
+#define POD_VIS_LAUNCH_LISTS 16
+#define POD_VIS_LAUNCH_FRAMES 8
+#define POD_VIS_COLOUR_ENTROPY 0
+#define POD_VIS_COLOUR_FIXED 1
+#define POD_VIS_COLOUR_PALETTE 2
+#define POD_VIS_COLOUR_ARRAY 3
+#define POD_VIS_COV_BY_RANK 0
+#define POD_VIS_COV_OWN 1
+#define POD_VIS_LABEL_BOX 3
+#define POD_VIS_LABEL_GLYPH 4
+
+typedef struct PodVisList {
+    const float* boxes;          /* dev (n, box_stride) XYXY in frame pixels */
+    const float* cov;            /* dev (n, cov_stride) row-major 4x4 corner covariances, or NULL: no ellipses */
+    const float* probs;          /* dev (n, prob_stride): POD_VIS_COLOUR_ENTROPY takes the max of the first n_probs */
+    const float* colours;        /* dev (n, colour_stride >= 3) rgb: POD_VIS_COLOUR_ARRAY */
+    const int32_t* count;        /* dev int32 or NULL */
+    float* out;                  /* dev (max_n, POD_VIS_INST_WORDS) */
+    int32_t* n_out;              /* dev int32: n */
+    int32_t max_n, box_stride, cov_stride, prob_stride, n_probs, colour_mode, colour_stride;
+    int32_t cov_pairing;         /* POD_VIS_COV_BY_RANK (PV) or POD_VIS_COV_OWN */
+    float colour[4];
+    int32_t frame_h, frame_w;    /* the visualiser's image size (label rules, default font size) */
+    float scale, alpha;
+} PodVisList;
+
+typedef struct PodVisFrame {
+    const uint8_t* src;
+    int64_t sy, sx, sc;
+    int32_t src_h, src_w, bgr, bilinear;
+    int32_t frame_h, frame_w, out_h, out_w;
+    uint8_t* dst;                /* dev (out_h, out_w, 3) RGB */
+    float scale, stroke;
+    const float* inst[2];        /* pod_vis_layout outputs, or NULL */
+    const int32_t* n_inst[2];    /* their n_out words */
+    const float* labels;         /* dev (n_labels, POD_VIS_PRIM_WORDS), or NULL */
+    const uint8_t* atlas;        /* dev glyph coverage (0..255) */
+    int32_t n_labels, reserved;
+} PodVisFrame;
+
+int pod_vis_layout(const PodVisList* lists, int32_t n_lists, pod_stream_t stream);
+int pod_vis_render(const PodVisFrame* frames, int32_t n_frames, pod_stream_t stream);
 
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */

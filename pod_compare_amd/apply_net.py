@@ -376,6 +376,13 @@ def main(argv=None):
                                                              "that is given) as --eval does")
     ap.add_argument("--min-allowed-score", type=float, default=None, help="--eval: the detections' score threshold of PM and CE")
     ap.add_argument("--map-results", default="", help="--eval: take the PM / CE threshold from this mAP_res.txt (PM:50-65)")
+    ap.add_argument("--vis-dir", default="", help="also write every image of this rank annotated as visualize_inference draws it (PI:113-146): "
+                                                   "the first --vis-max-boxes detections with their corner-covariance ellipses over the frame at "
+                                                   "its original size, rendered on the GPU (K19) and encoded on host threads as <dir>/<file stem>.png")
+    ap.add_argument("--vis-max-boxes", type=int, default=20, help="--vis-dir: detections drawn per image (PI:125)")
+    ap.add_argument("--vis-ellipse-pairing", choices=("reference", "box"), default="reference",
+                    help="--vis-dir: reference = the ellipses as PV:70-86 pairs them (the box drawn k-th, by area, gets the k-th covariance of "
+                         "the result order); box = every box with its own covariance")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     evaluating = args.eval or args.eval_only
@@ -384,6 +391,8 @@ def main(argv=None):
             raise SystemExit("--eval / --eval-only need ground truth: --coco-json with `annotations`")
         if args.ensemble_per_gpu:
             raise SystemExit("--ensemble-per-gpu runs on the synthetic frames only: it cannot be evaluated (--eval)")
+    if args.vis_dir and args.ensemble_per_gpu:
+        raise SystemExit("--vis-dir draws the images of the sharded loop; --ensemble-per-gpu is not supported")
     if args.eval_only:
         binary = bool(args.binary_output) and args.output is None
         if int(os.environ.get("RANK", "0")) != 0:
@@ -471,6 +480,11 @@ def main(argv=None):
         recs, cnts = [], []
         workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
         loaded = iter(Prefetched(dataset, mine, workers=workers)) if dataset is not None else None
+        vis = None
+        if args.vis_dir:
+            from .visualization import InferenceFrameWriter
+            vis = InferenceFrameWriter(args.vis_dir, args.vis_max_boxes, bgr=str(cfg.INPUT.FORMAT) == "BGR", workers=max(1, workers),
+                                       cov_pairing=args.vis_ellipse_pairing)
         with torch.no_grad():
             for j in range(n_mine):
                 if j < len(mine):
@@ -486,6 +500,11 @@ def main(argv=None):
                             image = modeling.resize_test_image(frame, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
                             input_im = [{"image": image, "height": frame.shape[1], "width": frame.shape[2], "image_id": i}]
                         det = predictor(input_im)
+                        if vis is not None:           # enqueued behind the detections on this stream; not part of any captured graph
+                            if dataset is not None:
+                                vis.add(os.path.splitext(os.path.basename(d["file_name"]))[0] + ".png", input_im[0]["image"], d["height"], d["width"], det)
+                            else:
+                                vis.add("%06d.png" % i, frame, frame.shape[1], frame.shape[2], det)
                         chunk_ids.append(i)
                         recs.append(det.records)
                         cnts.append(det.n_det)
@@ -494,6 +513,9 @@ def main(argv=None):
                 if (j + 1) % F == 0 or j + 1 == n_mine:
                     flush(chunk_ids, recs, cnts)
                     chunk_ids, recs, cnts = [], [], []
+        if vis is not None:
+            vis.close()
+            print("rank %d: wrote %d annotated frames to %s" % (rank, vis.count, args.vis_dir))
     torch.cuda.synchronize()
     t_loop = time.perf_counter() - t_loop
     ids = all_ids

@@ -14,7 +14,7 @@ import torch
 
 from .build import LIB
 
-POD_ABI_VERSION = 17
+POD_ABI_VERSION = 18
 POD_MAX_LEVELS = 8
 POD_MAX_CLASSES = 16
 POD_MAX_RUNS = 64
@@ -25,6 +25,10 @@ POD_MAX_CANDIDATES = 8192
 POD_MAX_DETECTIONS = 128
 POD_COCO_MAX_IOU, POD_COCO_MAX_REC, POD_COCO_MAX_AREA, POD_COCO_MAX_MAXDET, POD_COCO_MAX_KEEP, POD_COCO_LDS_GT = 16, 128, 4, 4, 128, 64
 POD_CALIB_MAX_EDGES, POD_CALIB_BLOCK = 15, 1024
+POD_VIS_MAX_INSTANCES, POD_VIS_INST_WORDS, POD_VIS_PRIM_WORDS, POD_VIS_LAUNCH_FRAMES = 256, 32, 12, 8
+POD_VIS_COLOUR_ENTROPY, POD_VIS_COLOUR_FIXED, POD_VIS_COLOUR_PALETTE, POD_VIS_COLOUR_ARRAY = 0, 1, 2, 3
+POD_VIS_COV_BY_RANK, POD_VIS_COV_OWN = 0, 1
+POD_VIS_LABEL_BOX, POD_VIS_LABEL_GLYPH = 3, 4
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
@@ -34,7 +38,7 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_coco_eval_scratch_bytes", "pod_coco_eval_images", "pod_coco_accumulate_workspace_bytes", "pod_coco_accumulate",
            "pod_calib_keys", "pod_calib_reg_counts", "pod_calib_min_uncertainty_workspace_bytes", "pod_calib_min_uncertainty",
            "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_sort", "pod_calib_marginal_bins", "pod_calib_marginal_error_workspace_bytes",
-           "pod_calib_marginal_error")
+           "pod_calib_marginal_error", "pod_vis_layout", "pod_vis_render")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes")
@@ -89,6 +93,21 @@ class PodCocoParams(Structure):
     _fields_ = [("n_iou", c_int32), ("n_rec", c_int32), ("n_area", c_int32), ("n_maxdet", c_int32), ("n_cat", c_int32), ("reserved", c_int32),
                 ("iou_thrs", c_double * POD_COCO_MAX_IOU), ("rec_thrs", c_double * POD_COCO_MAX_REC), ("area_rng", c_double * (2 * POD_COCO_MAX_AREA)),
                 ("max_dets", c_int32 * POD_COCO_MAX_MAXDET)]
+
+
+class PodVisList(Structure):
+    """include/pod_mi355x.h: PodVisList (K19, one instance list of pod_vis_layout)."""
+    _fields_ = [(n, c_void_p) for n in ("boxes", "cov", "probs", "colours", "count", "out", "n_out")] + \
+               [(n, c_int32) for n in ("max_n", "box_stride", "cov_stride", "prob_stride", "n_probs", "colour_mode", "colour_stride", "cov_pairing")] + \
+               [("colour", c_float * 4), ("frame_h", c_int32), ("frame_w", c_int32), ("scale", c_float), ("alpha", c_float)]
+
+
+class PodVisFrame(Structure):
+    """include/pod_mi355x.h: PodVisFrame (K19, one frame of pod_vis_render)."""
+    _fields_ = [("src", c_void_p), ("sy", c_int64), ("sx", c_int64), ("sc", c_int64)] + \
+               [(n, c_int32) for n in ("src_h", "src_w", "bgr", "bilinear", "frame_h", "frame_w", "out_h", "out_w")] + \
+               [("dst", c_void_p), ("scale", c_float), ("stroke", c_float), ("inst", c_void_p * 2), ("n_inst", c_void_p * 2),
+                ("labels", c_void_p), ("atlas", c_void_p), ("n_labels", c_int32), ("reserved", c_int32)]
 
 
 class PodError(RuntimeError):
@@ -186,6 +205,8 @@ def load() -> ctypes.CDLL:
     lib.pod_calib_marginal_error_workspace_bytes.argtypes = [c_int32]
     lib.pod_calib_marginal_error_workspace_bytes.restype = c_size_t
     lib.pod_calib_marginal_error.argtypes = [P, P, P, c_int32, P, c_int32, P, c_int32, P, P, P]
+    lib.pod_vis_layout.argtypes = [POINTER(PodVisList), c_int32, P]
+    lib.pod_vis_render.argtypes = [POINTER(PodVisFrame), c_int32, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -118,6 +118,24 @@ class ProbabilisticPredictor(ABC):
             return self.post_processing_bayes_od(input_im)
         raise ValueError("Invalid inference mode {}.".format(self.inference_mode))
 
+    def visualize_inference(self, inputs, results, max_boxes: int = 20, cov_pairing: str = "reference"):
+        """PI:113-146 without cv2.imshow: the first `max_boxes` detections in the results' order with their corner-covariance ellipses
+        over the input frame resized to the output (height, width), drawn on the GPU (visualization.py, K19).  Returns the (height, width, 3)
+        uint8 RGB image.  results: the predictor's `Instances` or its device detections.  The frame's channel order is cfg.INPUT.FORMAT; the
+        image is RGB either way (the reference hands the BGR frame to an RGB visualiser).  cov_pairing: "reference" pairs
+        the ellipses as PV:70-86 does, "box" gives every box its own covariance (visualization.InstanceList)."""
+        from .visualization import render_inference
+        im = inputs[0]
+        if hasattr(results, "pred_boxes"):
+            boxes, cov, count = results.pred_boxes.tensor, results.pred_boxes_covariance, None
+        else:
+            boxes, cov, count = results.boxes, results.cov, results.n_det
+        dev = boxes.device
+        canvas = render_inference(im["image"].to(dev), im["height"], im["width"], boxes.float().contiguous(),
+                                  None if cov is None or len(cov) == 0 else cov.float().contiguous(), count, max_boxes,
+                                  bgr=str(self.cfg.INPUT.FORMAT) == "BGR", cov_pairing=cov_pairing)
+        return canvas.cpu().numpy()
+
     @abstractmethod
     def post_processing_standard_nms(self, input_im):
         pass
