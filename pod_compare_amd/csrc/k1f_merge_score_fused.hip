@@ -22,7 +22,6 @@
 // 16-byte loads, 765 wavefronts, less than one per SIMD -- walk their 9 runs as a chain of dependent round trips: 36 us; what hides the
 // HBM latency is wavefronts in flight.  Measured on one box, planted image: K1 + K1b 24.7 + 11.9 us; this kernel 25.9 us, of which the
 // streaming part alone 21 us -- profiles/r04_experiments.md.)  No MFMA: element-wise + reductions.
-#include <mutex>
 
 #include "pod_device.h"
 #include "pod_experiments.h"
@@ -309,14 +308,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 template <int KP, int WAVES, int CPL, bool VAR>
 static int k1f_launch(const pod::K1fParams& P, int units, hipStream_t stream) {
     constexpr size_t lds = sizeof(pod::K1fLds<KP, WAVES, CPL>);
-    static std::once_flag once[64];
-    static hipError_t attr[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return POD_E_LAUNCH;
-    std::call_once(once[dev], [dev] {
-        attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(pod::k1f_merge_score<KP, WAVES, CPL, VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (attr[dev] != hipSuccess) return POD_E_LAUNCH;
+    if (pod_lds_opt_in<pod::k1f_merge_score<KP, WAVES, CPL, VAR>>((int)lds) != POD_OK) return POD_E_LAUNCH;
     const int blocks = (units + WAVES - 1) / WAVES;
     hipLaunchKernelGGL((pod::k1f_merge_score<KP, WAVES, CPL, VAR>), dim3(blocks), dim3(64 * WAVES), lds, stream, P);
     POD_CHECK_LAUNCH();

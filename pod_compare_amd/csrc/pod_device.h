@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "../../include/pod_mi355x.h"
 
 #define POD_WAVE 64
@@ -16,6 +18,19 @@
     do {                                                    \
         if (hipGetLastError() != hipSuccess) return POD_E_LAUNCH; \
     } while (0)
+
+// Host: more than 64 KB of dynamic LDS is a PER-DEVICE attribute of a kernel -- asked for once per device ordinal this process launches on.
+template <auto Kernel>
+static int pod_lds_opt_in(int bytes) {
+    static std::once_flag once[64];
+    static hipError_t attr[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return POD_E_LAUNCH;
+    std::call_once(once[dev], [dev, bytes] {
+        attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    });
+    return attr[dev] == hipSuccess ? POD_OK : POD_E_LAUNCH;
+}
 
 // -DPOD_TRACE (python -m pod_compare_amd.build with POD_TRACE=1; diagnostics only, never the shipped library): phase
 // time stamps of the first workgroups of a kernel, constant 100 MHz clock, dumped by pod_trace_dump() of the same file.

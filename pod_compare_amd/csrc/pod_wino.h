@@ -1,8 +1,10 @@
-// Shared by the two Winograd convolution kernels (k11_wino_conv.hip: fp32 MFMA; k12_wino_conv_split.hip: the same convolution with
-// every fp32 product formed from 3-way bf16 splits on the bf16 matrix cores): parameters, LDS geometry, the slot table of the stage
-// fills, wait immediates, diagnostics hooks.
+// The shared home of the Winograd convolution kernels: k11_wino_conv.hip (fp32 MFMA, the reference leg) and k12_wino_conv_split.hip
+// (production: every fp32 product formed on the f16 matrix cores from the two-term f16 split of the power-of-two-scaled operands) are
+// the same convolution around different inner products.  Here: the parameters and their host-side fill, the LDS geometry, the workgroup
+// schedule, the block record and the canvas, the pixel table and the patch fills, the output staging, the dropout mask, the two store
+// passes, the f16 split and the abs-max records (k13 / k14 use those too), wait immediates and the diagnostics hooks.  A kernel body
+// reads: schedule -> shared prologue -> its OWN filter loads, K loop and transforms -> wino_output_stage -> wino_store_*.
 #pragma once
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -32,25 +34,45 @@ static __device__ long long g_wino_trace[8192 * 16];
     do {                                                                                                       \
         if (threadIdx.x == 0 && blockIdx.x < 8192) g_wino_trace[blockIdx.x * 16 + (k)] = wall_clock64();       \
     } while (0)
+// a kernel's last words: the stores have left, end stamps, where the workgroup ran (XCC / HW id)
+#define WINO_STAMP_END()                                                                                       \
+    do {                                                                                                       \
+        __builtin_amdgcn_s_waitcnt(0);                                                                         \
+        WINO_STAMP(5);                                                                                         \
+        WINO_STAMP_WALL(13);                                                                                   \
+        if (threadIdx.x == 0 && blockIdx.x < 8192) {                                                           \
+            uint32_t hw, xcc;                                                                                  \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                   \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                                 \
+            g_wino_trace[blockIdx.x * 16 + 6] = ((long long)xcc << 32) | hw;                                   \
+        }                                                                                                      \
+    } while (0)
+// host: this translation unit's stamps (each kernel file exports it under a name of its own; not in include/pod_mi355x.h)
+static inline int wino_trace_dump(long long* host, int32_t n_workgroups) {
+    if (hipDeviceSynchronize() != hipSuccess) return POD_E_LAUNCH;
+    if (n_workgroups > 8192) n_workgroups = 8192;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wino_trace), (size_t)n_workgroups * 16 * sizeof(long long)) != hipSuccess) return POD_E_LAUNCH;
+    return POD_OK;
+}
 #else
 #define WINO_STAMP(k)
 #define WINO_STAMP_WALL(k)
+#define WINO_STAMP_END()
 #endif
 
 // s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14): lgkmcnt(0) with vmcnt(4) / vmcnt(0)
 constexpr int WINO_WAIT_VM4 = 0x0074, WINO_WAIT_VM0 = 0x0070, WINO_WAIT_VM16 = 0x4070, WINO_WAIT_LGKM0 = 0xC07F;
 
+// One launch = 1..4 convolutions ("sets") of the same shape in one grid -- layer l of the cls- and the bbox-subnet, the four predictors
+// (PodWinoConv with n_sets > 1, include/pod_mi355x.h).  Blocks [first[s], first[s + 1]) of the concatenated table belong to set s (its
+// records are relative to ITS buffers).  k11 serves one convolution and reads set 0 only.
 struct WinoParams {
-    const float* in;
-    float* out;
-    const float* U;
-    const float* bias;
     const int4* blocks;
-    int32_t n_blocks, C, K, KS, in_stride, out_stride, relu, k_planes;   // k_planes > 0: NCHW planes of k_planes real channels
+    int32_t n_blocks, C, K, KS, in_stride, out_stride, relu;
     uint32_t thresh;
     float scale;
-    uint64_t seed, offset;
-    // split over the input channels (pod_wino_conv3x3_split only; small maps: a res5 convolution is 48 workgroups of 32 chunks each):
+    uint64_t seed;
+    // split over the input channels (PodWinoConv with n_splits > 1; small maps: a res5 convolution is 48 workgroups of 32 chunks each):
     // grid.y = C / (16 c_split) workgroup sets, set z accumulates chunks [z c_split, (z + 1) c_split) and stores its partial sums at
     // out + z split_out_stride (channels-last, no bias / ReLU / dropout); pod_wino_reduce adds the partials in a fixed order.  0: no split.
     int32_t c_split;
@@ -62,27 +84,21 @@ struct WinoParams {
     // word POD_SPARSE_LIVE_HEAD one entry of POD_SPARSE_LIVE_STRIDE words each, {record, 11 words of need bits} (include/pod_mi355x.h).
     // Workgroup slot t takes entry t and slots >= live[0] exit at once (the grid is sized for the whole table: the count never visits the host).
     const int32_t* live;
-    // the store pass writes `replicas` copies of the image (pod_wino_conv3x3_split_replicas: channels-last, one input image per record),
-    // replica r as image r of the output canvas, each under its own dropout mask -- the mask pod_expand_dropout would draw for it.  1: off.
-    int32_t replicas;
-    // Grouped launch (pod_wino_conv3x3_split_grouped): up to four convolutions of the same shape -- the cls- and the bbox-subnet layer l,
-    // the four predictors -- in ONE grid.  Blocks [set_first[s], set_first[s + 1]) of the concatenated table belong to set s (its records
-    // are relative to ITS buffers); a set has its own input, output, filter, bias, Philox offset, replica count and plane count.
-    // k_wino_conv3x3_split reads these, not the fields above (an ordinary launch is one set).
     struct Sets {
         int32_t first[4];         // first block of set s (first[0] = 0; unused sets: INT32_MAX)
         const float* in[4];
         float* out[4];
-        const float* U[4];
+        const float* U[4];        // k11: fp32 slabs; k12: the pre-split f16 terms + the abs-max trailer
         const float* bias[4];
         const float* in_amax[4];  // device word >= max |in| of the set (the f16 split's operand scale is derived from it)
         float* out_amax[4];       // null, or a device word the store pass max'es with |every value it stores|
-        uint64_t offset[4];
+        uint64_t offset[4];       // Philox counter of the set's first 8 output floats
+        // > 0 (PodWinoConv with replicas; channels-last, one input image per record): the store pass writes that many copies of the image,
+        // replica r as image r of the output canvas, each under its own dropout mask -- the mask pod_expand_dropout would draw for it
         int32_t replicas[4];
-        int32_t k_planes[4];
+        int32_t k_planes[4];      // > 0: NCHW planes of k_planes real channels
     } sets;
 };
-
 
 // What lane l3 = pixel slot, q = sub-slot of an LDS-DMA instruction fetches (see the layout in the kernel): per pixel slot 0..383
 // (py 18 + px) | rot << 16 (pixel 324: the slot holds no pixel), computed at compile time.
@@ -112,6 +128,27 @@ __device__ __forceinline__ void wino_schedule(int KS, int n_blocks, int& ks, int
 inline int64_t wino_grid(int KS, int64_t n_blocks) {
     const int SP = KS >= 2 ? 2 : 1, G = KS / SP;
     return 8 * SP * ((n_blocks * G + 7) / 8);
+}
+// Host: the launch-wide fields of P (the caller value-initialises it and sets c_split / split_out_stride / live where it has them) and
+// the grid's x extent; -1: K is not 64 x {1, 2, 4, 8}, or the grid does not fit.
+inline int64_t wino_params_launch(WinoParams& P, const int32_t* blocks, int32_t n_blocks, int32_t C, int32_t K, int32_t relu, float p, uint64_t seed,
+                                  const uint64_t* epoch) {
+    const int32_t KS = K / 64;
+    if (KS != 1 && KS != 2 && KS != 4 && KS != 8) return -1;
+    P.blocks = reinterpret_cast<const int4*>(blocks);
+    P.n_blocks = n_blocks; P.C = C; P.K = K; P.KS = KS; P.in_stride = C; P.out_stride = K; P.relu = relu;
+    P.thresh = POD_DROPOUT_THRESH16(p);
+    P.scale = 1.0f / (1.0f - p);
+    P.seed = seed; P.epoch = epoch;
+    const int64_t grid = wino_grid(KS, n_blocks);
+    return grid > 0x7FFFFFFFLL ? -1 : grid;
+}
+inline void wino_params_set(WinoParams& P, int s, int32_t first, const float* in, float* out, const void* U, const float* bias, const float* in_amax,
+                            float* out_amax, uint64_t offset, int32_t replicas, int32_t k_planes) {
+    P.sets.first[s] = first;
+    P.sets.in[s] = in; P.sets.out[s] = out; P.sets.U[s] = reinterpret_cast<const float*>(U); P.sets.bias[s] = bias;
+    P.sets.in_amax[s] = in_amax; P.sets.out_amax[s] = out_amax;
+    P.sets.offset[s] = offset; P.sets.replicas[s] = replicas; P.sets.k_planes[s] = k_planes;
 }
 
 // Ties values into the instruction order at this point (no instruction is emitted): what was computed before cannot sink below, what
@@ -219,5 +256,333 @@ __device__ __forceinline__ void wino_static_for(F&& f, std::integer_sequence<int
     (f(std::integral_constant<int, Js>{}), ...);
 }
 
+
+// ---- the filter transform U = G4 g G6t of one (k, c) pair (4 x 6 positions: F(2,3) down the rows, F(4,3) along the columns),
+//   G4 = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]],  G6 = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],[1/24,1/12,1/6],[1/24,-1/12,1/6],[0,0,1]];
+// output channels >= K are zero
+__device__ __forceinline__ void wino_filter_values(const float* __restrict__ w, int k, int c, int K, int C, float (&u)[4][6]) {
+    float g[3][3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) g[i / 3][i % 3] = k < K ? w[((int64_t)k * C + c) * 9 + i] : 0.0f;
+    float t0[4][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        t0[0][j] = g[0][j];
+        t0[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
+        t0[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
+        t0[3][j] = g[2][j];
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float x0 = t0[a][0], x1 = t0[a][1], x2 = t0[a][2];
+        u[a][0] = 0.25f * x0;
+        u[a][1] = (-1.0f / 6.0f) * (x0 + x1 + x2);
+        u[a][2] = (-1.0f / 6.0f) * (x0 - x1 + x2);
+        u[a][3] = (1.0f / 24.0f) * x0 + (1.0f / 12.0f) * x1 + (1.0f / 6.0f) * x2;
+        u[a][4] = (1.0f / 24.0f) * x0 - (1.0f / 12.0f) * x1 + (1.0f / 6.0f) * x2;
+        u[a][5] = x2;
+    }
+}
+
+// ==== What the two convolution kernels share around their K loops ====================================================================
+//
+//   Y = At2 [ (G4 g G6^T) . (Bt4 d Bt6^T) ] At4^T     d: 4x6 input patch, g: 3x3 filter, Y: 2x4 outputs, "." summed over c
+//
+// Tiles are 2 rows x 4 columns of outputs (F(2,3) down the rows: 4 patch rows; F(4,3) along the columns: 6 patch columns), 24 Winograd
+// positions per tile and (c, k) pair where the direct convolution has 72 multiply-adds.  A workgroup (256 threads, one wavefront per
+// SIMD) computes a 16x16-pixel block = 8 x 4 = 32 tiles = one MFMA block of rows, for 64 output channels.  Wavefront `a` owns ROW a of the
+// 4 x 6 position grid (positions 6a .. 6a+5) for the 32 tiles and all 64 output channels (two 32-channel blocks, kb): 6 x 2 = 12 MFMA
+// blocks = 192 accumulators.  Row a of Bt4 d is one sum or difference of two patch rows (wino_rows), followed by the 6-point column
+// transform Bt6; every transformed value feeds two MFMAs (kb).  Filter operands never touch LDS (L2 -> registers, each kernel in its own
+// layout); the raw 18x18-pixel patch goes global -> LDS and is read from there, no transformed copy exists anywhere.
+//
+// CANVAS.  Activations are channels-last [pixel][C] fp32.  The images of a (level, launch) stand in a GRID on a virtual canvas, image i
+// at grid cell (i / gcols, i % gcols), top-left canvas pixel (row (H + 1), col (W + 1)): one zero row / column between neighbours is the
+// convolution's padding for both (reads outside an image return 0.0), and 16x16 blocks are cut from the canvas without regard to image
+// boundaries -- the partial blocks at the right and bottom edges are paid once per level instead of once per image.  A table of block
+// records (int4 {first pixel of image 0 in `in`, in `out`, gcols << 24 | H << 12 | W, n_images << 24 | by << 12 | bx}) says where.
+struct WinoBlock {
+    int64_t base_px, out_px;              // first pixel of image 0 in `in` / `out`
+    int gcols, H, W, n_img, y0, x0, Hv, Wv, HWi;
+    float rHv, rWv;
+};
+__device__ __forceinline__ WinoBlock wino_block(const int4 desc) {
+    WinoBlock B;
+    B.base_px = desc.x; B.out_px = desc.y;
+    B.gcols = (desc.z >> 24) & 0xFF; B.H = (desc.z >> 12) & 0xFFF; B.W = desc.z & 0xFFF; B.n_img = (desc.w >> 24) & 0xFF;
+    B.y0 = ((desc.w >> 12) & 0xFFF) * 16; B.x0 = (desc.w & 0xFFF) * 16; B.Wv = B.W + 1; B.Hv = B.H + 1; B.HWi = B.H * B.W;
+    B.rWv = 1.0f / (float)B.Wv; B.rHv = 1.0f / (float)B.Hv;
+    return B;
+}
+// canvas coordinate v >= 0 -> (grid index, coordinate inside the cell); canvas extents < 2^16: exact after the fix-up
+__device__ __forceinline__ int wino_cell(int v, int step, float rstep, int& idx) {
+    int n = (int)((float)v * rstep);
+    n -= n * step > v ? 1 : 0;
+    n += (n + 1) * step <= v ? 1 : 0;
+    idx = n;
+    return v - n * step;
+}
+
+// Row a of Bt4 d = x[row0] + sgn x[row1], wave-uniform:   a = 0: d0 - d2      a = 1: d1 + d2      a = 2: d2 - d1      a = 3: d1 - d3
+__device__ __forceinline__ void wino_rows(int a, int& row0, int& row1, float& sgn) {
+    row0 = a == 0 ? 0 : a == 2 ? 2 : 1;
+    row1 = a == 2 ? 1 : a == 3 ? 3 : 2;
+    sgn = a == 1 ? 1.0f : -1.0f;
+}
+
+// PATCH IN LDS, one stage (WINO_SB_FLOATS; two of them) per SUPER-CHUNK of 32 input channels = the 128-byte line a pixel owns in the
+// channels-last source: [pixel slot][8 parts of 16 B], so that 8 consecutive lanes of an LDS-DMA instruction fetch ONE full line
+// (measured, profiles/r03_experiments.md: a pixel per lane -- 64 lines per instruction, each line fetched again by the next three
+// 8-channel chunks -- stalls the in-order instruction streams by ~400 cycles per chunk once the lines come from HBM; full lines cost 55).
+// Pixel slot of patch pixel (py, px): 2 (rank(py) 18 + px) + ((py >> 2) & 1), rank = (py & 3) + 4 (py >> 3) (rows 0-3, 8-11, 16, 17
+// on the even slots, rows 4-7, 12-15 on the odd ones); part P of that pixel sits at sub-slot (P + rot) & 7,
+// rot = ((px >> 2) & 3) + 4 ((py >> 1) & 1): the 16 lanes a ds_read_b128 serves per LDS cycle (4 tile rows x 4 tile columns,
+// one part) then hit 16 different 16-byte bank groups -- conflict-free for every (row, column, chunk).
+// (The kernels keep their tables of these addresses themselves, `areg` / `amini`: a lane of k11 reads the 4 chunks of a super-chunk in
+// 4-channel parts, a lane of k12 its 2 x 2 halves.)
+// The first 16 input channels come from two MINI stages behind the two stages (8 channels each, 324 pixels x 32 B, 3 LDS-DMA
+// instructions per wave each), so the matrix cores start after 20 KB have landed instead of a 48 KB super-chunk; super-chunk 0 lands
+// behind the first MFMAs.  Mini layout: 16-byte slot 2 (py 21 + (px & 3) 5 + (px >> 2)) + half: the 16 lanes of a ds_read_b128 group hit
+// every bank group twice.  Behind the mini stages: the pixel table.
+//
+// Where a patch pixel lives in the source: thread t works out pixel t (and t + 256) of the 18 x 18 patch ONCE -- canvas row -> (grid
+// row, row inside the image), canvas column -> (grid column, column) -- and parks its pixel index in LDS (-1: outside every image, or a
+// pixel whose need bit is off (sparse launches; need[i]: the bits of pixels t = tid + 256 i): the loads then use a buffer offset past the
+// resource, which reads 0.0 -- that IS the zero padding of the convolution); the lanes look their pieces up there: two divisions per
+// thread instead of two per lane and piece.  WINO_FILL_PIXEL_TABLE fills the table and publishes it (a barrier).
+__device__ __forceinline__ int* wino_pixel_table(float* lds) { return reinterpret_cast<int*>(lds + 2 * WINO_SB_FLOATS + 2 * 3072); }
+// (A statement macro, like WINO_FILL_SLOTS below: as functions the two are simplified on their own before they are inlined -- without
+// the kernel's bound on threadIdx and with their arguments in place of the kernel's values -- and come out as different, if equivalent,
+// integer arithmetic, which reschedules the prologue of k12's hand-pinned instruction stream.  tid: the thread index.)
+#define WINO_FILL_PIXEL_TABLE(pix_tab, B, need, tid)                                                                                  \
+    _Pragma("unroll") for (int it_ = 0; it_ < 2; ++it_) {                                                                             \
+        const int t = (tid) + 256 * it_;                                                                                              \
+        if (t >= 325) break;                                                                                                          \
+        const int py = t / 18, px = t - py * 18, vy = (B).y0 - 1 + py, vx = (B).x0 - 1 + px;                                          \
+        int m, n;                                                                                                                     \
+        const int gy = wino_cell(vy < 0 ? 0 : vy, (B).Hv, (B).rHv, m), gx = wino_cell(vx < 0 ? 0 : vx, (B).Wv, (B).rWv, n), img = m * (B).gcols + n; \
+        const bool ok = (t < 324) & (vy >= 0) & (gy < (B).H) & (vx >= 0) & (gx < (B).W) & (n < (B).gcols) & (img < (B).n_img) & ((((need)[it_] >> (t & 31)) & 1u) != 0); \
+        (pix_tab)[t] = ok ? img * (B).HWi + gy * (B).W + gx : -1;      /* entry 324 = -1: the "no pixel" slots of the fills point here */ \
+    }                                                                                                                                 \
+    __syncthreads();                                                                                                                  \
+    WINO_STAMP(8)                                      /* (the block record has arrived, the pixel table stands) */
+
+// The fills of a lane.  LDS-DMA of a stage: 48 instructions of 8 pixel slots x 8 parts (the last 3 fetch nothing), wave a issues
+// 12 a .. 12 a + 11.  Lane (l3 = lane >> 3, q = lane & 7) of instruction I fills sub-slot q of pixel slot 8 I + l3 with part
+// (q - rot) & 7 of its pixel.  The buffer resource (the record's images, from the first channel the workgroup reads) is the caller's.
+// What does not depend on the block record -- slot_e: the lane's 12 pixel slots of a stage fill, patch pixel | rot << 16 (a constant
+// table: asked for first, so that nothing queues behind the patch loads that follow); mini_pidx: the patch pixel of its 3 slots of a
+// mini-stage fill (324: none).
+#define WINO_FILL_SLOTS(slot_e, mini_pidx, tid)                                                                                       \
+    _Pragma("unroll") for (int i = 0; i < 12; ++i) (slot_e)[i] = g_wino_slots.v[96 * ((tid) >> 6) + 8 * i + (((tid) & 63) >> 3)];     \
+    _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                                                                   \
+        const int pp = ((((tid) >> 6) * 3 + r) * 64 + ((tid) & 63)) >> 1, py = pp / 21, pi = pp - py * 21, px = 4 * (pi % 5) + pi / 5; \
+        (mini_pidx)[r] = py < 18 && pi < 20 && px < 18 ? py * 18 + px : 324;                                                          \
+    }
+// pixel index of the table -> byte offset of its 4-float part in the source.  (P by pointer, not by reference, on purpose: behind a
+// reference the load of in_stride is known to be safe, the compiler then turns the branch into a select, and k12's prologue comes out
+// in another order than the one its instruction stream was measured with.)
+__device__ __forceinline__ int wino_byte_offset(const WinoParams* P, int pix, int part4) {
+    return pix >= 0 ? (pix * P->in_stride + part4) * 4 : 0x7FFFFF00;
+}
+__device__ __forceinline__ void wino_mini_offsets(const WinoParams* P, const int* pix_tab, const int (&mini_pidx)[3], int (&dmini)[3], int lane) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) dmini[r] = pix_tab[mini_pidx[r]];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) dmini[r] = wino_byte_offset(P, dmini[r], 4 * (lane & 1));
+}
+// (the 12 offsets of a stage fill, doff[i] = wino_byte_offset(P, pix_tab[slot_e[i] & 0xFFFF], 4 (((lane & 7) - (slot_e[i] >> 16)) & 7)),
+// are a lambda of each kernel, defined here and called behind the first loads: every shared form of it reorders k12's prologue)
+typedef __attribute__((address_space(3))) void wino_lds_void;
+// wave a's piece r (1 KB) of the 8-channel patch `which` (0 / 1) into its mini stage
+__device__ __forceinline__ void wino_mini_piece(__amdgpu_buffer_rsrc_t rsrc, float* lds, int a, int which, int r, int dmini_r) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (wino_lds_void*)(lds + 2 * WINO_SB_FLOATS + which * 3072 + (a * 3 + r) * 256), 16, dmini_r, which * 32, 0, 0);
+}
+// wave a's piece i (1 KB: 8 pixels x 32 channels) of super-chunk sc, straight into LDS
+__device__ __forceinline__ void wino_patch_piece(__amdgpu_buffer_rsrc_t rsrc, float* stage, int a, int sc, int i, int doff_i) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (wino_lds_void*)(stage + (a * 12 + i) * 256), 16, doff_i, sc * 128, 0, 0);
+}
+
+// OUTPUT TRANSFORM Y = At2 M At4^T, At2 = [[1,1,1,0],[0,1,-1,-1]], At4 = [[1,1,1,1,1,0],[0,1,-1,2,-2,0],[0,1,1,4,4,0],[0,1,-1,8,-8,1]].
+// Every wave applies At4 to its row of 6 positions in registers (4 output columns) and parks Z[a][tile][column][channel] in LDS (the
+// stages have been read out: they become the staging); the store pass combines the four rows in a fixed order:
+// Y[0][x] = (Z[0][x] + Z[1][x]) + Z[2][x],  Y[1][x] = (Z[1][x] - Z[2][x]) - Z[3][x].
+// The MFMAs run with the FILTER as the row operand: a lane's accumulator register reg of block (p, kb) is channel
+// 32 kb + (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of tile lane & 31 -- four consecutive channels per register quad, so the
+// transform runs on packed pairs and a 16-byte store parks 4 channels.  Staging: Z[a][tile][column e][64 channels], a tile's 4 x 64
+// floats + 4 pad (1040 B: the 8 tiles of a store's lane group hit 8 different 16-byte bank groups), 4 x 32 x 1040 B = WINO_LDS_BYTES.
+constexpr int WINO_TS = 260;               // floats per (a, tile)
+constexpr int WINO_ZA = 32 * WINO_TS;      // floats per position row a
+// -> false: an elimination build (POD_WINO_ELIM & 128 / & 32) that ends here
+__device__ __forceinline__ bool wino_output_stage(const f32x16 (&acc)[12], float* lds, int a, int i32, int h) {
+    if (POD_WINO_ELIM & 128) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) asm volatile("" ::"v"(acc[i]));
+        return false;
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 m[6];
+#pragma unroll
+            for (int p6 = 0; p6 < 6; ++p6) m[p6] = f32x4{acc[p6 * 2 + kb][4 * g], acc[p6 * 2 + kb][4 * g + 1], acc[p6 * 2 + kb][4 * g + 2], acc[p6 * 2 + kb][4 * g + 3]};
+            const f32x4 s1 = m[1] + m[2], d1 = m[1] - m[2], s2 = m[3] + m[4], d2 = m[3] - m[4];
+            float* o = lds + (a * 32 + i32) * WINO_TS + kb * 32 + 8 * g + 4 * h;
+            *reinterpret_cast<f32x4*>(o) = (m[0] + s1) + s2;
+            *reinterpret_cast<f32x4*>(o + 64) = __builtin_elementwise_fma(f32x4{2.f, 2.f, 2.f, 2.f}, d2, d1);
+            *reinterpret_cast<f32x4*>(o + 128) = __builtin_elementwise_fma(f32x4{4.f, 4.f, 4.f, 4.f}, s2, s1);
+            *reinterpret_cast<f32x4*>(o + 192) = __builtin_elementwise_fma(f32x4{8.f, 8.f, 8.f, 8.f}, d2, d1) + m[5];
+        }
+    __syncthreads();
+    WINO_STAMP(4);
+    return !(POD_WINO_ELIM & 32);
+}
+
+// STORE PASSES: staging -> y = (row combination) * inv + bias -> ReLU -> dropout -> memory.
+struct WinoStore {
+    float* out;               // of the workgroup's set (and input-channel split)
+    const float* bias;        // null: none
+    float* out_amax;          // null, or: the pass returns the abs-max of what the thread stores (the caller publishes it)
+    float inv;                // what takes the operand scales of the f16 split off again -- a power of two, exact inside the fma; 1: fp32 operands
+    uint64_t offset;          // Philox counter of the set's first 8 floats
+    int replicas, k_planes;
+};
+__device__ __forceinline__ void wino_relu4(f32x4& v) {
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+}
+// Dropout of the 8 consecutive floats at e (a multiple of 8): ONE Philox call, 16 mask bits per element -- pod_bias_act's mask with
+// counter word 0, pod_expand_dropout's (the replicas) with word 2.
+__device__ __forceinline__ void wino_dropout8(f32x4& v0, f32x4& v1, int64_t e, uint64_t offset, uint32_t word, uint64_t key, uint32_t thresh, float scale) {
+    const uint64_t ctr = offset + (uint64_t)(e >> 3);
+    const u32x4 r4 = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), word, STREAM_DROPOUT_CONV}, (uint32_t)key, (uint32_t)(key >> 32));
+    v0.x = (r4.x & 0xFFFFu) >= thresh ? v0.x * scale : 0.f;
+    v0.y = (r4.x >> 16) >= thresh ? v0.y * scale : 0.f;
+    v0.z = (r4.y & 0xFFFFu) >= thresh ? v0.z * scale : 0.f;
+    v0.w = (r4.y >> 16) >= thresh ? v0.w * scale : 0.f;
+    v1.x = (r4.z & 0xFFFFu) >= thresh ? v1.x * scale : 0.f;
+    v1.y = (r4.z >> 16) >= thresh ? v1.y * scale : 0.f;
+    v1.z = (r4.w & 0xFFFFu) >= thresh ? v1.z * scale : 0.f;
+    v1.w = (r4.w >> 16) >= thresh ? v1.w * scale : 0.f;
+}
+
+// NCHW planes (the predictors: the layout K1 streams): thread -> (channel, row of the block, 4 pixels along x = one tile's columns);
+// 64-byte runs per (channel, row).  No dropout, no replicas.
+__device__ __forceinline__ float wino_store_planes(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+    const int tid = threadIdx.x;
+    float lmax = 0.0f;
+    const f32x4 inv = f32x4{S.inv, S.inv, S.inv, S.inv};
+    const int oy = (tid >> 2) & 15, ox = (tid & 3) * 4;
+    int m;
+    const int gy = wino_cell(B.y0 + oy, B.Hv, B.rHv, m);
+    int64_t px0[4];                                   // output pixel (of plane 0) per column, -1: not a pixel of any image
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        int n;
+        const int gx = wino_cell(B.x0 + ox + e, B.Wv, B.rWv, n), img = m * B.gcols + n;
+        px0[e] = (n < B.gcols && img < B.n_img && gx < B.W && gy < B.H) ? (B.out_px + (int64_t)img * B.HWi) * S.k_planes + (int64_t)gy * B.W + gx : -1;
+    }
+    const bool vec = px0[0] >= 0 && px0[3] == px0[0] + 3 && (px0[0] & 3) == 0 && (B.HWi & 3) == 0;
+    const int tile = (oy >> 1) * 4 + (tid & 3);
+#pragma unroll 2
+    for (int it = 0; it < 16; ++it) {
+        const int k = it * 4 + (tid >> 6), kg = ks * 64 + k;
+        if (kg >= S.k_planes) continue;
+        const float bias = S.bias ? S.bias[kg] : 0.0f;
+        float y[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float* r = lds + tile * WINO_TS + e * 64 + k;                 // Z[a][tile][e][k] at + a * WINO_ZA
+            y[e] = (oy & 1) == 0 ? (r[0] + r[WINO_ZA]) + r[2 * WINO_ZA] : (r[WINO_ZA] - r[2 * WINO_ZA]) - r[3 * WINO_ZA];
+        }
+        f32x4 v = __builtin_elementwise_fma(f32x4{y[0], y[1], y[2], y[3]}, inv, f32x4{bias, bias, bias, bias});
+        if (P.relu) wino_relu4(v);
+        if (S.out_amax)
+            lmax = fmaxf(fmaxf(lmax, px0[0] >= 0 ? fabsf(v.x) : 0.f), fmaxf(fmaxf(px0[1] >= 0 ? fabsf(v.y) : 0.f, px0[2] >= 0 ? fabsf(v.z) : 0.f), px0[3] >= 0 ? fabsf(v.w) : 0.f));
+        float* plane = S.out + (int64_t)kg * B.HWi;
+        if (vec) {
+            *reinterpret_cast<f32x4*>(plane + px0[0]) = v;
+        } else {
+            if (px0[0] >= 0) plane[px0[0]] = v.x;
+            if (px0[1] >= 0) plane[px0[1]] = v.y;
+            if (px0[2] >= 0) plane[px0[2]] = v.z;
+            if (px0[3] >= 0) plane[px0[3]] = v.w;
+        }
+    }
+    return lmax;
+}
+
+// Channels-last: thread -> 8 consecutive channels (one Philox call) of one pixel column, rows of one parity.
+__device__ __forceinline__ float wino_store_channels_last(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+    const int tid = threadIdx.x;
+    float lmax = 0.0f;
+    const f32x4 inv = f32x4{S.inv, S.inv, S.inv, S.inv};
+    const int k8 = (tid & 7) * 8, kg = ks * 64 + k8, ox = (tid >> 3) & 15, odd = tid >> 7;
+    f32x4 bias0 = f32x4{0.f, 0.f, 0.f, 0.f}, bias1 = bias0;
+    if (S.bias) {
+        bias0 = *reinterpret_cast<const f32x4*>(S.bias + kg);
+        bias1 = *reinterpret_cast<const f32x4*>(S.bias + kg + 4);
+    }
+    const uint64_t drop_key = P.thresh ? dropout_key(P.seed, P.epoch) : 0ull;
+    int n;
+    const int gx = wino_cell(B.x0 + ox, B.Wv, B.rWv, n);
+    const bool col_ok = n < B.gcols && gx < B.W;
+    int m, gy = wino_cell(B.y0 + odd, B.Hv, B.rHv, m) - 2;                       // canvas row y0 + 2 it + odd: grid row m, image row gy (H: the separator)
+    const float* rbase = lds + (ox >> 2) * WINO_TS + (ox & 3) * 64 + k8 + (odd ? WINO_ZA : 0);      // Z[a][tile][ox & 3][k8] of row a = odd
+    // Rows in BATCHES of four: the 24 LDS reads of a batch are issued together (one round trip, not four behind four branches), then
+    // the four rows' arithmetic, Philox calls and stores run as independent chains (round 5: 12.6 k -> cycles of the workgroup's 81 k)
+#pragma unroll 1
+    for (int g = 0; g < 2; ++g) {
+        f32x4 z[4][6];
+        int gyi[4], imgi[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            gy += 2;
+            if (gy >= B.Hv) {
+                gy -= B.Hv;
+                ++m;
+            }
+            gyi[it] = gy;
+            imgi[it] = m * B.gcols + n;
+            const float* r = rbase + (4 * g + it) * 4 * WINO_TS;                          // tile (4 g + it, ox >> 2)
+            z[it][0] = *reinterpret_cast<const f32x4*>(r); z[it][1] = *reinterpret_cast<const f32x4*>(r + 4);
+            z[it][2] = *reinterpret_cast<const f32x4*>(r + WINO_ZA); z[it][3] = *reinterpret_cast<const f32x4*>(r + WINO_ZA + 4);
+            z[it][4] = *reinterpret_cast<const f32x4*>(r + 2 * WINO_ZA); z[it][5] = *reinterpret_cast<const f32x4*>(r + 2 * WINO_ZA + 4);
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int gy_ = gyi[it], img = imgi[it];
+            if (!col_ok || gy_ >= B.H || img >= B.n_img) continue;
+            f32x4 v0 = __builtin_elementwise_fma(odd ? (z[it][0] - z[it][2]) - z[it][4] : (z[it][0] + z[it][2]) + z[it][4], inv, bias0);
+            f32x4 v1 = __builtin_elementwise_fma(odd ? (z[it][1] - z[it][3]) - z[it][5] : (z[it][1] + z[it][3]) + z[it][5], inv, bias1);
+            if (P.relu) {
+                wino_relu4(v0);
+                wino_relu4(v1);
+            }
+            int64_t e = (B.out_px + (int64_t)img * B.HWi + (int64_t)gy_ * B.W + gx) * P.out_stride + kg;      // a multiple of 8
+            if (S.out_amax) {                                        // (a masked value is 0 or v * scale: v * scale bounds both, whatever the masks)
+                const f32x4 a0v = __builtin_elementwise_abs(v0), a1v = __builtin_elementwise_abs(v1);
+                const float mx = fmaxf(fmaxf(fmaxf(a0v.x, a0v.y), fmaxf(a0v.z, a0v.w)), fmaxf(fmaxf(a1v.x, a1v.y), fmaxf(a1v.z, a1v.w)));
+                lmax = fmaxf(lmax, P.thresh ? mx * P.scale : mx);
+            }
+            if (S.replicas > 0) {                                    // (0: an ordinary launch; 1: one "replica" under the replicas' mask)
+                // The first conv of an MC-dropout subnet: its output is the same for every run, so the store pass writes the runs'
+                // masked replicas itself (replica r = image r of the output canvas) -- the separate expand pass read this tensor back
+                // and wrote them in a launch of its own.
+                for (int rep = 0; rep < S.replicas; ++rep, e += (int64_t)B.HWi * P.out_stride) {
+                    f32x4 w0 = v0, w1 = v1;
+                    if (P.thresh) wino_dropout8(w0, w1, e, S.offset, 2u, drop_key, P.thresh, P.scale);
+                    *reinterpret_cast<f32x4*>(S.out + e) = w0;
+                    *reinterpret_cast<f32x4*>(S.out + e + 4) = w1;
+                }
+                continue;
+            }
+            if (P.thresh && !(POD_WINO_ELIM & 64)) wino_dropout8(v0, v1, e, S.offset, 0u, drop_key, P.thresh, P.scale);
+            *reinterpret_cast<f32x4*>(S.out + e) = v0;
+            *reinterpret_cast<f32x4*>(S.out + e + 4) = v1;
+        }
+    }
+    return lmax;
+}
 
 }  // namespace pod

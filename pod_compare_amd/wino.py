@@ -207,7 +207,7 @@ class WinoConv:
 
     def replicas(self, src: torch.Tensor, dst: torch.Tensor, table: torch.Tensor, replicas: int, relu: bool = False, dropout_p: float = 0.0,
                  seed: int = 0, offset: int = 0, epoch: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """conv + bias (+ ReLU) of ONE image per level, stored `replicas` times with a dropout mask each (pod_wino_conv3x3_split_replicas):
+        """conv + bias (+ ReLU) of ONE image per level, stored `replicas` times with a dropout mask each (PodWinoConv with `replicas`):
         table = block_table(levels, 1, out_copies=replicas); dst: the `replicas` images per level, channels-last.  The masks are those
         of pod_expand_dropout called per level with offset + (first float of the level in dst) / 8 (`expand_offset`)."""
         assert self.split and self.K == self.Kpad and 1 <= replicas <= 127
@@ -217,7 +217,7 @@ class WinoConv:
         return dst
 
     def splits_for(self, n_blocks: int, cus: int = 256) -> int:
-        """How many ways to cut the input channels of a launch of n_blocks output blocks (pod_wino_conv3x3_split_partial): small maps
+        """How many ways to cut the input channels of a launch of n_blocks output blocks (PodWinoConv with `n_splits`): small maps
         give this tiling too few workgroups for the chip (res5 of a 768 x 1344 frame: 6 blocks x 8 filter slices = 48), each walking all
         C / 16 chunks; cutting C makes n_splits x as many workgroups of 1 / n_splits the chunks.  1 = no split."""
         if not self.split:
