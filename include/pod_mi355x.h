@@ -355,7 +355,7 @@ int pod_wino_conv3x3(const float* in, float* out, const float* U, const float* b
 
 /* ---- operand abs-max records (round 5; ABI 12) ----------------------------------------------------------------------------------
  * The split convolutions below form every fp32 product from TWO F16 terms per operand; f16 has fp32's precision budget here (11 + 1 + 11
- * bits, pod_wino.h) but not its range, so every operand tensor is scaled by a power of two derived from its abs-max.  Filters: static,
+ * bits, pod_split_gemm.h) but not its range, so every operand tensor is scaled by a power of two derived from its abs-max.  Filters: static,
  * inside the *_filter_split transforms.  Activations: a device RECORD `in_amax` of POD_AMAX_FLOATS floats whose largest element is
  * >= max |x| over what the launch reads (only elements k * POD_AMAX_STRIDE, k < POD_AMAX_SLOTS, are read or written: producers spread
  * their atomics over 16 cache lines -- thousands of same-address atomics serialise in the L2) -- an upper bound is

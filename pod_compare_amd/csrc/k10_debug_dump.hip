@@ -9,7 +9,7 @@
 // (tests/test_native_exact_gpu.py).  Not on the inference path; nothing else calls them.
 #include "pod_device.h"
 #include "../../include/pod_mi355x_test.h"
-#include "pod_wino.h"
+#include "pod_split_gemm.h"
 
 namespace pod {
 
@@ -80,7 +80,7 @@ extern "C" int pod_dump_box_normals(const PodConfig* cfg, const int32_t* global_
     return POD_OK;
 }
 
-// pod_debug_f16_split2 -- test support: the 2-way f16 split of the power-of-two-scaled operands of the round-5 split kernels (pod_wino.h:
+// pod_debug_f16_split2 -- test support: the 2-way f16 split of the power-of-two-scaled operands of the round-5 split kernels (pod_split_gemm.h:
 // wino_f16_split2, the functions the kernels' loops call): terms[2][n] f16 bit patterns of x[n] * scale (n even).
 namespace pod {
 __global__ void __launch_bounds__(256) k_debug_f16_split2(const float* __restrict__ x, float scale, uint16_t* __restrict__ terms, int64_t n) {

@@ -8,11 +8,12 @@
 //   y[p][k] = act( sum_c x[pin(p)][c] w[k][c] + bias[k] (+ residual[p][k]) ),   x, y, residual channels-last ([pixel][channel])
 //
 // Same arithmetic contract as pod_wino_conv3x3_split (k12).  Rounds 3-4: exact 3-way bf16 splits of both operands, 6 partial products.
-// Round 5: 2-way F16 splits of the power-of-two-scaled operands (pod_wino.h: x s = x0 + x1 to 2^-23 |x s|), 3 partial products on
+// Round 5: 2-way F16 splits of the power-of-two-scaled operands (pod_split_gemm.h: x s = x0 + x1 to 2^-23 |x s|), 3 partial products on
 // v_mfma_f32_32x32x16_f16, fp32 accumulate -- half the matrix instructions and a shorter fp32 accumulation chain (closer to fp64 than
 // both the bf16 form and the fp32 MFMA: tools/f16_split_numerics.hip).  The weights are split once (pod_conv1x1_filter_split, scale from
 // their own abs-max), the activations in the loop with the very functions k12 uses (wino_f16_pair_scaled / wino_f16_residual_scaled),
-// their scale from the launch's `in_amax` word; the store pass publishes the output's abs-max for the next convolution.
+// their scale from the launch's `in_amax` word; the store pass publishes the output's abs-max for the next convolution.  The tile's
+// parts -- constants, filter ring, k-step, whole-line epilogue, filter preparation -- are pod_split_gemm.h's, shared with k14.
 //
 // Mapping.  Workgroup = ONE wavefront = 64 output pixels x (32 NCB) output channels (NCB = 2 as shipped): 2 NCB accumulator blocks
 // of 32 x 32.  The filter is the ROW operand of the MFMAs (a lane's accumulator quad is 4 consecutive output
@@ -23,7 +24,7 @@
 // back to back, so the activations come out of that XCD's L2 after the first.  One-wavefront workgroups because nothing is shared
 // through LDS and small maps need every tile to be its own schedulable unit (res5: 1008 pixels x 2048 channels = 256 tiles); where
 // even that leaves the chip idle the input channels are cut over grid.y (partial sums, finished by pod_conv1x1_reduce in a fixed order).
-#include "pod_wino.h"
+#include "pod_split_gemm.h"
 
 #ifdef POD_C1_TRACE       // experiment builds: 10-ns time stamps of every wavefront (start | first k-step done | loop done | end), pod_c1_trace_dump()
 static __device__ long long g_c1_trace[8192 * 4];
@@ -42,10 +43,6 @@ static __device__ long long g_c1_cycles[8192 * 4];      // s_memtime beside the 
 
 namespace pod {
 
-typedef uint32_t c1_u32x4 __attribute__((ext_vector_type(4)));
-constexpr int C1_KS_U16 = 2 * 2 * 256;       // u16 values of one (32-channel block, k-step): [term 2][h 2][i32 32][8 f16]
-constexpr int C1_TOP = 14;                   // both operands: scaled abs-max in [2^14, 2^15)
-
 struct C1Params {
     const float* x;
     float* y;                 // output, or the partial sums of split 0 (split z at + z * split_stride)
@@ -61,38 +58,18 @@ struct C1Params {
     int64_t split_stride;     // floats between partial outputs; 0: no split (bias / residual / ReLU applied here)
 };
 
-// weight (Cout, Cin) fp32 -> Ws: two nearest-even f16 terms per scaled value (w s = w0 + w1 to 2^-23), in the order a lane loads them;
-// s = the power of two that puts the weight's abs-max (first pass, -> the trailer word) into [2^14, 2^15)
-__global__ void __launch_bounds__(256) k_conv1x1_filter_amax(const float* __restrict__ w, int64_t n, float* __restrict__ amax) {
-    float m = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    wino_publish_amax1(amax, m);
-}
+// weight (Cout, Cin) fp32 -> Ws: the GEMM matrix as it is, one thread per (cout, pair of cins)
 __global__ void __launch_bounds__(256) k_conv1x1_filter_split(const float* __restrict__ w, uint16_t* __restrict__ Ws, const float* __restrict__ amax, int32_t Cout,
                                                               int32_t Cin) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // one thread per (cout, pair of cins)
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)Cout * (Cin / 2)) return;
     const int k = (int)(t / (Cin / 2)), c = 2 * (int)(t % (Cin / 2));
-    uint32_t terms[2];
-    wino_f16_split2(w[(int64_t)k * Cin + c], w[(int64_t)k * Cin + c + 1], wino_pow2_scale(*amax, C1_TOP), terms);
-    const int nks = Cin >> 4, cb = k >> 5, i32 = k & 31, ks = c >> 4, h = (c >> 3) & 1, e = c & 7;
-#pragma unroll
-    for (int term = 0; term < 2; ++term) {
-        uint16_t* d = Ws + ((((int64_t)cb * nks + ks) * 2 + term) * 2 + h) * 256 + i32 * 8 + e;
-        d[0] = (uint16_t)(terms[term] & 0xFFFFu);
-        d[1] = (uint16_t)(terms[term] >> 16);
-    }
+    sg_store_filter_terms(Ws, Cin >> 4, k, c, w[(int64_t)k * Cin + c], w[(int64_t)k * Cin + c + 1], amax);
 }
 
-template <int I>
-using c1_ic = std::integral_constant<int, I>;
-
-// RING: register buffers of one k-step each; loads run RING - 1 k-steps ahead.  3 leaves room for two wavefronts per SIMD.  Deeper rings
-// were measured on the launches that have at most one wavefront per SIMD anyway (res4 / res5, the laterals: 1600 cycles per k-step
-// against the 768 of its MFMAs) and change nothing (ring 4 / 5 / 6: 1.17 / 1.15 / 1.20 ms per image against 1.18): what those
-// wavefronts wait for is not the distance of the loads but the L1's time for the activation fragments -- 32 cache lines per
-// instruction (profiles/r04_experiments.md, K13).
-template <int NCB, int RING>
+// The direct-fragment form: every k-step's fragments straight from memory, through the ring (SG_RING, pod_split_gemm.h).  Serves the
+// launches whose workgroup sets accumulate an ODD number of k-steps (the LDS form below takes whole pairs).
+template <int NCB>
 __global__ void __launch_bounds__(64) k_conv1x1_split(const C1Params P) {
     const int lane = threadIdx.x & 63, i32 = lane & 31, h = lane >> 5;
     // blockIdx & 7 is the XCD (round-robin dispatch): an XCD takes pixel tiles xcd, xcd + 8, ... and runs all channel tiles of one back to back
@@ -118,88 +95,53 @@ __global__ void __launch_bounds__(64) k_conv1x1_split(const C1Params P) {
     const float* __restrict__ xa[2];
 #pragma unroll
     for (int pb = 0; pb < 2; ++pb) xa[pb] = P.x + (int64_t)pin[pb] * P.Cin + ks0 * 16 + 8 * h;
-    const uint16_t* __restrict__ const wa = P.Ws + ((int64_t)(tc * NCB) * nks_all + ks0) * C1_KS_U16 + (h * 32 + i32) * 8;     // + cb * nks_all * 1024 + ks * 1024 + term * 512
-    const int64_t w_cb = (int64_t)nks_all * C1_KS_U16;
-    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wino_pow2_scale(wino_read_amax(P.in_amax), C1_TOP))));
+    constexpr int RING = SG_RING;
+    const uint16_t* __restrict__ const wa = P.Ws + ((int64_t)(tc * NCB) * nks_all + ks0) * SG_KS_U16 + (h * 32 + i32) * 8;     // + cb * nks_all * 1024 + ks * 1024 + term * 512
+    const int64_t w_cb = (int64_t)nks_all * SG_KS_U16;
+    const float sx = sg_activation_scale(P.in_amax);
 
     f32x16 acc[NCB][2];
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x4 araw[RING][2][2];           // [buffer][pb][4-channel half of the lane's 8]
-    c1_u32x4 wf[RING][NCB][2];        // [buffer][cb][term]
+    sg_u32x4 wf[RING][NCB][2];        // [buffer][cb][term]
     auto load = [&](auto buf_t, int ks) __attribute__((always_inline)) {
         constexpr int buf = decltype(buf_t)::value;
-        if (!(POD_C1_ELIM & 1) || ks < RING) {
 #pragma unroll
-            for (int pb = 0; pb < 2; ++pb) {
-                araw[buf][pb][0] = *reinterpret_cast<const f32x4*>(xa[pb] + ks * 16);
-                araw[buf][pb][1] = *reinterpret_cast<const f32x4*>(xa[pb] + ks * 16 + 4);
-            }
+        for (int pb = 0; pb < 2; ++pb) {
+            araw[buf][pb][0] = *reinterpret_cast<const f32x4*>(xa[pb] + ks * 16);
+            araw[buf][pb][1] = *reinterpret_cast<const f32x4*>(xa[pb] + ks * 16 + 4);
         }
-        if (!(POD_C1_ELIM & 2) || ks < RING) {
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) wf[buf][cb][t] = *reinterpret_cast<const c1_u32x4*>(wa + cb * w_cb + (int64_t)ks * C1_KS_U16 + t * 512);
-        }
+        SG_LOAD_FILTER(wf[buf], NCB, wa, w_cb, ks);
     };
     auto step = [&](auto buf_t, auto first_t) __attribute__((always_inline)) {
         constexpr int buf = decltype(buf_t)::value;
-        constexpr bool first = decltype(first_t)::value;
-        c1_u32x4 at[2][2];            // the lane's 8 channels of its two pixels as two f16 terms
-#pragma unroll
-        for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {       // pair i: channels 2 i, 2 i + 1
-                float lo = araw[buf][pb][i >> 1][2 * (i & 1)], hi = araw[buf][pb][i >> 1][2 * (i & 1) + 1];
-                if (POD_C1_ELIM & 4) {
-                    at[pb][0][i] = at[pb][1][i] = __builtin_bit_cast(uint32_t, lo);
-                    continue;
-                }
-                const uint32_t t0 = wino_f16_pair_scaled(lo, hi, sx);
-                wino_f16_residual_scaled(t0, lo, hi, sx);
-                at[pb][0][i] = t0;
-                at[pb][1][i] = wino_f16_pair(lo, hi);
-            }
-        // the 3 partial products that matter, small ones first (as k12): w0 x1, w1 x0, w0 x0
-#pragma unroll
-        for (int prod = 0; prod < 3; ++prod) {
-            const int sa = prod == 1 ? 1 : 0;
-            const int sb = prod == 0 ? 1 : 0;
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int pb = 0; pb < 2; ++pb) {
-                    if (first && prod == 0)
-                        acc[cb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, wf[buf][cb][sa]), __builtin_bit_cast(wino_f16x8, at[pb][sb]), zero16, 0, 0, 0);
-                    else
-                        acc[cb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, wf[buf][cb][sa]), __builtin_bit_cast(wino_f16x8, at[pb][sb]), acc[cb][pb], 0, 0, 0);
-                }
-        }
+        sg_kstep<decltype(first_t)::value>(acc, wf[buf], sx, [&](int pb, int i) __attribute__((always_inline)) {
+            return f32x2{araw[buf][pb][i >> 1][2 * (i & 1)], araw[buf][pb][i >> 1][2 * (i & 1) + 1]};
+        });
     };
     // k-step j computes from buffer j % RING and, before that, refills the buffer k-step j - 1 just left with k-step j + RING - 1;
     // the buffers rotate at compile time (RING k-steps per trip of the loop)
     auto prologue = [&](auto self, auto r_t) __attribute__((always_inline)) -> void {
         constexpr int R = decltype(r_t)::value;
         if constexpr (R < RING - 1) {
-            if (R < nks) load(c1_ic<R>{}, R);
-            self(self, c1_ic<R + 1>{});
+            if (R < nks) load(sg_ic<R>{}, R);
+            self(self, sg_ic<R + 1>{});
         }
     };
-    prologue(prologue, c1_ic<0>{});
-    if (RING - 1 < nks) load(c1_ic<RING - 1>{}, RING - 1);
-    step(c1_ic<0>{}, std::true_type{});
+    prologue(prologue, sg_ic<0>{});
+    if (RING - 1 < nks) load(sg_ic<RING - 1>{}, RING - 1);
+    step(sg_ic<0>{}, std::true_type{});
     C1_STAMP(1);
     auto trip = [&](auto self, auto r_t, int ks) __attribute__((always_inline)) -> void {        // k-steps ks + R, R = 0 .. RING - 1, ks % RING == 1
         constexpr int R = decltype(r_t)::value;
         if constexpr (R < RING) {
             if (ks + R < nks) {
-                if (ks + R + RING - 1 < nks) load(c1_ic<R % RING>{}, ks + R + RING - 1);
-                step(c1_ic<(R + 1) % RING>{}, std::false_type{});
-                self(self, c1_ic<R + 1>{}, ks);
+                if (ks + R + RING - 1 < nks) load(sg_ic<R % RING>{}, ks + R + RING - 1);
+                step(sg_ic<(R + 1) % RING>{}, std::false_type{});
+                self(self, sg_ic<R + 1>{}, ks);
             }
         }
     };
-    for (int ks = 1; ks < nks; ks += RING) trip(trip, c1_ic<0>{}, ks);
+    for (int ks = 1; ks < nks; ks += RING) trip(trip, sg_ic<0>{}, ks);
 
     C1_STAMP(2);
     // ---- epilogue: a lane's accumulator register r of block (cb, pb) is channel 32 cb + (r & 3) + 8 (r >> 2) + 4 h of pixel 32 pb + i32.
@@ -211,8 +153,7 @@ __global__ void __launch_bounds__(64) k_conv1x1_split(const C1Params P) {
     const float* __restrict__ const bias = P.bias;
     const bool final_pass = P.split_stride == 0;
     const int k0 = tc * NCB * 32 + 4 * h;                       // + 32 cb + 8 q
-    // the accumulators hold (s_w w) (s_x x) sums: the two powers of two come off here, exactly, inside the multiply-add that adds the bias
-    const float inv1 = wino_pow2_inverse(sx) * wino_pow2_inverse(wino_pow2_scale(*reinterpret_cast<const float*>(P.Ws + (int64_t)P.Cout * P.Cin * 2), C1_TOP));
+    const float inv1 = sg_inverse_scale(sx, P.Ws, (int64_t)P.Cout * P.Cin * 2);
     const f32x4 inv = f32x4{inv1, inv1, inv1, inv1};
     float lmax = 0.0f;
 #pragma unroll
@@ -242,12 +183,10 @@ __global__ void __launch_bounds__(64) k_conv1x1_split(const C1Params P) {
                 v = __builtin_elementwise_fma(v, inv, final_pass && bias ? *reinterpret_cast<const f32x4*>(bias + k) : f32x4{0.f, 0.f, 0.f, 0.f});
                 if (final_pass) {
                     if (res) v += r[cb][q];
-                    if (P.relu) {
-                        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-                    }
-                    lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+                    if (P.relu) wino_relu4(v);
+                    lmax = wino_absmax4(lmax, v);
                 }
-                if (!(POD_C1_ELIM & 8) || v.x == 12345.678f) *reinterpret_cast<f32x4*>(yo + e0 + 32 * cb + 8 * q) = v;
+                *reinterpret_cast<f32x4*>(yo + e0 + 32 * cb + 8 * q) = v;
             }
         }
     }
@@ -258,15 +197,9 @@ __global__ void __launch_bounds__(64) k_conv1x1_split(const C1Params P) {
 #endif
 }
 
-// The epilogue of the LDS kernels, in whole lines: the accumulators (a lane: 4 consecutive channels of ONE pixel per register quad -- 32
-// pixels x 32 B per store instruction) go through 16 KB of LDS, [pixel 64][chunk position 16][16 B] with position = chunk ^ (pixel & 15),
-// and come back as 4 pixels x 256 B per instruction: residual loads and output stores of 8 full lines each, all 16 residual loads
-// requested before the first is used (one wavefront per SIMD: nobody else hides them).
-__device__ __forceinline__ void c1_epilogue(const C1Params& P, float* const lds_o, f32x16 (&acc)[2][2], int tp, int tc, int lane, int i32, int h, float sx) {
-    constexpr int NCB = 2;
-    const float inv1 = wino_pow2_inverse(sx) * wino_pow2_inverse(wino_pow2_scale(*reinterpret_cast<const float*>(P.Ws + (int64_t)P.Cout * P.Cin * 2), C1_TOP));
-    const f32x4 inv = f32x4{inv1, inv1, inv1, inv1};
-    float lmax = 0.0f;
+// The epilogue of the LDS kernels: sg_line_epilogue with this kernel's residual and destinations -- residual loads and output stores of
+// 8 full lines each, all 16 residual loads requested before the first is used (one wavefront per SIMD: nobody else hides them).
+__device__ __forceinline__ void c1_epilogue(const C1Params& P, float* const lds_o, f32x16 (&acc)[2][2], int tp, int tc, int lane, float sx) {
     float* __restrict__ const yo = P.y + (int64_t)blockIdx.y * P.split_stride;
     const float* __restrict__ const res = P.residual;
     const bool final_pass = P.split_stride == 0;
@@ -290,39 +223,18 @@ __device__ __forceinline__ void c1_epilogue(const C1Params& P, float* const lds_
 #pragma unroll
         for (int j = 0; j < 16; ++j) r[j] = (gp0 + 4 * j < P.P_out) ? *reinterpret_cast<const f32x4*>(res + e0 + (int64_t)(4 * j) * P.Cout) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};                            // (partial sums: no bias, residual, ReLU or abs-max -- pod_conv1x1_reduce's)
     if (final_pass && P.bias) b4 = *reinterpret_cast<const f32x4*>(P.bias + tc * 64 + 4 * oc);
-#pragma unroll
-    for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int pix = 32 * pb + i32, c = 8 * cb + 2 * q + h;
-                *reinterpret_cast<f32x4*>(lds_o + pix * 64 + 4 * (c ^ (i32 & 15))) =
-                    f32x4{acc[cb][pb][4 * q], acc[cb][pb][4 * q + 1], acc[cb][pb][4 * q + 2], acc[cb][pb][4 * q + 3]};
-            }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int pix = 4 * j + op;
-        f32x4 v = __builtin_elementwise_fma(*reinterpret_cast<const f32x4*>(lds_o + pix * 64 + 4 * (oc ^ (pix & 15))), inv, b4);      // (b4 = 0 for partial sums)
-        if (final_pass) {
-            if (res) v += r[j];
-            if (P.relu) {
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            }
-        }
-        if (gp0 + 4 * j < P.P_out) {
-            *reinterpret_cast<f32x4*>(yo + e0 + (int64_t)(4 * j) * P.Cout) = v;
-            lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-        }
-    }
-    if (final_pass && P.out_amax) wino_publish_amax(P.out_amax, lmax);
+    sg_line_epilogue(lds_o, acc, lane, sg_inverse_scale(sx, P.Ws, (int64_t)P.Cout * P.Cin * 2), b4, final_pass && res ? r : nullptr, final_pass && P.relu,
+                     final_pass ? P.out_amax : nullptr, [&](int j, int, float*& dst) __attribute__((always_inline)) {
+                         dst = yo + e0 + (int64_t)(4 * j) * P.Cout;
+                         return gp0 + 4 * j < P.P_out;
+                     });
 }
 
 // The same tile with the activations taken through LDS (the production form whenever a workgroup set accumulates an even number of
 // k-steps).  k_conv1x1_split loads a lane's MFMA fragment straight from memory: 16 B of each of 32 pixels per instruction = 32 cache
-// lines for 1 KB, and the CU's L1 takes a cycle per line -- measured (POD_C1_ELIM builds, res4 conv1): the activation loads are 6.3 of
+// lines for 1 KB, and the CU's L1 takes a cycle per line -- measured (elimination builds of round 4, res4 conv1): the activation loads are 6.3 of
 // the launch's 31.8 us, the filter loads (8 lines per instruction) 1.7.  Here a PAIR of k-steps (32 channels = one 128-B line per
 // pixel) is loaded in whole lines -- 8 instructions of 8 pixels x 128 B -- one pair ahead, parked in LDS, and the fragments come back
 // by ds_read_b128.  LDS image of a pair: [pixel 64][chunk position 8][16 B]; position c of pixel p holds channels 4 (c ^ key(p)) ..
@@ -363,9 +275,9 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
     }
     const float* __restrict__ const xg = P.x;
     const int key = (i32 >> 1) & 7;
-    const uint16_t* __restrict__ const wa = P.Ws + ((int64_t)(tc * NCB) * nks_all + ks0) * C1_KS_U16 + (h * 32 + i32) * 8;
-    const int64_t w_cb = (int64_t)nks_all * C1_KS_U16;
-    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wino_pow2_scale(wino_read_amax(P.in_amax), C1_TOP))));
+    const uint16_t* __restrict__ const wa = P.Ws + ((int64_t)(tc * NCB) * nks_all + ks0) * SG_KS_U16 + (h * 32 + i32) * 8;
+    const int64_t w_cb = (int64_t)nks_all * SG_KS_U16;
+    const float sx = sg_activation_scale(P.in_amax);
 
     f32x16 acc[NCB][2];
 #pragma unroll
@@ -376,7 +288,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
             for (int r = 0; r < 16; ++r) acc[cb][pb][r] = 0.f;
     const int npairs = nks >> 1;
     f32x4 stg[8];                     // the pair in flight
-    c1_u32x4 wf[3][NCB][2];           // [buffer][cb][term]
+    sg_u32x4 wf[SG_RING][NCB][2];     // [buffer][cb][term]
     auto stage_load = [&](int pair) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) stg[j] = *reinterpret_cast<const f32x4*>(xg + soff[j] + pair * 32);
@@ -385,13 +297,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
 #pragma unroll
         for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(&lds_a[b][j * 256 + lane * 4]) = stg[j];
     };
-    auto load_w = [&](auto buf_t, int ks) __attribute__((always_inline)) {
-        constexpr int buf = decltype(buf_t)::value;
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) wf[buf][cb][t] = *reinterpret_cast<const c1_u32x4*>(wa + cb * w_cb + (int64_t)ks * C1_KS_U16 + t * 512);
-    };
+    auto load_w = [&](auto buf_t, int ks) __attribute__((always_inline)) { SG_LOAD_FILTER(wf[decltype(buf_t)::value], NCB, wa, w_cb, ks); };
     // Built, measured and dropped (profiles/r04_experiments.md, K13): splitting k-step j + 1 beside the MFMAs of k-step j slot by slot as
     // k12 does -- first with units of 7 VALU instructions in every second MFMA gap (the loop kept its 0.73 us per k-step and the second
     // term buffer cost the second wavefront per SIMD that the large maps need: 1.02 ms per image against 0.975), then evenly (one part
@@ -404,36 +310,15 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
     auto step = [&](auto buf_t, auto t_t, int b) __attribute__((always_inline)) {       // k-step t of the pair in LDS buffer b
         constexpr int buf = decltype(buf_t)::value;
         constexpr int t = decltype(t_t)::value;
-        c1_u32x4 at[2][2];
-#pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-            const float* row = &lds_a[b][(pb * 32 + i32) * 32];
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(row + 4 * ((4 * t + 2 * h) ^ key));
-            const f32x4 a1 = *reinterpret_cast<const f32x4*>(row + 4 * ((4 * t + 2 * h + 1) ^ key));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float lo = i < 2 ? a0[2 * (i & 1)] : a1[2 * (i & 1)], hi = i < 2 ? a0[2 * (i & 1) + 1] : a1[2 * (i & 1) + 1];
-                const uint32_t t0 = wino_f16_pair_scaled(lo, hi, sx);
-                wino_f16_residual_scaled(t0, lo, hi, sx);
-                at[pb][0][i] = t0;
-                at[pb][1][i] = wino_f16_pair(lo, hi);
-            }
-        }
-#pragma unroll
-        for (int prod = 0; prod < 3; ++prod) {
-            const int sa = prod == 1 ? 1 : 0;
-            const int sb = prod == 0 ? 1 : 0;
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int pb = 0; pb < 2; ++pb)
-                    acc[cb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, wf[buf][cb][sa]), __builtin_bit_cast(wino_f16x8, at[pb][sb]), acc[cb][pb], 0, 0, 0);
-        }
+        sg_kstep<false>(acc, wf[buf], sx, [&](int pb, int i) __attribute__((always_inline)) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&lds_a[b][(pb * 32 + i32) * 32 + 4 * ((4 * t + 2 * h + (i >> 1)) ^ key)]);
+            return f32x2{a[2 * (i & 1)], a[2 * (i & 1) + 1]};
+        });
     };
     // prologue: pair 0 into LDS buffer 0, pair 1 in flight, filter terms of k-steps 0 and 1
     stage_load(0);
-    load_w(c1_ic<0>{}, 0);
-    load_w(c1_ic<1>{}, 1);
+    load_w(sg_ic<0>{}, 0);
+    load_w(sg_ic<1>{}, 1);
     stage_write(0);
     if (npairs > 1) stage_load(1);
     C1_STAMP(1);
@@ -444,20 +329,20 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
         if constexpr (R < 6) {
             const int j = j0 + R;
             if (j < nks) {
-                if (j + 2 < nks) load_w(c1_ic<(R + 2) % 3>{}, j + 2);
+                if (j + 2 < nks) load_w(sg_ic<(R + 2) % 3>{}, j + 2);
                 const int pair = j >> 1;
-                step(c1_ic<R % 3>{}, c1_ic<R & 1>{}, pair & 1);
+                step(sg_ic<R % 3>{}, sg_ic<R & 1>{}, pair & 1);
                 if constexpr ((R & 1) == 1) {
                     if (pair + 1 < npairs) {
                         stage_write((pair + 1) & 1);
                         if (pair + 2 < npairs) stage_load(pair + 2);
                     }
                 }
-                self(self, c1_ic<R + 1>{}, j0);
+                self(self, sg_ic<R + 1>{}, j0);
             }
         }
     };
-    for (int j0 = 0; j0 < nks; j0 += 6) trip(trip, c1_ic<0>{}, j0);
+    for (int j0 = 0; j0 < nks; j0 += 6) trip(trip, sg_ic<0>{}, j0);
     C1_STAMP(2);
 
     if constexpr (WAVES > 1) {
@@ -485,7 +370,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES > 1 ? 1 : 2) k_conv1x1_split
                     for (int r = 0; r < 16; ++r) acc[cb][pb][r] += o[((cb * 2 + pb) * 16 + r) * 64 + lane];
         }
     }
-    c1_epilogue(P, &lds_a[0][0], acc, tp, tc, lane, i32, h, sx);
+    c1_epilogue(P, &lds_a[0][0], acc, tp, tc, lane, sx);
 #ifdef POD_C1_TRACE
     __builtin_amdgcn_s_waitcnt(0);
     C1_STAMP(3);
@@ -503,11 +388,9 @@ __global__ void __launch_bounds__(256) k_conv1x1_reduce(const float* __restrict_
         for (int s = 1; s < n_splits; ++s) v += *reinterpret_cast<const f32x4*>(partials + (int64_t)s * split_stride + 4 * i);
         if (bias) v += *reinterpret_cast<const f32x4*>(bias + (int)((4 * i) % Cout));
         if (residual) v += *reinterpret_cast<const f32x4*>(residual + 4 * i);
-        if (relu) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
+        if (relu) wino_relu4(v);
         *reinterpret_cast<f32x4*>(y + 4 * i) = v;
-        lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        lmax = wino_absmax4(lmax, v);
     }
     if (out_amax) wino_publish_amax_block(out_amax, lmax);
 }
@@ -522,14 +405,10 @@ extern "C" int64_t pod_conv1x1_filter_split_bytes(int32_t Cout, int32_t Cin) {  
 extern "C" int pod_conv1x1_filter_split(const float* weight, void* Ws, int32_t Cout, int32_t Cin, pod_stream_t stream) {
     if (!weight || !Ws || Cout < 32 || (Cout & 31) != 0 || Cin < 16 || (Cin & 15) != 0 || (reinterpret_cast<uintptr_t>(Ws) & 15u) != 0) return POD_E_INVALID;
     const int64_t n = (int64_t)Cout * (Cin / 2);
-    float* amax = reinterpret_cast<float*>(reinterpret_cast<char*>(Ws) + (int64_t)Cout * Cin * 4);
-    if (hipMemsetAsync(amax, 0, 16, (hipStream_t)stream) != hipSuccess) return POD_E_LAUNCH;
-    hipLaunchKernelGGL(pod::k_conv1x1_filter_amax, dim3(256), dim3(256), 0, (hipStream_t)stream, weight, (int64_t)Cout * Cin, amax);
-    POD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pod::k_conv1x1_filter_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax,
-                       Cout, Cin);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::sg_filter_prepare(weight, (int64_t)Cout * Cin, Ws, (int64_t)Cout * Cin * 2, (hipStream_t)stream, [&](const float* amax) {
+        hipLaunchKernelGGL(pod::k_conv1x1_filter_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax,
+                           Cout, Cin);
+    });
 }
 
 extern "C" int pod_conv1x1_split(const float* x, float* y, const void* Ws, const float* bias, const float* residual, int32_t H_out, int32_t W_out, int32_t H_in,
@@ -573,16 +452,14 @@ extern "C" int pod_conv1x1_split(const float* x, float* y, const void* Ws, const
     P.split_stride = n_splits > 1 ? P_out * Cout : 0;
     const int64_t grid = 8LL * ((P.n_pt + 7) / 8) * P.n_ct;
     if (grid > 0x7FFFFFFFLL) return POD_E_INVALID;
-    if (POD_C1_DIRECT)          // (experiment builds: the direct-fragment kernel everywhere, pod_experiments.h)
-        hipLaunchKernelGGL((pod::k_conv1x1_split<2, POD_C1_RING>), dim3((unsigned)grid, (unsigned)n_splits), dim3(64), 0, (hipStream_t)stream, P);
-    else if ((P.ks_per_split & 1) == 0 && waves == 4)
+    if ((P.ks_per_split & 1) == 0 && waves == 4)
         hipLaunchKernelGGL((pod::k_conv1x1_split_lds<2, 4>), dim3((unsigned)grid, (unsigned)n_splits), dim3(256), 0, (hipStream_t)stream, P);
     else if ((P.ks_per_split & 1) == 0 && waves == 2)
         hipLaunchKernelGGL((pod::k_conv1x1_split_lds<2, 2>), dim3((unsigned)grid, (unsigned)n_splits), dim3(128), 0, (hipStream_t)stream, P);
     else if ((P.ks_per_split & 1) == 0)
         hipLaunchKernelGGL((pod::k_conv1x1_split_lds<2, 1>), dim3((unsigned)grid, (unsigned)n_splits), dim3(64), 0, (hipStream_t)stream, P);
     else
-        hipLaunchKernelGGL((pod::k_conv1x1_split<2, POD_C1_RING>), dim3((unsigned)grid, (unsigned)n_splits), dim3(64), 0, (hipStream_t)stream, P);
+        hipLaunchKernelGGL((pod::k_conv1x1_split<2>), dim3((unsigned)grid, (unsigned)n_splits), dim3(64), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     if (n_splits > 1) {
         const int64_t n4 = P_out * Cout / 4;

@@ -10,14 +10,11 @@
 // of 16 -- the 7 x 7 window padded to 8 x 8 with zero weights, ordered so that a lane's 8 k values are 8 CONSECUTIVE input columns of
 // one row (h = the row of the pair): k = ((c 4 + d2) 2 + h) 8 + dx, dy = 2 d2 + h.  Workgroup = one wavefront = an 8 x 8 tile of output
 // pixels x 64 channels; its 22 x 24 x 3 input patch is loaded once into LDS (zero outside the image) and every MFMA fragment is four
-// ds_read_b64 of it; filter terms straight from L2 (3-deep register ring); epilogue through LDS in whole lines as k13's.
-#include "pod_wino.h"
+// ds_read_b64 of it; filter terms straight from L2 (3-deep register ring); epilogue through LDS in whole lines as k13's.  The tile's
+// parts are pod_split_gemm.h's, shared with k13: this file holds the patch, the 7 x 7 -> 8 x 8 filter gather and where the pixels go.
+#include "pod_split_gemm.h"
 
 namespace pod {
-
-constexpr int ST_KS_U16 = 2 * 2 * 256, ST_TOP = 14;     // u16 values of one (32-channel block, k-step); scaled abs-max of both operands in [2^14, 2^15)
-typedef uint32_t st_u32x4 __attribute__((ext_vector_type(4)));
-typedef float st_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ST_KS = 12;                 // k-steps
 constexpr int ST_PR = 22, ST_PC = 24;     // patch rows (2 * 7 + 7 + 1), columns (2 * 7 + 8, padded to 24)
@@ -35,32 +32,16 @@ struct StemParams {
     int32_t H, W, Ho, Wo, tiles_x, relu;
 };
 
-// weight (64, 3, 7, 7) fp32 -> Ws: the (64 x 192) GEMM matrix in the k order above, two nearest-even f16 terms per scaled value
-__global__ void __launch_bounds__(256) k_stem_filter_amax(const float* __restrict__ w, float* __restrict__ amax) {
-    float m = 0.0f;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 64 * 3 * 49; i += gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    wino_publish_amax1(amax, m);
-}
+// weight (64, 3, 7, 7) fp32 -> Ws: the (64 x 192) GEMM matrix in the k order above, one thread per (cout, pair of k)
 __global__ void __launch_bounds__(256) k_stem_filter_split(const float* __restrict__ w, uint16_t* __restrict__ Ws, const float* __restrict__ amax) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;          // one thread per (cout, pair of k)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 64 * 96) return;
     const int co = t / 96, k = 2 * (t % 96);
     const int ks = k >> 4, h = (k >> 3) & 1, dx = k & 7, c = ks >> 2, dy = 2 * (ks & 3) + h;
     const float lo = (dy < 7 && dx < 7) ? w[((co * 3 + c) * 7 + dy) * 7 + dx] : 0.f;
     const float hi = (dy < 7 && dx + 1 < 7) ? w[((co * 3 + c) * 7 + dy) * 7 + dx + 1] : 0.f;
-    uint32_t terms[2];
-    wino_f16_split2(lo, hi, wino_pow2_scale(*amax, ST_TOP), terms);
-    const int cb = co >> 5, i32 = co & 31;
-#pragma unroll
-    for (int term = 0; term < 2; ++term) {
-        uint16_t* d = Ws + ((((int64_t)cb * ST_KS + ks) * 2 + term) * 2 + h) * 256 + i32 * 8 + dx;
-        d[0] = (uint16_t)(terms[term] & 0xFFFFu);
-        d[1] = (uint16_t)(terms[term] >> 16);
-    }
+    sg_store_filter_terms(Ws, ST_KS, co, k, lo, hi, amax);
 }
-
-template <int I>
-using st_ic = std::integral_constant<int, I>;
 
 __global__ void __launch_bounds__(64, 2) k_stem7x7_split(const StemParams P) {
     __shared__ __attribute__((aligned(16))) float lds[64 * 64];                 // patch (3 x 22 x 24 floats), then the output tile (64 pixels x 64 channels)
@@ -86,7 +67,7 @@ __global__ void __launch_bounds__(64, 2) k_stem7x7_split(const StemParams P) {
         }
     }
     const uint16_t* __restrict__ const wa = P.Ws + (h * 32 + i32) * 8;          // + cb * 12 * 1024 + ks * 1024 + term * 512
-    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wino_pow2_scale(wino_read_amax(P.in_amax), ST_TOP))));
+    const float sx = sg_activation_scale(P.in_amax);
     // this lane's two pixels (pb = 0, 1): tile pixel q = 32 pb + i32 = (q >> 3, q & 7); patch offset of its window's row h, column 0
     int base[2];
 #pragma unroll
@@ -101,80 +82,32 @@ __global__ void __launch_bounds__(64, 2) k_stem7x7_split(const StemParams P) {
         for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[cb][pb][r] = 0.f;
-    st_u32x4 wf[3][2][2];
-    auto load_w = [&](auto buf_t, int ks) __attribute__((always_inline)) {
-        constexpr int buf = decltype(buf_t)::value;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) wf[buf][cb][t] = *reinterpret_cast<const st_u32x4*>(wa + (cb * ST_KS + ks) * ST_KS_U16 + t * 512);
-    };
+    sg_u32x4 wf[SG_RING][2][2];
+    auto load_w = [&](auto buf_t, int ks) __attribute__((always_inline)) { SG_LOAD_FILTER(wf[decltype(buf_t)::value], 2, wa, (int64_t)ST_KS * SG_KS_U16, ks); };
     auto step = [&](auto ks_t) __attribute__((always_inline)) {
-        constexpr int ks = decltype(ks_t)::value, buf = ks % 3, c = ks >> 2, d2 = ks & 3;
-        st_u32x4 at[2][2];
-#pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-            const float* row = lds + c * ST_PR * ST_PC + 2 * d2 * ST_PC + base[pb];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const st_f32x2 v = *reinterpret_cast<const st_f32x2*>(row + 2 * i);
-                float lo = v.x, hi = v.y;
-                const uint32_t t0 = wino_f16_pair_scaled(lo, hi, sx);
-                wino_f16_residual_scaled(t0, lo, hi, sx);
-                at[pb][0][i] = t0;
-                at[pb][1][i] = wino_f16_pair(lo, hi);
-            }
-        }
-#pragma unroll
-        for (int prod = 0; prod < 3; ++prod) {
-            const int sa = prod == 1 ? 1 : 0;
-            const int sb = prod == 0 ? 1 : 0;
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int pb = 0; pb < 2; ++pb)
-                    acc[cb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, wf[buf][cb][sa]), __builtin_bit_cast(wino_f16x8, at[pb][sb]), acc[cb][pb], 0, 0, 0);
-        }
+        constexpr int ks = decltype(ks_t)::value, c = ks >> 2, d2 = ks & 3;
+        sg_kstep<false>(acc, wf[ks % SG_RING], sx, [&](int pb, int i) __attribute__((always_inline)) {
+            return *reinterpret_cast<const f32x2*>(lds + c * ST_PR * ST_PC + 2 * d2 * ST_PC + base[pb] + 2 * i);
+        });
     };
-    load_w(st_ic<0>{}, 0);
-    load_w(st_ic<1>{}, 1);
+    load_w(sg_ic<0>{}, 0);
+    load_w(sg_ic<1>{}, 1);
     __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the patch is written (one wavefront: no barrier)
     wino_static_for([&](auto KS) __attribute__((always_inline)) {
         constexpr int ks = decltype(KS)::value;
-        if constexpr (ks + 2 < ST_KS) load_w(st_ic<(ks + 2) % 3>{}, ks + 2);
+        if constexpr (ks + 2 < ST_KS) load_w(sg_ic<(ks + 2) % 3>{}, ks + 2);
         step(KS);
     }, std::make_integer_sequence<int, ST_KS>{});
 
-    // ---- epilogue in whole lines through LDS (k13's): [pixel 64][chunk position 16][16 B], position = chunk ^ (pixel & 15)
-    const int oc = lane & 15, op = lane >> 4;
+    // ---- epilogue in whole lines through LDS: pixel 4 j + op of the 8 x 8 tile
     f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int oc = lane & 15;                           // the lane finishes channels 4 oc .. 4 oc + 3
     if (P.bias) b4 = *reinterpret_cast<const f32x4*>(P.bias + 4 * oc);
-    const float inv1 = wino_pow2_inverse(sx) * wino_pow2_inverse(wino_pow2_scale(*reinterpret_cast<const float*>(P.Ws + 64 * 192 * 2), ST_TOP));
-    const f32x4 inv = f32x4{inv1, inv1, inv1, inv1};
-    float lmax = 0.0f;
-#pragma unroll
-    for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int pix = 32 * pb + i32, c = 8 * cb + 2 * q + h;
-                *reinterpret_cast<f32x4*>(lds + pix * 64 + 4 * (c ^ (i32 & 15))) =
-                    f32x4{acc[cb][pb][4 * q], acc[cb][pb][4 * q + 1], acc[cb][pb][4 * q + 2], acc[cb][pb][4 * q + 3]};
-            }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int pix = 4 * j + op, oy = oy0 + (pix >> 3), ox = ox0 + (pix & 7);
-        f32x4 v = __builtin_elementwise_fma(*reinterpret_cast<const f32x4*>(lds + pix * 64 + 4 * (oc ^ (pix & 15))), inv, b4);
-        if (P.relu) {
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
-        if (oy < P.Ho && ox < P.Wo) {
-            *reinterpret_cast<f32x4*>(P.y + ((int64_t)oy * P.Wo + ox) * 64 + 4 * oc) = v;
-            lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-        }
-    }
-    if (P.out_amax) wino_publish_amax(P.out_amax, lmax);
+    sg_line_epilogue(lds, acc, lane, sg_inverse_scale(sx, P.Ws, 64 * 192 * 2), b4, nullptr, P.relu != 0, P.out_amax, [&](int, int pix, float*& dst) __attribute__((always_inline)) {
+        const int oy = oy0 + (pix >> 3), ox = ox0 + (pix & 7);
+        dst = P.y + ((int64_t)oy * P.Wo + ox) * 64 + 4 * oc;
+        return oy < P.Ho && ox < P.Wo;
+    });
 }
 
 // max_pool2d(kernel 3, stride 2, padding 1) of a channels-last map: 16 B (4 channels) per lane, the window's taps that lie inside the map
@@ -217,9 +150,7 @@ __global__ void __launch_bounds__(256) k_im2col3x3s2_cl(const float* __restrict_
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
         if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) {
             v = *reinterpret_cast<const f32x4*>(x + (((int64_t)iy * Wi + ix) * C4 + c4) * 4);
-            if (relu) {
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            }
+            if (relu) wino_relu4(v);
         }
         *reinterpret_cast<f32x4*>(y + i * 4) = v;
     }
@@ -229,13 +160,9 @@ __global__ void __launch_bounds__(256) k_im2col3x3s2_cl(const float* __restrict_
 
 extern "C" int pod_stem7x7_filter_split(const float* weight, void* Ws, pod_stream_t stream) {
     if (!weight || !Ws || (reinterpret_cast<uintptr_t>(Ws) & 15u) != 0) return POD_E_INVALID;
-    float* amax = reinterpret_cast<float*>(reinterpret_cast<char*>(Ws) + 64 * 192 * 4);        // the 16-byte trailer behind the 2 x 64 x 192 f16 terms
-    if (hipMemsetAsync(amax, 0, 16, (hipStream_t)stream) != hipSuccess) return POD_E_LAUNCH;
-    hipLaunchKernelGGL(pod::k_stem_filter_amax, dim3(8), dim3(256), 0, (hipStream_t)stream, weight, amax);
-    POD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pod::k_stem_filter_split, dim3((64 * 96 + 255) / 256), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::sg_filter_prepare(weight, 64 * 3 * 49, Ws, 2 * 64 * 192, (hipStream_t)stream, [&](const float* amax) {      // (the trailer: behind the 2 x 64 x 192 f16 terms)
+        hipLaunchKernelGGL(pod::k_stem_filter_split, dim3((64 * 96 + 255) / 256), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax);
+    });
 }
 
 extern "C" int pod_stem7x7_split(const void* x, int32_t x_is_u8, int32_t H_img, int32_t W_img, const float* mean, const float* stddev, float* y, const void* Ws,

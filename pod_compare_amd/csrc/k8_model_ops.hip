@@ -5,7 +5,7 @@
 // per image in MC-dropout mode (PR:103-108).  torch runs it as two kernels (clamp: read+write, fused_dropout:
 // read+write+mask); this is one pass, 16 B per lane, 16 Philox bits per element (pod_device.h: dropout_words; keep iff
 // uniform >= p, scaled by 1/(1-p), torch.nn.functional.dropout's definition).  HBM-bound: 8 bytes per element.
-#include "pod_wino.h"
+#include "pod_split_gemm.h"
 
 namespace pod {
 
@@ -199,10 +199,10 @@ __global__ void __launch_bounds__(256) k_wino_reduce(const float* __restrict__ p
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int r = (tid >> 4) + 16 * it, c4 = (tid & 15) * 4;
-        float4 v = float4{0.f, 0.f, 0.f, 0.f};
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
         if (hw0 + r < HW && c0 + c4 < Kpad) {
             const float* src = partials + (hw0 + r) * Kpad + c0 + c4;
-            v = *reinterpret_cast<const float4*>(src);
+            v = *reinterpret_cast<const f32x4*>(src);
             for (int s = 1; s < n_splits; ++s) {
                 const float4 w = *reinterpret_cast<const float4*>(src + (int64_t)s * split_stride);
                 v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
@@ -211,12 +211,10 @@ __global__ void __launch_bounds__(256) k_wino_reduce(const float* __restrict__ p
                 const float4 b = *reinterpret_cast<const float4*>(bias + c0 + c4);
                 v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
             }
-            if (relu) {
-                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            }
+            if (relu) wino_relu4(v);
         }
         tile[r][c4 + 0] = v.x; tile[r][c4 + 1] = v.y; tile[r][c4 + 2] = v.z; tile[r][c4 + 3] = v.w;
-        lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));     // (padded channels: 0 + 0)
+        lmax = wino_absmax4(lmax, v);     // (padded channels: 0 + 0)
     }
     if (out_amax) wino_publish_amax_block(out_amax, lmax);
     __syncthreads();

@@ -2,20 +2,13 @@
 // (production: every fp32 product formed on the f16 matrix cores from the two-term f16 split of the power-of-two-scaled operands) are
 // the same convolution around different inner products.  Here: the parameters and their host-side fill, the LDS geometry, the workgroup
 // schedule, the block record and the canvas, the pixel table and the patch fills, the output staging, the dropout mask, the two store
-// passes, the f16 split and the abs-max records (k13 / k14 use those too), wait immediates and the diagnostics hooks.  A kernel body
+// passes, wait immediates and the diagnostics hooks (the f16 split and the abs-max records: pod_split_gemm.h).  A kernel body
 // reads: schedule -> shared prologue -> its OWN filter loads, K loop and transforms -> wino_output_stage -> wino_store_*.
 #pragma once
-#include <type_traits>
-#include <utility>
-
-#include "pod_device.h"
 #include "pod_experiments.h"
+#include "pod_split_gemm.h"
 
 namespace pod {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t STREAM_DROPOUT_CONV = 0x64726f70u;   // = STREAM_DROPOUT of k8_model_ops.hip: same mask as pod_bias_act
 
@@ -161,101 +154,6 @@ template <typename... T>
 __device__ __forceinline__ void wino_pin(T&... v) {
     (wino_pin_one(v), ...);
 }
-
-// ---- an fp32 value as the sum of two FP16 values (round 5: k12 / k13 / k14; pod_debug_f16_split2 exposes the same code to the tests)
-// The f16 matrix cores run at the bf16 rate, and two f16 terms carry 11 + 1 (the sign of the residual) + 11 = 23 of an fp32's 24
-// significand bits: x s = x0 + x1 + e, |e| <= 2^-23 |x s| in the worst case (exact whenever the residual has <= 11 significant bits), where
-// x0 = f16(x s) (round to nearest even), r = x s - x0 EXACTLY (one fma), x1 = f16(r).  Three partial products (x0 u1, x1 u0, x0 u0) then form
-// an fp32 product where the 3-way bf16 split needs six -- and with half as many roundings in the fp32 accumulation chain the result is
-// CLOSER to the fp64 value than both the bf16 x 6 form and the fp32 MFMA (measured on the matrix cores: tools/f16_split_numerics.hip,
-// profiles/r05_f16_split_numerics.txt).  What f16 lacks is range (2^-24 .. 65504): every operand tensor is therefore multiplied by a
-// power of two s (exact) chosen from its abs-max, so that the largest scaled value lies in [2^14, 2^15) (filters; static) or below 2^15
-// (activations: abs-max word of the producing launch x the largest gain of the transform); values more than ~2^29 below their tensor's
-// abs-max fall into f16's denormals and keep an ABSOLUTE error of 2^-25 / s -- 2^-40 of the abs-max, against an fp32 rounding's 2^-24 |x|.
-typedef _Float16 wino_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 wino_f16x8 __attribute__((ext_vector_type(8)));
-// 2^(top - floor(log2 amax)): the power of two that puts amax into [2^top, 2^(top+1)).  amax = 0 or absurdly small: the largest scale (the
-// operand is zero / all products underflow anyway); inf / nan: the smallest (the products are inf / nan, as an fp32 product would be).
-__device__ __forceinline__ float wino_pow2_scale(float amax, int top) {
-    const int E = (int)((__float_as_uint(amax) >> 23) & 0xFFu);
-    int b = 254 + top - E;
-    b = b < 1 ? 1 : b > 254 ? 254 : b;
-    return __uint_as_float((uint32_t)b << 23);
-}
-__device__ __forceinline__ float wino_pow2_inverse(float s) {        // 1 / s for a power of two s = 2^k, |k| <= 126: exact
-    return __uint_as_float((254u << 23) - __float_as_uint(s));
-}
-// (lo s, hi s) -> the f16 pair nearest to them (v_fma_mixlo_f16 / v_fma_mixhi_f16: the scaling rides on the conversion)
-__device__ __forceinline__ uint32_t wino_f16_pair_scaled(float lo, float hi, float s) {
-    uint32_t w;
-    asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\tv_fma_mixhi_f16 %0, %2, %3, 0" : "=&v"(w) : "v"(lo), "v"(hi), "s"(s));
-    return w;
-}
-__device__ __forceinline__ uint32_t wino_f16_pair(float lo, float hi) {              // v_cvt_pk_f16_f32: nearest even, lo in bits 15:0
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, wino_f16x2));
-}
-// (lo, hi) <- (lo s, hi s) - the f16 pair w, exactly: one v_fma_mix_f32 per value (f32 x f32 - f16, a single rounding of a result that is
-// representable: |x s - x0| <= 2^-11 |x s| and both are multiples of the last place of x s)
-__device__ __forceinline__ void wino_f16_residual_scaled(uint32_t w, float& lo, float& hi, float s) {
-    asm("v_fma_mix_f32 %0, %0, %1, -%2 op_sel_hi:[0,0,1]" : "+v"(lo) : "s"(s), "v"(w));
-    asm("v_fma_mix_f32 %0, %0, %1, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(hi) : "s"(s), "v"(w));
-}
-__device__ __forceinline__ void wino_f16_split2(float lo, float hi, float s, uint32_t (&w)[2]) {
-    w[0] = wino_f16_pair_scaled(lo, hi, s);
-    wino_f16_residual_scaled(w[0], lo, hi, s);
-    w[1] = wino_f16_pair(lo, hi);
-}
-// ---- operand abs-max RECORDS (include/pod_mi355x.h).  The abs-max of a tensor lives in POD_AMAX_SLOTS words POD_AMAX_STRIDE floats apart
-// (one 128-byte line each); a producer max'es into slot (workgroup + wavefront) mod 16, a consumer takes the largest of the 16.  One word
-// would do for the arithmetic -- but thousands of same-address atomics serialise in the L2 at ~10 ns each, and the wavefronts of a
-// streaming launch all finish together (measured with one word: pod_absmax of 22 MB 109 us, a 5-us reduce launch 47 us).
-// (POD_AMAX_SLOTS = 16, POD_AMAX_STRIDE = 32, POD_AMAX_FLOATS = 512: include/pod_mi355x.h)
-// floats >= 0 order like their bit patterns: an integer atomic max.  One atomic per wavefront at most, skipped when the slot already holds more.
-__device__ __forceinline__ void wino_publish_amax1(float* word, float lmax) {      // one wavefront's maximum into ONE word (a filter's trailer)
-#pragma unroll
-    for (int o = 32; o; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
-    if ((threadIdx.x & 63) == 0 && lmax > 0.0f) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(word);
-        const uint32_t bits = __float_as_uint(lmax);
-        if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bits) atomicMax(w, bits);
-    }
-}
-__device__ __forceinline__ void wino_publish_amax(float* rec, float lmax) {        // ... into its slot of a record
-    const unsigned wg = blockIdx.x + blockIdx.y * gridDim.x;
-    wino_publish_amax1(rec + ((wg * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (POD_AMAX_SLOTS - 1)) * POD_AMAX_STRIDE, lmax);
-}
-// the same for a whole workgroup (every thread calls it; <= 16 wavefronts): ONE atomic per workgroup
-__device__ __forceinline__ void wino_publish_amax_block(float* rec, float lmax) {
-    __shared__ float wave_max[16];
-#pragma unroll
-    for (int o = 32; o; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o));
-    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = lmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (unsigned w = 1; w < (blockDim.x >> 6); ++w) lmax = fmaxf(lmax, wave_max[w]);
-        if (lmax > 0.0f) {
-            uint32_t* word = reinterpret_cast<uint32_t*>(rec + ((blockIdx.x + blockIdx.y * gridDim.x) & (POD_AMAX_SLOTS - 1)) * POD_AMAX_STRIDE);
-            const uint32_t bits = __float_as_uint(lmax);
-            if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bits) atomicMax(word, bits);
-        }
-    }
-}
-__device__ __forceinline__ float wino_load_amax(const float* rec) {                // this lane's slot of the record (ask early, reduce late)
-    const int lane = threadIdx.x & 63;
-    return lane < POD_AMAX_SLOTS ? rec[lane * POD_AMAX_STRIDE] : 0.0f;
-}
-__device__ __forceinline__ float wino_reduce_amax(float v) {                       // the record's value, wave-uniform (a scalar register)
-#pragma unroll
-    for (int o = POD_AMAX_SLOTS / 2; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ float wino_read_amax(const float* rec) { return wino_reduce_amax(wino_load_amax(rec)); }
-
-template <typename F, int... Js>
-__device__ __forceinline__ void wino_static_for(F&& f, std::integer_sequence<int, Js...>) {
-    (f(std::integral_constant<int, Js>{}), ...);
-}
-
 
 // ---- the filter transform U = G4 g G6t of one (k, c) pair (4 x 6 positions: F(2,3) down the rows, F(4,3) along the columns),
 //   G4 = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]],  G6 = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],[1/24,1/12,1/6],[1/24,-1/12,1/6],[0,0,1]];
@@ -448,9 +346,6 @@ struct WinoStore {
     uint64_t offset;          // Philox counter of the set's first 8 floats
     int replicas, k_planes;
 };
-__device__ __forceinline__ void wino_relu4(f32x4& v) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-}
 // Dropout of the 8 consecutive floats at e (a multiple of 8): ONE Philox call, 16 mask bits per element -- pod_bias_act's mask with
 // counter word 0, pod_expand_dropout's (the replicas) with word 2.
 __device__ __forceinline__ void wino_dropout8(f32x4& v0, f32x4& v1, int64_t e, uint64_t offset, uint32_t word, uint64_t key, uint32_t thresh, float scale) {
@@ -498,7 +393,7 @@ __device__ __forceinline__ float wino_store_planes(const WinoParams& P, const Wi
         f32x4 v = __builtin_elementwise_fma(f32x4{y[0], y[1], y[2], y[3]}, inv, f32x4{bias, bias, bias, bias});
         if (P.relu) wino_relu4(v);
         if (S.out_amax)
-            lmax = fmaxf(fmaxf(lmax, px0[0] >= 0 ? fabsf(v.x) : 0.f), fmaxf(fmaxf(px0[1] >= 0 ? fabsf(v.y) : 0.f, px0[2] >= 0 ? fabsf(v.z) : 0.f), px0[3] >= 0 ? fabsf(v.w) : 0.f));
+            lmax = wino_absmax4(lmax, f32x4{px0[0] >= 0 ? v.x : 0.f, px0[1] >= 0 ? v.y : 0.f, px0[2] >= 0 ? v.z : 0.f, px0[3] >= 0 ? v.w : 0.f});
         float* plane = S.out + (int64_t)kg * B.HWi;
         if (vec) {
             *reinterpret_cast<f32x4*>(plane + px0[0]) = v;

@@ -125,7 +125,7 @@ def _split2(x, scale):
 
 def test_two_f16_terms_carry_the_scaled_fp32_value_to_2_pow_minus_23():
     """The arithmetic contract of the round-5 split kernels, first half: for the values the kernels' own split code produces
-    (pod_debug_f16_split2 runs pod_wino.h: wino_f16_split2, the functions the K loops call)
+    (pod_debug_f16_split2 runs pod_split_gemm.h: wino_f16_split2, the functions the K loops call)
         x s = x0 + x1 + e,   |e| <= 2^-23 |x s|   (and e = 0 whenever the residual fits 11 bits),
     x0 the nearest-even f16 of x s, x1 the nearest-even f16 of the EXACT residual -- over every binade the scale can put an operand in
     (the launch scales its operand tensor so that |x s| < 2^15), values with long carry chains and ties, both signs.  Below 2^-14 (f16's
