@@ -645,6 +645,33 @@ typedef struct PodVisFrame {
 int pod_vis_layout(const PodVisList* lists, int32_t n_lists, pod_stream_t stream);
 int pod_vis_render(const PodVisFrame* frames, int32_t n_frames, pod_stream_t stream);
 
+/* ---- K20  the loader's resize (uint8, PIL-exact) ------------------------------------------------
+ * Replaces: what the reference's test loader does to a decoded frame on a host worker (AN:83-84, build_detection_test_loader ->
+ * DatasetMapper(is_train=False): ResizeShortestEdge applied by ResizeTransform with PIL's Image.resize(BILINEAR) on the uint8 HWC array,
+ * the RGB -> BGR flip of cfg.INPUT.FORMAT and the HWC -> CHW transpose), i.e. apply_net.CocoImages.__getitem__ after the decode.
+ *
+ * The arithmetic is Pillow's 8-bit separable resample: a horizontal pass into a uint8 intermediate, then a vertical pass; a pass is
+ * skipped when its axis keeps its size.  Per axis (in -> out pixels), in fp64: scale = in / out, fs = max(scale, 1), support = fs,
+ * ksize = (int)ceil(support) * 2 + 1; for output index i: center = (i + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ * count = min((int)(center + support + 0.5), in) - xmin, weights w_x = max(1 - |(x + xmin - center + 0.5) / fs|, 0) normalised by their sum,
+ * coefficient (int)(w 2^22 + 0.5).  A pixel of a pass is clip8((2^21 + sum pixel * coefficient) >> 22), summed in int32.  Integer
+ * arithmetic on the device: the bytes are Pillow's.
+ *
+ * pod_resize_taps   (host only): ksize of one axis, or -1 when a size is < 1 or > POD_RESIZE_MAX_SIDE.
+ * pod_resize_coeffs (host only): fills HOST arrays bounds[out][2] = (xmin, count) and coeffs[out][ksize] (zero beyond count).
+ * pod_resize_frame_u8: one launch, one thread per output position.  src dev uint8 (in_h, in_w, 3) with rows `row_stride` bytes apart
+ *   (>= 3 in_w); dst dev uint8 planar (3, out_h, out_w); flip_channels != 0: plane c receives source channel 2 - c (RGB -> BGR).
+ *   xbounds / xcoeffs (dev, as pod_resize_coeffs(in_w, out_w) fills them, xk = its ksize) and ybounds / ycoeffs / yk for the rows.  Both
+ *   tables of an axis NULL (and its k 0): the axis keeps its size and its pass is skipped; a table for an axis of equal size gives the
+ *   same bytes (its coefficients are the identity).  A table entry that points outside the source is clamped to it, never followed.
+ * Three new symbols under POD_ABI_VERSION 18: no entry or structure that existed changed, so the number stands. */
+#define POD_RESIZE_MAX_SIDE 32768
+int pod_resize_taps(int32_t in_size, int32_t out_size);
+int pod_resize_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs);
+int pod_resize_frame_u8(const uint8_t* src, int32_t in_h, int32_t in_w, int64_t row_stride, const int32_t* xbounds, const int32_t* xcoeffs,
+                        int32_t xk, const int32_t* ybounds, const int32_t* ycoeffs, int32_t yk, uint8_t* dst, int32_t out_h, int32_t out_w,
+                        int32_t flip_channels, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -126,13 +126,15 @@ class CocoImages:
     the file read with PIL as RGB and flipped to BGR (cfg.INPUT.FORMAT), ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) applied
     with PIL's bilinear filter on the uint8 HWC array (detectron2's ResizeTransform does exactly that for uint8 images), then a
     (3, H, W) uint8 tensor; 'height' / 'width' are the ORIGINAL size from the json (the output resolution, PI:106-107) and
-    'image_id' the dataset's id."""
+    'image_id' the dataset's id.  device_resize: the entry carries 'frame', the decoded RGB (h, w, 3) uint8 tensor, instead of 'image';
+    resize, flip and transpose are then left to `resize.resize_frame_u8` on the device, which gives the same bytes."""
 
-    def __init__(self, json_path: str, image_root: str, min_size: int = 800, max_size: int = 1333):
+    def __init__(self, json_path: str, image_root: str, min_size: int = 800, max_size: int = 1333, device_resize: bool = False):
         with open(json_path, "r") as f:
             data = json.load(f)
         self.images = list(data["images"])
         self.root, self.min_size, self.max_size = image_root, int(min_size), int(max_size)
+        self.device_resize = bool(device_resize)
 
     def __len__(self) -> int:
         return len(self.images)
@@ -148,6 +150,9 @@ class CocoImages:
         with Image.open(os.path.join(self.root, rec["file_name"])) as im:
             im = im.convert("RGB")
             h, w = im.height, im.width
+            if self.device_resize:
+                return {"frame": torch.as_tensor(np.array(im)), "height": int(rec.get("height", h)), "width": int(rec.get("width", w)),
+                        "image_id": rec["id"], "file_name": rec["file_name"]}
             nh, nw = anchors.resize_shortest_edge(h, w, self.min_size, self.max_size)
             if (nh, nw) != (h, w):
                 im = im.resize((nw, nh), Image.BILINEAR)
@@ -172,7 +177,8 @@ class Prefetched:
     def _load(self, i: int) -> dict:
         d = self.dataset[i]
         if self.pin:
-            d["image"] = d["image"].pin_memory()
+            key = "image" if "image" in d else "frame"
+            d[key] = d[key].pin_memory()
         return d
 
     def __len__(self) -> int:
@@ -354,6 +360,10 @@ def main(argv=None):
     ap.add_argument("--loader-workers", type=int, default=-1,
                     help="host threads that read / decode / resize the files of --coco-json ahead of the GPU (the reference's DATALOADER.NUM_WORKERS); "
                          "-1 = the config's value, 0 = in the main loop")
+    ap.add_argument("--resize-on-gpu", action="store_true",
+                    help="--coco-json: the loader threads only decode; ResizeShortestEdge (PIL's uint8 bilinear filter), the RGB -> BGR flip and the "
+                         "HWC -> CHW transpose run on the GPU in one launch on the image's stream (K20).  Bit-identical to the host path: the same "
+                         "network input, the same detections.  Off by default")
     ap.add_argument("--flush-every", type=int, default=64,
                     help="images per rank between two gathers of the device-resident records (SURVEY 8e: ~0.74 MB per rank and flush)")
     ap.add_argument("--ensemble-per-gpu", action="store_true",
@@ -424,8 +434,9 @@ def main(argv=None):
         cfg.MODEL.WEIGHTS, cfg.OUTPUT_DIR = "", ""
     cfg.MODEL.DEVICE = "cuda:%d" % local_rank
     K = cfg.MODEL.RETINANET.NUM_CLASSES
-    from . import modeling
-    dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST) if args.coco_json else None
+    from . import modeling, resize
+    dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST,
+                         device_resize=args.resize_on_gpu) if args.coco_json else None
     if dataset is not None:
         if args.ensemble_per_gpu:
             raise SystemExit("--ensemble-per-gpu runs on the synthetic frames only")
@@ -493,7 +504,11 @@ def main(argv=None):
                         _, d = next(loaded)                             # resized on the host exactly as detectron2's mapper does, a few entries ahead
                     with torch.cuda.stream(streams[j % len(streams)]):
                         if dataset is not None:
-                            input_im = [{"image": d["image"].to(dev, non_blocking=True), "height": d["height"], "width": d["width"],
+                            if args.resize_on_gpu:      # the decoded frame goes up; the host path's bytes come out (K20), outside any captured graph
+                                image = resize.resize_frame_u8(d["frame"].to(dev, non_blocking=True), cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+                            else:
+                                image = d["image"].to(dev, non_blocking=True)
+                            input_im = [{"image": image, "height": d["height"], "width": d["width"],
                                          "image_id": i}]                # position in the list: the dataset's id is restored below
                         else:
                             frame = synthetic.synthetic_frame(i, device=dev)
@@ -538,7 +553,7 @@ def main(argv=None):
                 steady = "; %.1f images/s after the first flush" % ((flushed[-1][1] - flushed[0][1]) / (flushed[-1][0] - flushed[0][0]))
             print("inference loop: %d images on %d rank(s) in %.2f s = %.1f images/s%s (%d stream(s) per GPU%s)" % (
                 len(ids), world, t_loop, len(ids) / t_loop, steady, n_streams,
-                ", %d loader thread(s)" % workers if dataset is not None else ", synthetic frames made on the device"))
+                ", %d loader thread(s)%s" % (workers, ", resized on the GPU" if args.resize_on_gpu else "") if dataset is not None else ", synthetic frames made on the device"))
     res = None
     if rank == 0 and args.eval:
         res = evaluate_results(args.output, args.coco_json, args.train_dataset, args.test_dataset, min_allowed_score=args.min_allowed_score,

@@ -29,6 +29,7 @@ POD_VIS_MAX_INSTANCES, POD_VIS_INST_WORDS, POD_VIS_PRIM_WORDS, POD_VIS_LAUNCH_FR
 POD_VIS_COLOUR_ENTROPY, POD_VIS_COLOUR_FIXED, POD_VIS_COLOUR_PALETTE, POD_VIS_COLOUR_ARRAY = 0, 1, 2, 3
 POD_VIS_COV_BY_RANK, POD_VIS_COV_OWN = 0, 1
 POD_VIS_LABEL_BOX, POD_VIS_LABEL_GLYPH = 3, 4
+POD_RESIZE_MAX_SIDE = 32768
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
@@ -38,7 +39,7 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_coco_eval_scratch_bytes", "pod_coco_eval_images", "pod_coco_accumulate_workspace_bytes", "pod_coco_accumulate",
            "pod_calib_keys", "pod_calib_reg_counts", "pod_calib_min_uncertainty_workspace_bytes", "pod_calib_min_uncertainty",
            "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_sort", "pod_calib_marginal_bins", "pod_calib_marginal_error_workspace_bytes",
-           "pod_calib_marginal_error", "pod_vis_layout", "pod_vis_render")
+           "pod_calib_marginal_error", "pod_vis_layout", "pod_vis_render", "pod_resize_taps", "pod_resize_coeffs", "pod_resize_frame_u8")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes")
@@ -207,6 +208,9 @@ def load() -> ctypes.CDLL:
     lib.pod_calib_marginal_error.argtypes = [P, P, P, c_int32, P, c_int32, P, c_int32, P, P, P]
     lib.pod_vis_layout.argtypes = [POINTER(PodVisList), c_int32, P]
     lib.pod_vis_render.argtypes = [POINTER(PodVisFrame), c_int32, P]
+    lib.pod_resize_taps.argtypes = [c_int32, c_int32]
+    lib.pod_resize_coeffs.argtypes = [c_int32, c_int32, P, P]
+    lib.pod_resize_frame_u8.argtypes = [P, c_int32, c_int32, c_int64, P, P, c_int32, P, P, c_int32, P, c_int32, c_int32, c_int32, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int
