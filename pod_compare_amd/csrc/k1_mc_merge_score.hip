@@ -19,7 +19,8 @@
 //   * "box" workgroups: flat element-wise merge of the delta / reg_var planes (pure streaming).
 // ~1.6k workgroups, ~11k waves at BASELINE size (R = 193374, N = 10): every CU holds several
 // waves with >= 16 loads in flight each.  No MFMA: element-wise + reductions.
-#include "pod_device.h"
+// The merge order, the prune bound, the scoring group and the host's layout helpers are shared with K1f: pod_merge_score.h.
+#include "pod_merge_score.h"
 
 namespace pod {
 
@@ -83,56 +84,34 @@ __device__ __forceinline__ float4 div4(float4 a, float d) {
     return float4{__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d)};
 }
 
-// CNT straight-line independent 16-B loads of runs run0..run0+CNT-1 of NT tensors (same index and run
-// stride), then the adds in the reference's order.  No branch between the loads: they are all in flight
-// together (CNT * NT * 16 B per lane), which is what keeps HBM busy with ~28 waves per CU.
-template <bool VEC, int NT, int CNT>
-__device__ __forceinline__ void merge_batch(float4* acc, const float* const* base, int64_t rs, int64_t i, int64_t n, int run0) {
-    float4 v[NT][CNT];
+// The accumulator merge_runs (pod_merge_score.h) walks: NT tensors (same index and run stride) at elements [i, i+4).  add<CNT> is CNT
+// straight-line independent 16-B loads per tensor, then the adds in the reference's order.  No branch between the loads: they are all in
+// flight together (CNT * NT * 16 B per lane), which is what keeps HBM busy with ~28 waves per CU.
+template <bool VEC, int NT>
+struct RunAcc4 {
+    float4* acc;
+    const float* const* base;
+    int64_t rs, i, n;
+    __device__ __forceinline__ void first() { for (int t = 0; t < NT; ++t) acc[t] = ld4<VEC>(base[t], i, n); }
+    __device__ __forceinline__ void twice() { for (int t = 0; t < NT; ++t) acc[t] = add4(acc[t], acc[t]); }
+    template <int CNT>
+    __device__ __forceinline__ void add(int run0) {
+        float4 v[NT][CNT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int j = 0; j < CNT; ++j) v[t][j] = ld4<VEC>(base[t] + (int64_t)(run0 + j) * rs, i, n);
+            for (int j = 0; j < CNT; ++j) v[t][j] = ld4<VEC>(base[t] + (int64_t)(run0 + j) * rs, i, n);
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int j = 0; j < CNT; ++j) acc[t] = add4(acc[t], v[t][j]);
-}
-
-// PI:216-222 merge of the N runs of NT tensors at elements [i, i+4).
-//   quirk: acc = x0; acc += x0; acc += x1 .. x_{N-2}; acc /= N      true mean: acc = x0; acc += x1 .. x_{N-1}; acc /= N
+            for (int j = 0; j < CNT; ++j) acc[t] = add4(acc[t], v[t][j]);
+    }
+    __device__ __forceinline__ void div(float d) { for (int t = 0; t < NT; ++t) acc[t] = div4(acc[t], d); }
+};
 template <bool VEC, int NT, int BATCH>
-__device__ __forceinline__ void merge_runs4(float4* acc, const float* const* base, int64_t rs, int64_t i, int64_t n, int n_runs,
-                                            int quirk) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = ld4<VEC>(base[t], i, n);
-    if (n_runs == 1) return;
-    int r = 1, last = n_runs;          // runs [r, last) are still to be added
-    if (quirk) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = add4(acc[t], acc[t]);
-        last = n_runs - 1;
-    }
-    while (r + BATCH <= last) {
-        merge_batch<VEC, NT, BATCH>(acc, base, rs, i, n, r);
-        r += BATCH;
-    }
-    if (BATCH > 4 && r + 4 <= last) {
-        merge_batch<VEC, NT, 4>(acc, base, rs, i, n, r);
-        r += 4;
-    }
-    if (BATCH > 2 && r + 2 <= last) {
-        merge_batch<VEC, NT, 2>(acc, base, rs, i, n, r);
-        r += 2;
-    }
-    if (r + 1 <= last) {
-        merge_batch<VEC, NT, 1>(acc, base, rs, i, n, r);
-        r += 1;
-    }
-    if (BATCH <= 2 && r < last) merge_batch<VEC, NT, 1>(acc, base, rs, i, n, r);
-    const float fn = (float)n_runs;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = div4(acc[t], fn);
+__device__ __forceinline__ void merge_runs4(float4* acc, const float* const* base, int64_t rs, int64_t i, int64_t n, int n_runs, int quirk) {
+    RunAcc4<VEC, NT> r = {acc, base, rs, i, n};
+    merge_runs<BATCH>(r, n_runs, quirk);
 }
 
 // ---- box role: element-wise merge of delta (role 1) or reg_var (role 2) ---------------------------------
@@ -190,10 +169,7 @@ __global__ void __launch_bounds__(1024) k1_mc_merge_score(const K1Params P) {
     extern __shared__ __attribute__((aligned(16))) float lds_probs[];   // [K][256]
     const int b = blockIdx.x;
     const int L = P.n_levels;
-    // locate role + level (scalar search over <= 24 segment starts)
-    int seg = 0;
-#pragma unroll 1
-    while (seg + 1 < 3 * L && b >= P.seg_begin[seg + 1]) ++seg;
+    const int seg = find_segment(P.seg_begin, 3 * L, b);   // role + level
     const int role = seg / L;
     const int l = seg - role * L;
     const PodLevel& lv = P.lv[l];
@@ -248,13 +224,10 @@ __global__ void __launch_bounds__(1024) k1_mc_merge_score(const K1Params P) {
 }
 
 // ---- K1 prune mode: one flat streaming kernel ------------------------------------------------------------------
-// Native RNG + variance head.  box_muller16() bounds every draw by |eps| < POD_EPS_MAX, so
-//     mean_s sigmoid(logit + eps_s*sigma) <= sigmoid(logit + POD_EPS_MAX*sigma):
-// an (anchor, class) with logit + POD_EPS_MAX*sigma <= logit(score_thresh) can never become a candidate.  The dense
-// pass therefore draws nothing: it merges, stores, and sets one bit per anchor that MAY pass (exact superset);
-// K1b samples those.  With no max-over-classes left there is no LDS, no barrier and no class-per-wave shape: every
-// tensor is walked as a flat array, 256 threads x 16 B = 4 KiB contiguous per run per workgroup (the access
-// pattern of a plain streaming merge), logit and log-variance planes side by side.
+// The dense pass draws nothing (may_pass, pod_merge_score.h): it merges, stores, and sets one bit per anchor that MAY pass; K1b samples
+// those.  With no max-over-classes left there is no LDS, no barrier and no class-per-wave shape: every tensor is walked as a flat
+// array, 256 threads x 16 B = 4 KiB contiguous per run per workgroup (the access pattern of a plain streaming merge), logit and
+// log-variance planes side by side.
 // OR over the 16 lanes of a DPP row (row_ror:8,4,2,1): every lane ends up with the row's OR, no LDS crossbar
 __device__ __forceinline__ uint32_t row_or16(uint32_t v) {
     v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);
@@ -287,7 +260,7 @@ __device__ __forceinline__ void prune_cls(const K1Params& P, const PodLevel& lv,
         unsigned nib = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (fmaf(POD_EPS_MAX, __builtin_amdgcn_exp2f(0.7213475204444817f * vr[j]), lg[j]) > P.skip_logit) nib |= 1u << j;
+            if (may_pass(lg[j], vr[j], true, P.skip_logit)) nib |= 1u << j;
         // one bitmap word per (plane, 64 cells): the classes of an anchor do NOT share a word.  (They did in round 1: with
         // every anchor flagged, 7 classes x 8 words hammered each 64-byte line with 56 same-line atomics, and K1 took 48 us
         // instead of 23 -- the stores, not their being atomic: tools/exp_k1_worst.py.)  K1b ORs the K words of an anchor.
@@ -306,7 +279,7 @@ __device__ __forceinline__ void prune_cls(const K1Params& P, const PodLevel& lv,
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (i + j >= n) break;
-            if (!(fmaf(POD_EPS_MAX, __builtin_amdgcn_exp2f(0.7213475204444817f * vr[j]), lg[j]) > P.skip_logit)) continue;
+            if (!may_pass(lg[j], vr[j], true, P.skip_logit)) continue;
             const int plane = (int)((i + j) / HW);
             const int hw = (int)(i + j - (int64_t)plane * HW);
             atomicOr(reinterpret_cast<unsigned long long*>(bits + plane * P.wpa[l] + (hw >> 6)), 1ull << (hw & 63));
@@ -318,9 +291,7 @@ template <int BATCH>
 __global__ void __launch_bounds__(256) k1_prune_stream(const K1Params P) {
     const int b = blockIdx.x;
     const int L = P.n_levels;
-    int seg = 0;
-#pragma unroll 1
-    while (seg + 1 < 3 * L && b >= P.pseg_begin[seg + 1]) ++seg;
+    const int seg = find_segment(P.pseg_begin, 3 * L, b);
     const int role = seg / L;
     const int l = L - 1 - (seg - role * L);   // last (smallest) level first: its ragged maps take the scalar path, whose
                                               // longer chain of dependent loads then overlaps the bulk instead of trailing it
@@ -342,7 +313,7 @@ __global__ void __launch_bounds__(256) k1_prune_stream(const K1Params P) {
 // logits / log-variances K1 just wrote (or the single run when N == 1).  Persistent grid, static work split
 // (wavefront w owns bitmap words w, w + nwaves, ...: no work-list atomics); a wavefront scores 64/KP flagged
 // anchors at a time (KP = 8 or 16 lanes per anchor, lane = class), reduces max over the class lanes by
-// butterfly and appends the keys of anchors above the threshold with one aggregated atomic.
+// butterfly (score_group, pod_merge_score.h) and appends the keys of anchors above the threshold with one aggregated atomic.
 struct K1bParams {
     PodLevel lv[POD_MAX_LEVELS];
     int32_t word_begin[POD_MAX_LEVELS + 1];   // level l = bitmap words [word_begin[l], word_begin[l+1]), K per (anchor shape, 64 cells)
@@ -367,11 +338,10 @@ __global__ void __launch_bounds__(256) k1b_score_maybe(const K1bParams P) {
     const int sub = lane / KP, k = lane % KP;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int L = P.n_levels, K = P.K, A = P.A;
+    const int L = P.n_levels, K = P.K;
     const int total_units = P.unit_begin[L];
     for (int w = wave; w < total_units; w += nwaves) {
-        int l = 0;
-        while (l + 1 < L && w >= P.unit_begin[l + 1]) ++l;
+        const int l = find_segment(P.unit_begin, L, w);
         const PodLevel& lv = P.lv[l];
         const int wl = w - P.unit_begin[l];
         const int a = wl / P.wpa[l];
@@ -411,26 +381,23 @@ __global__ void __launch_bounds__(256) k1b_score_maybe(const K1bParams P) {
             }
             const bool valid = bit >= 0;
             const int hw = hw_base + bit;
-            float p = 0.0f;
+            float lg = 0.0f, vr = 0.0f;
             if (valid && k < K) {
                 const int64_t e = (int64_t)(a * K + k) * HW + hw;
-                p = class_prob_cell(src[e], srcv[e], true, P.cls_samples, nullptr, HW * A, K, A, l, hw, a, k, P.seed);
+                lg = src[e];
+                vr = srcv[e];
             }
-            float best = p;
-#pragma unroll
-            for (int o = KP >> 1; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
-            if (P.probs_dense && valid && k < K && best > P.score_thresh)      // the gather kernel reuses them (same function, same inputs)
-                P.probs_dense[((int64_t)lv.anchor_base + (int64_t)hw * A + a) * K + k] = p;
-            const bool emit = valid && k == 0 && best > P.score_thresh;
+            uint64_t key;
+            const bool emit = score_group<KP>(P, lg, vr, true, valid, l, hw, a, k, key);
             const unsigned long long em = __ballot(emit);
-            if (emit) park[parked + __popcll(em & ((1ull << lane) - 1ull))] = make_key(best, hw * A + a);
+            if (emit) park[parked + __popcll(em & ((1ull << lane) - 1ull))] = key;
             parked += __popcll(em);
         }
         if (parked > 0) {
             int pos = 0;
             if (lane == 0) pos = atomicAdd(&P.cand_count[l], parked);
             pos = __shfl(pos, 0, 64);
-            if (lane < parked && (int64_t)pos + lane < HW * A) P.cand_keys[(int64_t)lv.anchor_base + pos + lane] = park[lane];   // same wave wrote park[]
+            if (lane < parked && (int64_t)pos + lane < HW * P.A) P.cand_keys[(int64_t)lv.anchor_base + pos + lane] = park[lane];   // same wave wrote park[]
         }
     }
 }
@@ -458,9 +425,7 @@ extern "C" int pod_mc_merge_score(const PodConfig* cfg, const PodLevel* levels, 
             if (levels[l].eps_cls) return POD_E_INVALID;
     }
     const int L = cfg->n_levels, K = cfg->num_classes, A = cfg->num_anchors, N = cfg->n_runs, D = cfg->cov_dims;
-    if (L < 1 || L > POD_MAX_LEVELS || K < 1 || K > POD_MAX_CLASSES || A < 1 || N < 1 || N > POD_MAX_RUNS) return POD_E_INVALID;
-    if (!(D == 0 || D == 4 || D == 10)) return POD_E_INVALID;
-    if (cfg->has_cls_var && (cfg->cls_samples < 1 || cfg->cls_samples > POD_MAX_CLS_SAMPLES)) return POD_E_INVALID;
+    if (!pod_merge_score_cfg_ok(cfg) || !(D == 0 || D == 4 || D == 10)) return POD_E_INVALID;
     pod::K1Params P;
     const int threads = 64 * K;
     for (int l = 0; l < L; ++l) {
@@ -497,22 +462,13 @@ extern "C" int pod_mc_merge_score(const PodConfig* cfg, const PodLevel* levels, 
     P.seg_begin[s] = nb;
     P.n_levels = L; P.n_runs = N; P.A = A; P.K = K; P.D = D;
     P.has_cls_var = cfg->has_cls_var; P.quirk = cfg->merge_quirk; P.cls_samples = cfg->cls_samples;
-    P.score_thresh = cfg->score_thresh; P.seed = cfg->philox_seed;
-    {
-        const double t = (double)cfg->score_thresh;
-        P.skip_logit = (t > 0.0 && t < 1.0) ? (float)(log(t / (1.0 - t)) - 0.02) : -INFINITY;   // margin covers the fast-math error
-    }
+    P.score_thresh = cfg->score_thresh; P.seed = cfg->philox_seed; P.skip_logit = pod_prune_logit(cfg->score_thresh);
     P.mean_cls = mean_cls; P.mean_cls_var = mean_cls_var; P.mean_delta = mean_delta; P.mean_reg_var = mean_reg_var;
     P.cand_keys = cand_keys; P.cand_count = cand_count; P.maybe_bits = maybe_bits;
     if (maybe_bits) {
         // prune mode: flat streaming kernel, 256-thread workgroups
-        int32_t wb = 0, pb = 0, q = 0;
-        for (int l = 0; l < L; ++l) {
-            P.word_begin[l] = wb;
-            P.wpa[l] = (int32_t)(((int64_t)levels[l].H * levels[l].W + 63) / 64);
-            wb += A * K * P.wpa[l];
-        }
-        P.word_begin[L] = wb;
+        int32_t pb = 0, q = 0;
+        pod_bitmap_layout(cfg, levels, P.wpa, P.word_begin);
         for (int role = 0; role <= 2; ++role)
             for (int l = L - 1; l >= 0; --l) {   // segment order inside a role: last level first (see k1_prune_stream)
                 P.pseg_begin[q++] = pb;
@@ -538,10 +494,8 @@ extern "C" int pod_mc_merge_score(const PodConfig* cfg, const PodLevel* levels, 
 
 extern "C" int64_t pod_maybe_words(const PodConfig* cfg, const PodLevel* levels) {
     if (!cfg || !levels || cfg->n_levels < 1 || cfg->n_levels > POD_MAX_LEVELS) return POD_E_INVALID;
-    int64_t w = 0;
-    for (int l = 0; l < cfg->n_levels; ++l)
-        w += (int64_t)cfg->num_anchors * cfg->num_classes * (((int64_t)levels[l].H * levels[l].W + 63) / 64);
-    return w;
+    int32_t wpa[POD_MAX_LEVELS], word_begin[POD_MAX_LEVELS + 1];
+    return pod_bitmap_layout(cfg, levels, wpa, word_begin);
 }
 
 extern "C" int pod_score_maybe(const PodConfig* cfg, const PodLevel* levels, const float* mean_cls, const float* mean_cls_var,
@@ -549,21 +503,17 @@ extern "C" int pod_score_maybe(const PodConfig* cfg, const PodLevel* levels, con
                                pod_stream_t stream) {
     if (!cfg || !levels || !maybe_bits || !cand_keys || !cand_count) return POD_E_INVALID;
     const int L = cfg->n_levels, K = cfg->num_classes;
-    if (L < 1 || L > POD_MAX_LEVELS || K < 1 || K > POD_MAX_CLASSES || !cfg->has_cls_var) return POD_E_INVALID;
+    if (!pod_merge_score_cfg_ok(cfg) || !cfg->has_cls_var) return POD_E_INVALID;
     if (cfg->n_runs > 1 && (!mean_cls || !mean_cls_var)) return POD_E_INVALID;
-    if (cfg->cls_samples < 1 || cfg->cls_samples > POD_MAX_CLS_SAMPLES) return POD_E_INVALID;
     pod::K1bParams P;
-    int32_t wb = 0, ub = 0;
+    pod_bitmap_layout(cfg, levels, P.wpa, P.word_begin);
+    int32_t ub = 0;
     for (int l = 0; l < L; ++l) {
         if (!levels[l].cls || !levels[l].cls_var || levels[l].eps_cls) return POD_E_INVALID;
         P.lv[l] = levels[l];
-        P.wpa[l] = (int32_t)(((int64_t)levels[l].H * levels[l].W + 63) / 64);
-        P.word_begin[l] = wb;
         P.unit_begin[l] = ub;
-        wb += cfg->num_anchors * K * P.wpa[l];
         ub += cfg->num_anchors * P.wpa[l];
     }
-    P.word_begin[L] = wb;
     P.unit_begin[L] = ub;
     P.n_levels = L; P.n_runs = cfg->n_runs; P.A = cfg->num_anchors; P.K = K; P.cls_samples = cfg->cls_samples;
     P.score_thresh = cfg->score_thresh; P.seed = cfg->philox_seed; P.mean_cls = mean_cls; P.mean_cls_var = mean_cls_var;

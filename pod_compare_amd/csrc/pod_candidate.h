@@ -5,7 +5,7 @@
 // One wavefront per candidate in both; the fused kernel hands the merged deltas / log-variances over in registers and
 // the per-run deltas in LDS instead of through the candidate arrays in HBM.
 #pragma once
-#include "pod_device.h"
+#include "pod_merge_score.h"
 
 namespace pod {
 
@@ -17,8 +17,8 @@ struct K2bParams {
     const uint64_t* cat_keys;      // level-concatenated selection written by K2 (row = candidate)
     const int32_t* cat_level;
     const int32_t* n_total;        // number of candidates (written by K2)
-    int32_t* cand_count;           // the per-level counters K1 / K1b appended with: consumed (zeroed) here
-    const float* probs_dense;      // (R, K) class probabilities K1b stored for the anchors it emitted, or null (recompute)
+    int32_t* cand_count;           // the per-level counters K1 / K1b / K1f appended with: consumed (zeroed) here
+    const float* probs_dense;      // (R, K) class probabilities the scoring group (K1b / K1f) stored for the anchors it emitted, or null (recompute)
     int32_t* cand_anchor_idx;
     int32_t* cand_level;
     float* cand_score;
@@ -30,8 +30,9 @@ struct K2bParams {
     float* cand_run_delta;
 };
 
-// Merged value of one element (plane-layout offset `e` inside a run) in the reference order; all N
-// loads of a batch are issued before the first add.  Optionally hands every run's raw value to `sink`.
+// Merged value of one element (plane-layout offset `e` inside a run) in the order of merge_runs (pod_merge_score.h: the one
+// statement of PI:216-222), in a shape of its own: ONE round of up to 16 independent loads, issued before the first add, and every
+// run's raw value handed to `sink`.
 template <class Sink>
 __device__ __forceinline__ float merge_scalar(const float* base, int64_t rs, int64_t e, int n_runs, int quirk, Sink sink) {
     float acc = 0.0f;
@@ -48,9 +49,9 @@ __device__ __forceinline__ float merge_scalar(const float* base, int64_t rs, int
                 sink(run, v[j]);
                 if (run == 0) {
                     x0 = v[j];
-                    acc = (quirk && n_runs > 1) ? x0 + x0 : x0;   // term 0 (+ term 1 = run 0 again, PI:216-219)
+                    acc = (quirk && n_runs > 1) ? x0 + x0 : x0;
                 } else if (!quirk || run < n_runs - 1) {
-                    acc = acc + v[j];                             // quirk: the last run is never added
+                    acc = acc + v[j];
                 }
             }
         }
@@ -93,7 +94,7 @@ __device__ __forceinline__ bool gather_candidate(const K2bParams& P, int dst, in
     const float4 anc = *reinterpret_cast<const float4*>(P.anchors + ((int64_t)lv.anchor_base + r) * 4);
     float merged = 0.0f;
     if (lane < K + nvar && P.probs_dense) {
-        // class channels: only needed to re-derive the probabilities, which K1b already stored for this anchor
+        // class channels: only needed to re-derive the probabilities, which K1b / K1f already stored for this anchor
     } else if (lane < K) {
         merged = merge_scalar(lv.cls, lv.run_stride_cls, (int64_t)(a * K + lane) * HW + hw, N, P.quirk, [](int, float) {});
     } else if (lane < K + nvar) {
@@ -116,7 +117,7 @@ __device__ __forceinline__ bool gather_candidate(const K2bParams& P, int dst, in
     const float lvar = has_var ? __shfl(merged, (lane < K ? lane : 0) + K, 64) : 0.0f;
     float p = -1.0f;
     if (lane < K) {
-        // K1b evaluated exactly this function on exactly these merged values when it emitted the anchor: reuse its result
+        // K1b / K1f evaluated exactly this function on exactly these merged values when it emitted the anchor: reuse its result
         // (bit-identical; saves 3 Philox calls + 10 sigmoids on the critical path of every candidate)
         p = P.probs_dense ? P.probs_dense[((int64_t)lv.anchor_base + r) * K + lane]
                           : class_prob_cell(merged, lvar, has_var, P.cls_samples, lv.eps_cls, HW * A, K, A, l, hw, a, lane, P.seed);

@@ -92,7 +92,7 @@ __device__ __forceinline__ void dropout_words(uint64_t base, uint64_t g, uint32_
 // Native-RNG normals: Box-Muller on two 16-bit uniforms (one 32-bit Philox word per pair of normals,
 // 8 normals per Philox4x32-10 call).  u1 = (a + 0.5) / 2^16 >= 2^-17 bounds the radius, so
 //     |z| <= sqrt(-2 ln 2^-17) = 4.855 < POD_EPS_MAX,
-// which is what lets K1 prune anchors EXACTLY (see k1_mc_merge_score.hip).  Statistical parity only: the
+// which is what lets K1 / K1f prune anchors EXACTLY (pod_merge_score.h: may_pass).  Statistical parity only: the
 // eps-replay mode never comes here.  v_log_f32 is log2; v_sin/v_cos take their argument in revolutions.
 __device__ __forceinline__ void box_muller16(uint32_t w, float& n0, float& n1) {
     const float u1 = ((float)(w & 0xFFFFu) + 0.5f) * 1.52587890625e-05f;   // (0,1)
@@ -129,55 +129,6 @@ __device__ __forceinline__ float sigmoid_ref(float x) { return __fdiv_rn(1.0f, 1
 // native-RNG mode only (no bit-level comparison with the CPU is possible there): v_exp_f32 + v_rcp_f32.
 __device__ __forceinline__ float sigmoid_fast(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
-
-// PI:216-222 merge of N runs, in the reference's association order.
-//   quirk: acc = x0; acc += x0; acc += x1; ... acc += x_{N-2}; acc /= N
-//   true : acc = x0; acc += x1; ... acc += x_{N-1};           acc /= N
-// `term_run(t)` is the run whose value is term t (t = 0..N-1).
-__device__ __forceinline__ int merge_term_run(int t, int quirk) { return (quirk && t > 0) ? t - 1 : t; }
-
-// Class probability of one (anchor, class): PI:289-297.
-//   no variance head : sigmoid(logit)
-//   variance head    : mean_s sigmoid(logit + eps_s * sqrt(exp(var))), s = 0..S-1, summed in order, / S
-//
-// eps source.  Replay (parity mode): tensor (S, R_l, K) in the reference layout, every op the reference's.
-// Native: Philox draws organised per group of 4 consecutive cells (the 4 anchors one K1 lane owns); normal
-// q = j*S + s (j = hw & 3, s = sample) is component q&7 of the call with counter
-// (hw>>2, level<<16 | a<<8 | k, q>>3, STREAM_CLS).  K1, K1b and K2b all come through this one function, so
-// they see bit-identical draws and sums and nothing has to be stored.  Transcendentals use the hardware
-// approximations in native mode (the draws differ from torch's anyway).
-__device__ __forceinline__ float class_prob_cell(float logit, float logvar, bool has_var, int S, const float* replay,
-                                                int64_t level_anchors, int K, int A, int level, int hw, int a, int k, uint64_t seed) {
-    if (!has_var) return sigmoid_ref(logit);
-    float acc = 0.0f;
-    if (replay) {
-        const float sigma = sqrtf(expf(logvar));
-        const float* e = replay + ((int64_t)hw * A + a) * K + k;
-        const int64_t stride_s = level_anchors * K;
-        for (int s = 0; s < S; ++s) {
-            const float x = logit + e[(int64_t)s * stride_s] * sigma;
-            acc = acc + sigmoid_ref(x);
-        }
-        return __fdiv_rn(acc, (float)S);
-    }
-    const float sigma = __builtin_amdgcn_exp2f(0.7213475204444817f * logvar);   // sqrt(exp(v)) = 2^(v / (2 ln 2))
-    const int q0 = (hw & 3) * S, q1 = q0 + S;
-    const uint32_t c0 = (uint32_t)(hw >> 2), c1 = ((uint32_t)level << 16) | ((uint32_t)a << 8) | (uint32_t)k;
-    for (int call = q0 >> 3; call * 8 < q1; ++call) {
-        const u32x4 r = philox4x32_10(u32x4{c0, c1, (uint32_t)call, STREAM_CLS}, (uint32_t)seed, (uint32_t)(seed >> 32));
-        float z[8];
-        box_muller16(r.x, z[0], z[1]);
-        box_muller16(r.y, z[2], z[3]);
-        box_muller16(r.z, z[4], z[5]);
-        box_muller16(r.w, z[6], z[7]);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int q = call * 8 + c;
-            if (q >= q0 && q < q1) acc += sigmoid_fast(fmaf(z[c], sigma, logit));
-        }
-    }
-    return acc * __builtin_amdgcn_rcpf((float)S);
 }
 
 // detectron2 Box2BoxTransform.apply_deltas / IU:510-547 on one box; dw, dh clamped at log(1000/16).

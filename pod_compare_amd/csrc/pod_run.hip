@@ -31,7 +31,7 @@ extern "C" int pod_run_image_part(const PodConfig* cfg, const PodLevel* levels, 
     for (int l = 0; l < cfg->n_levels; ++l)
         if (levels[l].eps_cls) return POD_E_INVALID;   // eps-replay needs the host between launches
     const bool merged = cfg->n_runs > 1;
-    const bool prune = cfg->has_cls_var != 0;           // native draws + variance head: K1 flags, K1b samples
+    const bool prune = cfg->has_cls_var != 0;           // native draws + variance head: K1f flags and samples (pod_merge_score.h: may_pass, score_group)
     const bool has_cov = cfg->cov_dims > 0 || merged;   // PI:381: otherwise the reference carries no covariance
     if (prune && !ws->probs_dense) return POD_E_INVALID;
     if (!ws->cat_keys || !ws->cat_level || !ws->n_total) return POD_E_INVALID;

@@ -140,7 +140,7 @@ class HotPath:
         self.sel_count = i32(self.L)
         self.cat_keys = torch.empty(self.L * params.topk_candidates, dtype=torch.int64, device=dev)   # level-concatenated selection
         self.cat_level = i32(self.L * params.topk_candidates)
-        # class probabilities of the anchors K1b emits, reused by the gather kernel (native draws + variance head)
+        # class probabilities of the anchors K1b / K1f emit, reused by the gather kernel (native draws + variance head)
         self.probs_dense = f32(self.R * K) if has_cls_var else None
         n = self.n_cap
         self.n_total = i32(1)
@@ -189,7 +189,9 @@ class HotPath:
                   "mean_delta": f32(self.R * 4) if merged and self.dense_box_merge else None,
                   "mean_reg_var": f32(self.R * D) if merged and D > 0 and self.dense_box_merge else None, "maybe_bits": None}
             if self.has_cls_var:
-                n_words = sum(self.p.num_anchors * K * ((h * w + 63) // 64) for h, w in self.shapes)   # == pod_maybe_words(): a word per (plane, 64 cells)
+                n_words = int(self.lib.pod_maybe_words(self.cfg, self._geometry_levels()))      # a word per (plane, 64 cells)
+                if n_words < 0:
+                    hip.check(n_words, "pod_maybe_words")
                 pl["maybe_bits"] = torch.zeros(n_words, dtype=torch.int64, device=dev)
             for name, t in pl.items():
                 setattr(self.ws, name, hip.ptr(t))
@@ -225,7 +227,7 @@ class HotPath:
         """Philox key of the next image's in-kernel draws: (seed, draw id).  The reference draws FRESH normals on every
         call (PI:291-294, PI:351-356); with a constant key every image -- and every member of a post-NMS ensemble --
         would see the same eps at the same (level, anchor, class, sample).  draw_id=None takes the next value of this
-        workspace's own counter; pass an explicit id (e.g. the image id) for reproducible draws.  K1, K1b and K2b/K3 of
+        workspace's own counter; pass an explicit id (e.g. the image id) for reproducible draws.  K1, K1b / K1f and K2b/K3 of
         one image read the key from the same PodConfig, so they still re-derive identical draws."""
         if draw_id is None:
             draw_id = self._draws
@@ -245,12 +247,20 @@ class HotPath:
                 self._planes["maybe_bits"].zero_()
             self._dirty = False
 
+    def _geometry_levels(self):
+        """A level array that carries the geometry alone (H, W, anchor_base): for the entry points that read no tensor."""
+        lv = self._levels_t()
+        for l, (h, w) in enumerate(self.shapes):
+            lv[l].H, lv[l].W, lv[l].anchor_base = h, w, self.anchor_base[l]
+        return lv
+
     def _run_strided(self, name, l, t, c):
         """A level tensor (n_runs, A*c, H, W): every run a contiguous NCHW slab; the run stride is free (batched MC
         runs: A*c*H*W; ensemble members gathered into packed per-member buffers: the packed size)."""
         h, w = self.shapes[l]
         shape = (self.n_runs, self.p.num_anchors * c, h, w)
-        ok = t.dtype == torch.float32 and tuple(t.shape) == shape and tuple(t.stride()[1:]) == (h * w, w, 1) and t.device == self.device
+        dense = all(n == 1 or st == want for n, st, want in zip(shape[1:], t.stride()[1:], (h * w, w, 1)))      # a dimension of 1 has no stride to speak of
+        ok = t.dtype == torch.float32 and tuple(t.shape) == shape and dense and t.device == self.device
         if not ok:
             raise hip.PodError("{}[{}]: expected fp32 {} with contiguous runs on {}, got {} {} strides {} on {}".format(
                 name, l, shape, self.device, t.dtype, tuple(t.shape), tuple(t.stride()), t.device))
@@ -299,7 +309,7 @@ class HotPath:
         self._lv_keepalive = (lv, eps_cls)
         P = hip.ptr
         # cand_count is zero here: allocated zeroed, and the gather kernel consumes (re-zeroes) it every image
-        # prune mode: native RNG with a variance head -> dense pass flags, K1b samples (see k1_mc_merge_score.hip)
+        # prune mode: native RNG with a variance head -> the streaming pass flags, K1b / K1f's tail samples (csrc/pod_merge_score.h: may_pass)
         prune = self.has_cls_var and eps_cls is None
         wm = (write_merged or prune) and self.n_runs > 1
         if fused:
@@ -333,12 +343,10 @@ class HotPath:
 
     # -- test support: the native-RNG draws of one draw id, in the reference's tensor layouts ----------------------
     def dump_cls_normals(self, draw_id: int) -> List[torch.Tensor]:
-        """Per level, the (cls_samples, H*W*A, K) normals K1b / K2b use for `draw_id` (PI:291-294's rsample)."""
+        """Per level, the (cls_samples, H*W*A, K) normals K1b / K1f / K2b use for `draw_id` (PI:291-294's rsample)."""
         self._begin_draw(int(draw_id))
         A, K, S = self.p.num_anchors, self.p.num_classes, self.p.cls_var_num_samples
-        lv = self._levels_t()
-        for l, (h, w) in enumerate(self.shapes):
-            lv[l].H, lv[l].W, lv[l].anchor_base = h, w, self.anchor_base[l]
+        lv = self._geometry_levels()
         out = []
         for l, (h, w) in enumerate(self.shapes):
             t = torch.empty((S, h * w * A, K), dtype=torch.float32, device=self.device)

@@ -316,11 +316,17 @@ def test_native_candidate_moments_match_replay_statistically():
 # ---------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("quirk", [True, False])
-@pytest.mark.parametrize("runs,padded,prune", [(10, (384, 512), True), (5, (384, 512), False), (3, (96, 352), True), (2, (160, 224), False)])
+@pytest.mark.parametrize("runs,padded,prune", [(10, (384, 512), True), (5, (384, 512), False), (3, (96, 352), True), (2, (160, 224), False)] + [
+    # every tail of the shared run-merge schedule: with m = the runs added after the first (N - 1, or N - 2 under the quirk), K1's batches
+    # of 4 cut m into 4s, then 2, then 1 and K1f's batches of 2 into 2s, then 1 -- N = 7, 8, 9 give m = 5 .. 8, 4 + 2 and 4 + 2 + 1 among
+    # them.  (96, 352): 12x44 (vector path, H*W % 64 != 0: atomicOr), 6x22 / 3x11 (ragged: scalar path), 2x6 / 1x3 (less than a chunk);
+    # (128, 128): 16x16 = exactly one 256-cell chunk, H*W % 64 == 0 (row_or16's plain store)
+    (n, sz, pr) for n in (7, 8, 9) for sz in ((96, 352), (128, 128)) for pr in (True, False)])
 def test_dense_merge_planes_equal_reference_merge(runs, padded, prune, quirk):
     """pod_mc_merge_score with every mean_* output requested (HotPath(dense_box_merge=True)) against the oracle's
     left-to-right merge (PI:216-222: x0 twice, last run never, one divide), in both kernels (streaming prune kernel /
-    LDS class-per-wave kernel) and on ragged maps (scalar tails).  Layout: level-major, NCHW inside a level."""
+    LDS class-per-wave kernel) and on ragged maps (scalar tails); then the class planes pod_merge_score_fused stores
+    against the same reference.  Layout: level-major, NCHW inside a level."""
     from pod_compare_amd import hip
     ho = synthetic.planted_head_outputs(padded, runs, seed=31 + runs, num_boxes=8)
     params = hotpath.PathParams(num_classes=ho.num_classes, num_anchors=ho.num_anchors, merge_quirk=quirk)
@@ -336,15 +342,28 @@ def test_dense_merge_planes_equal_reference_merge(runs, padded, prune, quirk):
     torch.cuda.synchronize()
     if prune:
         hp.maybe_bits.zero_()
-    for name, out, src in (("cls", hp.mean_cls, ho.cls), ("cls_var", hp.mean_cls_var, ho.cls_var),
-                           ("delta", hp.mean_delta, ho.delta), ("reg_var", hp.mean_reg_var, ho.reg_var)):
-        off = 0
-        for l, x in enumerate(src):
-            ref = po.merge_runs([x[r] for r in range(runs)], quirk=quirk)           # (A*C, H, W)
-            got = out[off:off + ref.numel()].cpu().view_as(ref)
-            assert torch.equal(got, ref), (name, l, float((got - ref).abs().max()))
-            off += ref.numel()
-        assert off == out.numel()
+    refs = {name: [po.merge_runs([x[r] for r in range(runs)], quirk=quirk) for x in src]           # per level (A*C, H, W)
+            for name, src in (("cls", ho.cls), ("cls_var", ho.cls_var), ("delta", ho.delta), ("reg_var", ho.reg_var))}
+
+    def check_planes(kernel, outs):
+        for name, out in outs:
+            off = 0
+            for l, ref in enumerate(refs[name]):
+                got = out[off:off + ref.numel()].cpu().view_as(ref)
+                assert torch.equal(got, ref), (kernel, name, l, float((got - ref).abs().max()))
+                off += ref.numel()
+            assert off == out.numel()
+
+    check_planes("k1", (("cls", hp.mean_cls), ("cls_var", hp.mean_cls_var), ("delta", hp.mean_delta), ("reg_var", hp.mean_reg_var)))
+    # the fused launch, planes stored
+    for t in (hp.mean_cls, hp.mean_cls_var):
+        t.fill_(float("nan"))
+    hip.check(lib.pod_reset_counters(P(hp.counters), 8, st), "reset")
+    hip.check(lib.pod_merge_score_fused(hp.cfg, lv, P(hp.mean_cls), P(hp.mean_cls_var), P(hp.cand_keys), P(hp.cand_count),
+                                        P(hp.probs_dense), st), "k1f")
+    hip.check(lib.pod_reset_counters(P(hp.counters), 8, st), "reset")
+    torch.cuda.synchronize()
+    check_planes("k1f", (("cls", hp.mean_cls), ("cls_var", hp.mean_cls_var)))
 
 
 def test_product_path_skips_the_dense_box_merge_and_gets_the_same_detections():
