@@ -4,10 +4,15 @@
 // `> test_score_thresh` filter :300-308 (K1 already applied the threshold, which commutes with
 // top-k), the per-level gathers :305-338 and the level concatenation :341-342 / :387-388.
 //
-// K2: one 1024-thread workgroup per FPN level.  Keys are 64-bit (score bits, ~anchor index), all
-// distinct, so "top-k, ties to the lower index" is a plain descending sort.  Up to 2048
-// candidates are sorted directly in LDS (bitonic network); a level with more candidates first runs
-// an 8-pass MSB radix select (LDS histograms) to find the k-th largest key, then compacts.
+// K2: a grid of n_levels x TOPK_SLICES 1024-thread workgroups.  Keys are 64-bit (score bits, ~anchor index), all distinct, so
+// "top-k, ties to the lower index" is a plain descending sort.  A level falls into one of three size classes:
+//   <= SORT_CAP (2048) candidates, every level of a typical image: slice 0's workgroup sorts them directly in LDS (bitonic network);
+//   <= CACHE_CAP (16 384): slice 0's workgroup holds the level in registers (16 keys per thread), an MSB radix select (LDS
+//      histograms) narrows it to what the bitonic network then sorts;
+//   beyond: every workgroup narrows its own slice (keys in registers while a slice fits CACHE_CAP, re-fetched per pass beyond
+//      that), writes the survivors over the head of the slice and takes a ticket; the workgroup that draws the last ticket of
+//      its level selects and sorts the final top-k from the survivors.  No spinning: the others exit.
+// The radix select is stated once (radix_select); where a pass takes its keys from is the key source it is handed.
 // K2b: one thread per selected candidate re-derives the class probabilities with K1's own device
 // function (bit-identical), and gathers merged deltas / log-variances, the anchor and every run's
 // raw delta into the level-concatenated candidate arrays.
@@ -85,11 +90,10 @@ constexpr int TOPK_SLICES = 16;   // workgroups per level; only a level with mor
 struct TopkLds {
     uint64_t keys[SORT_CAP];
     uint32_t hist[256];
-    uint64_t prefix;
-    uint32_t wtot[4];
-    int32_t remaining, fill, bucket, ticket, pick, pick_rem;
-    uint64_t red_or[TOPK_THREADS / 64], red_and[TOPK_THREADS / 64];
+    uint64_t red_or[TOPK_THREADS / 64], red_and[TOPK_THREADS / 64];     // at a multiple of 16 bytes: read back as 16-byte vectors
     uint32_t red_n[TOPK_THREADS / 64];
+    uint32_t wtot[4];
+    int32_t pick, pick_rem, bucket, fill, ticket;      // the first three are pick_bucket's result
 };
 
 // Where level l's rows start in the level-concatenated candidate list, and the list's length: the counts of ALL levels are
@@ -121,139 +125,110 @@ __device__ __forceinline__ void write_selection(const K2Params& P, const TopkLds
     }
 }
 
-// The `want` largest of the `count` keys fetch(0..count-1) (all distinct, or 0 = absent), sorted descending in S.keys[0..want).
-// count <= SORT_CAP: straight into the LDS bitonic network.  Otherwise an MSB radix select (LDS histograms, from the top byte
-// down) runs until the keys that can still be in the top `want` fit the sort buffer: after a pass the candidates are {keys
-// above the chosen bucket} + {the bucket}; typically 2-4 passes.  8 independent fetches per thread per step.
-// SORT = false stops before the sort: S.keys[0 .. returned size) then holds an unordered SUPERSET of the top `want` (at most
-// SORT_CAP keys, zero-padded), which is all a slice has to hand to the final selection.
-template <bool SORT, class Fetch>
-__device__ __forceinline__ int topk_into_lds(TopkLds& S, Fetch fetch, int count, int want) {
-    const int tid = threadIdx.x;
-    int n_sort;
-    if (count <= SORT_CAP) {
-        n_sort = 1;
-        while (n_sort < count) n_sort <<= 1;
-        for (int i = tid; i < n_sort; i += TOPK_THREADS) S.keys[i] = (i < count) ? fetch(i) : 0ull;
-        __syncthreads();
-    } else {
-        if (tid == 0) {
-            S.prefix = 0ull;
-            S.remaining = want;
-            S.fill = 0;
+// ---- the MSB radix select: three steps, each stated once, and the driver that runs them over a key source ----------------------
+// One key's vote for its digit.  Every lane of the wavefront calls this together.  Top digits of score keys are heavily skewed:
+// one LDS atomic when the whole wavefront agrees.
+__device__ __forceinline__ void hist_vote(TopkLds& S, bool live, uint32_t digit) {
+    const unsigned long long lm = __ballot(live);
+    if (lm != 0ull) {
+        const int leader = __ffsll((long long)lm) - 1;
+        const uint32_t d0 = __shfl(digit, leader, 64);
+        if (__ballot(live && digit == d0) == lm) {
+            if ((threadIdx.x & 63) == leader) atomicAdd(&S.hist[d0], (uint32_t)__popcll(lm));
+        } else if (live) {
+            atomicAdd(&S.hist[digit], 1u);
         }
-        __syncthreads();
-        uint64_t lower_bound = 0ull;     // every key >= lower_bound is still a candidate; there are <= SORT_CAP of them at exit
-        for (int pass = 7; pass >= 0; --pass) {
-            const int shift = pass * 8;
-            if (tid < 256) S.hist[tid] = 0u;
-            __syncthreads();
-            const uint64_t prefix = S.prefix;
-            const uint64_t himask = (pass == 7) ? 0ull : (~0ull << (shift + 8));
-            for (int i0 = 0; i0 < count; i0 += TOPK_THREADS * 8) {
-                uint64_t kk[8];
+    }
+}
+
+// The bucket holding the `remaining`-th largest live key: the largest d with sum_{j >= d} hist[j] >= remaining.  Suffix sums by
+// wavefront scans (a single thread walking the 256 bins through LDS cost ~7 us per pass).  S.hist is complete on entry (the caller's
+// barrier); on return every thread may read S.pick (the bucket), S.pick_rem (what is still needed from it) and S.bucket (its size).
+__device__ __forceinline__ void pick_bucket(TopkLds& S, int remaining) {
+    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
+    uint32_t cnt = 0, incl = 0;
+    if (tid < 256) {
+        cnt = S.hist[tid];
+        incl = cnt;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int i = i0 + u * TOPK_THREADS + tid;
-                    kk[u] = (i < count) ? fetch(i) : 0ull;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int i = i0 + u * TOPK_THREADS + tid;
-                    const bool live = i < count && (kk[u] & himask) == prefix;
-                    // top digits of score keys are heavily skewed: one LDS atomic when the whole wavefront agrees
-                    const uint32_t digit = (uint32_t)(kk[u] >> shift) & 255u;
-                    const unsigned long long lm = __ballot(live);
-                    if (lm != 0ull) {
-                        const int leader = __ffsll((long long)lm) - 1;
-                        const uint32_t d0 = __shfl(digit, leader, 64);
-                        if (__ballot(live && digit == d0) == lm) {
-                            if ((threadIdx.x & 63) == leader) atomicAdd(&S.hist[d0], (uint32_t)__popcll(lm));
-                        } else if (live) {
-                            atomicAdd(&S.hist[digit], 1u);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            // bucket holding the `remaining`-th largest live key: the largest d with sum_{j >= d} hist[j] >= remaining.  Suffix sums by
-            // wavefront scans (a single thread walking the 256 bins through LDS cost ~7 us per pass)
-            uint32_t cnt = 0, incl = 0;
-            if (tid < 256) {
-                cnt = S.hist[tid];
-                incl = cnt;
-                const int ln = tid & 63;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t up = __shfl_down(incl, o, 64);
-                    if (ln + o < 64) incl += up;
-                }
-                if (ln == 0) S.wtot[tid >> 6] = incl;
-            }
-            __syncthreads();
-            if (tid < 256) {
-                for (int w = (tid >> 6) + 1; w < 4; ++w) incl += S.wtot[w];
-                const uint32_t excl = incl - cnt;                   // live keys in the buckets above this one
-                const uint32_t rem = (uint32_t)S.remaining;
-                // exactly one bucket qualifies; bucket 0 takes what no higher bucket covers (as a walk from the top would)
-                const bool chosen = tid == 0 ? excl < rem : (excl < rem && rem <= incl);
-                if (chosen) {
-                    S.pick = tid;
-                    S.pick_rem = (int)(rem - excl);
-                    S.bucket = (int)cnt;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) {
-                S.remaining = S.pick_rem;                            // still needed from bucket `pick`
-                S.prefix = prefix | ((uint64_t)S.pick << shift);
-            }
-            __syncthreads();
-            lower_bound = S.prefix;
-            // candidates = (want - remaining) keys above the bucket + the bucket itself
-            if ((want - S.remaining) + S.bucket <= SORT_CAP) break;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_down(incl, o, 64);
+            if (ln + o < 64) incl += up;
         }
-        const int n_cand = (want - S.remaining) + S.bucket;         // exact count of keys >= lower_bound
-        n_sort = 1;
-        while (n_sort < n_cand) n_sort <<= 1;
-        for (int i = tid; i < n_sort; i += TOPK_THREADS) S.keys[i] = 0ull;
-        __syncthreads();
+        if (ln == 0) S.wtot[wv] = incl;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        for (int w = wv + 1; w < 4; ++w) incl += S.wtot[w];
+        const uint32_t excl = incl - cnt, rem = (uint32_t)remaining;      // excl: live keys in the buckets above this one
+        // exactly one bucket qualifies; bucket 0 takes what no higher bucket covers (as a walk from the top would)
+        const bool chosen = tid == 0 ? excl < rem : (excl < rem && rem <= incl);
+        if (chosen) {
+            S.pick = tid;
+            S.pick_rem = (int)(rem - excl);
+            S.bucket = (int)cnt;
+        }
+    }
+    __syncthreads();
+}
+
+// One key's move into S.keys[0 .. limit).  Every lane of the wavefront calls this together.  One returning LDS atomic per wavefront
+// and call, not per key (2048 same-address returning atomics: ~40 us).  slot < limit always holds for distinct keys; a caller's
+// duplicates must not write past the buffer.
+__device__ __forceinline__ void compact_key(TopkLds& S, bool sel, uint64_t key, int limit) {
+    const unsigned long long sm = __ballot(sel);
+    if (sm != 0ull) {
+        const int ln = threadIdx.x & 63, leader = __ffsll((long long)sm) - 1;
+        int at = 0;
+        if (ln == leader) at = atomicAdd(&S.fill, __popcll(sm));
+        at = __shfl(at, leader, 64);
+        const int slot = at + __popcll(sm & ((1ull << ln) - 1ull));
+        if (sel && slot < limit) S.keys[slot] = key;
+    }
+}
+
+// A key source hands each(f) every key of this thread, 0 for an absent one; every thread of the workgroup makes the same number of
+// calls of f, so f may vote and ballot.
+constexpr int KPT = 16;
+constexpr int CACHE_CAP = KPT * TOPK_THREADS;
+
+// count <= CACHE_CAP keys fetched ONCE: a thread keeps its KPT keys in registers through all radix passes and the compaction.
+template <class Fetch>
+struct RegisterKeys {
+    uint64_t kk[KPT];
+    __device__ __forceinline__ RegisterKeys(Fetch fetch, int count) {
+#pragma unroll
+        for (int u = 0; u < KPT; ++u) {
+            const int i = u * TOPK_THREADS + threadIdx.x;
+            kk[u] = (i < count) ? fetch(i) : 0ull;
+        }
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F f) const {
+#pragma unroll
+        for (int u = 0; u < KPT; ++u) f(kk[u]);
+    }
+};
+
+// Any count, re-fetched on every walk: 8 independent fetches per thread per step.
+template <class Fetch>
+struct StreamedKeys {
+    Fetch fetch;
+    int count;
+    template <class F>
+    __device__ __forceinline__ void each(F f) const {
         for (int i0 = 0; i0 < count; i0 += TOPK_THREADS * 8) {
             uint64_t kk[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * TOPK_THREADS + tid;
+                const int i = i0 + u * TOPK_THREADS + threadIdx.x;
                 kk[u] = (i < count) ? fetch(i) : 0ull;
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * TOPK_THREADS + tid;
-                // one returning LDS atomic per wavefront and step, not per key (2048 same-address returning atomics: ~40 us)
-                const bool sel = i < count && kk[u] >= lower_bound && kk[u] != 0ull;
-                const unsigned long long sm = __ballot(sel);
-                if (sm != 0ull) {
-                    const int ln = threadIdx.x & 63, leader = __ffsll((long long)sm) - 1;
-                    int at = 0;
-                    if (ln == leader) at = atomicAdd(&S.fill, __popcll(sm));
-                    at = __shfl(at, leader, 64);
-                    if (sel) S.keys[at + __popcll(sm & ((1ull << ln) - 1ull))] = kk[u];
-                }
-            }
+            for (int u = 0; u < 8; ++u) f(kk[u]);
         }
-        __syncthreads();
     }
-    if (SORT) bitonic_sort_desc(S.keys, n_sort, tid, TOPK_THREADS);
-    return n_sort;
-}
-
-// The same selection for count <= CACHE_CAP with every key fetched ONCE: a thread keeps its KPT keys in registers through all
-// radix passes and the compaction (the loop version above re-fetches the list per pass: with 9 000 - 16 000 keys that was 3 - 4
-// round trips to L2 / HBM per workgroup, twice on the critical path of a big level).  The digits start at the highest bit in
-// which two present keys DIFFER (an OR / AND reduction over the workgroup): scores of candidates lie in (threshold, 1], so the
-// top 6 bits of every key agree and a fixed byte grid would spend its first pass on them.  Narrows until at most `cap` keys
-// (>= want) are left; SORT = false leaves them unordered, zero-padded to `cap`, and returns how many there are.
-constexpr int KPT = 16;
-constexpr int CACHE_CAP = KPT * TOPK_THREADS;
+};
 
 // How far the select narrows before the bitonic network takes over: the smallest power of two that holds the `want` keys (a
 // 2048-key sort costs 20 us on one CU, a 1024-key sort 11, an extra radix pass over registers 2.5).
@@ -263,94 +238,25 @@ __device__ __forceinline__ int sort_cap(int want) {
     return c;
 }
 
-template <bool SORT, class Fetch>
-__device__ __forceinline__ int topk_cached(TopkLds& S, Fetch fetch, int count, int want, int cap, int tb = 0) {
-    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
-    uint64_t kk[KPT];
-#pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-        const int i = u * TOPK_THREADS + tid;
-        kk[u] = (i < count) ? fetch(i) : 0ull;
-    }
-    uint64_t vor = 0ull, vand = ~0ull;
-    uint32_t present = 0;
-#pragma unroll
-    for (int u = 0; u < KPT; ++u)
-        if (kk[u] != 0ull) {
-            vor |= kk[u];
-            vand &= kk[u];
-            ++present;
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        vor |= shfl_xor_u64(vor, o);
-        vand &= shfl_xor_u64(vand, o);
-        present += __shfl_xor(present, o, 64);
-    }
-    if (ln == 0) {
-        S.red_or[wv] = vor;
-        S.red_and[wv] = vand;
-        S.red_n[wv] = present;
-    }
-    if (tid == 0) S.fill = 0;
-    __syncthreads();
-    vor = 0ull, vand = ~0ull, present = 0;
-#pragma unroll
-    for (int w = 0; w < TOPK_THREADS / 64; ++w) {
-        vor |= S.red_or[w];
-        vand &= S.red_and[w];
-        present += S.red_n[w];
-    }
-    K2_STAMP(tb);
-    const uint64_t diff = vor ^ vand;                    // bits in which two present keys differ (keys are distinct)
-    int hi = diff ? 64 - __clzll((long long)diff) : 0;    // every present key agrees on bits >= hi
-    uint64_t prefix = hi < 64 ? (vand >> hi) << hi : 0ull;
-    int remaining = want, bucket = (int)present;         // candidates = (want - remaining) above the bucket + the bucket
+// The `want` largest present keys of `keys` (all distinct), given that every present key agrees with `prefix` on bits >= hi and
+// that there are `bucket` of them.  Digits of up to 8 bits, from bit hi down, narrow the candidates = {keys above the chosen
+// bucket} + {the bucket} until at most `cap` (>= want) are left; typically 2-4 passes.  They are then compacted into S.keys and,
+// SORT, sorted descending: returns the sorted size.  SORT = false leaves them unordered, zero-padded to `cap`, and returns how many
+// there are: an unordered SUPERSET of the top `want`, which is all a slice has to hand to the final selection.
+// Stamps tb + 1 .. tb + 3: passes done, compacted, sorted.
+template <bool SORT, class Keys>
+__device__ __forceinline__ int radix_select(TopkLds& S, const Keys& keys, int want, int cap, int hi, uint64_t prefix, int bucket, int tb) {
+    const int tid = threadIdx.x;
+    int remaining = want;                                      // candidates = (want - remaining) above the bucket + the bucket
     while ((want - remaining) + bucket > cap && hi > 0) {
         const int shift = hi > 8 ? hi - 8 : 0;
         const uint32_t dmask = (1u << (hi - shift)) - 1u;
         const uint64_t himask = hi < 64 ? (~0ull << hi) : 0ull;
         if (tid < 256) S.hist[tid] = 0u;
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < KPT; ++u) {
-            const bool live = kk[u] != 0ull && (kk[u] & himask) == prefix;
-            const uint32_t digit = (uint32_t)(kk[u] >> shift) & dmask;
-            const unsigned long long lm = __ballot(live);
-            if (lm != 0ull) {
-                const int leader = __ffsll((long long)lm) - 1;
-                const uint32_t d0 = __shfl(digit, leader, 64);
-                if (__ballot(live && digit == d0) == lm) {
-                    if (ln == leader) atomicAdd(&S.hist[d0], (uint32_t)__popcll(lm));
-                } else if (live) {
-                    atomicAdd(&S.hist[digit], 1u);
-                }
-            }
-        }
+        keys.each([&](uint64_t key) { hist_vote(S, key != 0ull && (key & himask) == prefix, (uint32_t)(key >> shift) & dmask); });
         __syncthreads();
-        uint32_t cnt = 0, incl = 0;
-        if (tid < 256) {
-            cnt = S.hist[tid];
-            incl = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t up = __shfl_down(incl, o, 64);
-                if (ln + o < 64) incl += up;
-            }
-            if (ln == 0) S.wtot[wv] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            for (int w = wv + 1; w < 4; ++w) incl += S.wtot[w];
-            const uint32_t excl = incl - cnt, rem = (uint32_t)remaining;
-            const bool chosen = tid == 0 ? excl < rem : (excl < rem && rem <= incl);
-            if (chosen) {
-                S.pick = tid;
-                S.pick_rem = (int)(rem - excl);
-                S.bucket = (int)cnt;
-            }
-        }
-        __syncthreads();
+        pick_bucket(S, remaining);
         remaining = S.pick_rem;
         bucket = S.bucket;
         prefix |= (uint64_t)S.pick << shift;
@@ -363,20 +269,9 @@ __device__ __forceinline__ int topk_cached(TopkLds& S, Fetch fetch, int count, i
     if (n_sort > SORT_CAP) n_sort = SORT_CAP;                 // only a caller's duplicate keys get here (distinct keys narrow to <= cap): the excess is dropped
     const int n_clear = SORT ? n_sort : (cap < SORT_CAP ? cap : SORT_CAP);
     for (int i = tid; i < n_clear; i += TOPK_THREADS) S.keys[i] = 0ull;
+    if (tid == 0) S.fill = 0;
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < KPT; ++u) {
-        const bool sel = kk[u] != 0ull && kk[u] >= prefix;
-        const unsigned long long sm = __ballot(sel);
-        if (sm != 0ull) {
-            const int leader = __ffsll((long long)sm) - 1;
-            int at = 0;
-            if (ln == leader) at = atomicAdd(&S.fill, __popcll(sm));
-            at = __shfl(at, leader, 64);
-            const int slot = at + __popcll(sm & ((1ull << ln) - 1ull));
-            if (sel && slot < n_clear) S.keys[slot] = kk[u];      // (always true for distinct keys; a caller's duplicates must not write past the buffer)
-        }
-    }
+    keys.each([&](uint64_t key) { compact_key(S, key != 0ull && key >= prefix, key, n_clear); });
     __syncthreads();
     K2_STAMP(tb + 2);
     if (SORT) {
@@ -387,12 +282,78 @@ __device__ __forceinline__ int topk_cached(TopkLds& S, Fetch fetch, int count, i
     return n_cand;
 }
 
-// Grid = n_levels x TOPK_SLICES workgroups.  A level with <= SORT_CAP candidates (every level of a typical image) is sorted by
-// its slice-0 workgroup alone.  A bigger level is cut into TOPK_SLICES slices: the global top-k is contained in the union of the
-// slices' top-k, so every workgroup narrows its slice down to <= 2048 candidates containing the slice's top-k (16x shorter scans,
-// on 16 CUs), writes them back over the head of its own slice and takes a ticket; the workgroup that draws the last ticket selects
-// and sorts the final top-k from the <= 32k survivors.
+// The `want` largest of the `count` keys fetch(0..count-1) (all distinct, or 0 = absent), sorted descending in S.keys[0..want).
+// count <= SORT_CAP: straight into the LDS bitonic network.  Otherwise the select runs over the re-fetched list on the byte grid
+// (hi = 64: every bit may differ) until the candidates fit the sort buffer.  It starts from bucket = count, which only says that
+// at least one pass is due: absent keys take no part in the histograms (they used to be counted in bucket 0 of the top byte).
+// That changes no output: the compaction never took them, and their count only entered the candidate count, and through it the
+// sorted size, when bucket 0 of the top byte was the chosen one.
+// SORT = false: as radix_select (for count <= SORT_CAP the list itself, zero-padded to a power of two).  Stamp tb: select entered.
+template <bool SORT, class Fetch>
+__device__ __forceinline__ int topk_into_lds(TopkLds& S, Fetch fetch, int count, int want, int tb) {
+    const int tid = threadIdx.x;
+    if (count > SORT_CAP) {
+        K2_STAMP(tb);
+        return radix_select<SORT>(S, StreamedKeys<Fetch>{fetch, count}, want, SORT_CAP, 64, 0ull, count, tb);
+    }
+    int n_sort = 1;
+    while (n_sort < count) n_sort <<= 1;
+    for (int i = tid; i < n_sort; i += TOPK_THREADS) S.keys[i] = (i < count) ? fetch(i) : 0ull;
+    __syncthreads();
+    if (SORT) bitonic_sort_desc(S.keys, n_sort, tid, TOPK_THREADS);
+    return n_sort;
+}
+
+// The same selection for count <= CACHE_CAP with every key fetched ONCE (the streamed source re-fetches the list per pass: with
+// 9 000 - 16 000 keys that was 3 - 4 round trips to L2 / HBM per workgroup, twice on the critical path of a big level).  The digits
+// start at the highest bit in which two present keys DIFFER (an OR / AND reduction over the workgroup): scores of candidates lie in
+// (threshold, 1], so the top 6 bits of every key agree and a fixed byte grid would spend its first pass on them.
+// Stamp tb: keys loaded and reduced.
+template <bool SORT, class Fetch>
+__device__ __forceinline__ int topk_cached(TopkLds& S, Fetch fetch, int count, int want, int cap, int tb) {
+    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6;
+    const RegisterKeys<Fetch> keys(fetch, count);
+    uint64_t vor = 0ull, vand = ~0ull;
+    uint32_t present = 0;
+    keys.each([&](uint64_t key) {
+        if (key != 0ull) {
+            vor |= key;
+            vand &= key;
+            ++present;
+        }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        vor |= shfl_xor_u64(vor, o);
+        vand &= shfl_xor_u64(vand, o);
+        present += __shfl_xor(present, o, 64);
+    }
+    if (ln == 0) {
+        S.red_or[wv] = vor;
+        S.red_and[wv] = vand;
+        S.red_n[wv] = present;
+    }
+    __syncthreads();
+    vor = 0ull, vand = ~0ull, present = 0;
+#pragma unroll
+    for (int w = 0; w < TOPK_THREADS / 64; ++w) {
+        vor |= S.red_or[w];
+        vand &= S.red_and[w];
+        present += S.red_n[w];
+    }
+    K2_STAMP(tb);
+    const uint64_t diff = vor ^ vand;                          // bits in which two present keys differ (keys are distinct)
+    const int hi = diff ? 64 - __clzll((long long)diff) : 0;    // every present key agrees on bits >= hi
+    return radix_select<SORT>(S, keys, want, cap, hi, hi < 64 ? (vand >> hi) << hi : 0ull, (int)present, tb);
+}
+
+// Grid = n_levels x TOPK_SLICES workgroups.  A level with <= CACHE_CAP candidates is sorted by its slice-0 workgroup alone.  A bigger
+// level is cut into TOPK_SLICES slices: the global top-k is contained in the union of the slices' top-k, so every workgroup
+// narrows its slice down to <= 2048 candidates containing the slice's top-k (16x shorter scans, on 16 CUs), writes them back over
+// the head of its own slice and takes a ticket; the workgroup that draws the last ticket selects and sorts the final top-k from the
+// <= 32k survivors.
 // No spinning: the others simply exit.
+// Stamps (POD_TRACE): 0 start, 1 counts, 2-5 a slice's (or the one workgroup's) select, 6 ticket, 7 fence, 8-11 the final select, 12 written.
 __global__ void __launch_bounds__(TOPK_THREADS) k2_level_topk(const K2Params P) {
     __shared__ TopkLds S;
     const int l = blockIdx.x / TOPK_SLICES, b = blockIdx.x % TOPK_SLICES;
@@ -408,27 +369,27 @@ __global__ void __launch_bounds__(TOPK_THREADS) k2_level_topk(const K2Params P) 
     uint64_t* out = P.sel_keys + (int64_t)l * P.topk;
     if (C <= SORT_CAP) {
         if (b != 0) return;
-        topk_into_lds<true>(S, [=](int i) { return keys[i]; }, C, k);
+        topk_into_lds<true>(S, [=](int i) { return keys[i]; }, C, k, 2);
         write_selection(P, S, l, k, out, off, total);
         return;
     }
     if (C <= CACHE_CAP) {                 // one workgroup holds the whole level in registers: no slices, no ticket
         if (b != 0) return;
-        topk_cached<true>(S, [=](int i) { return keys[i]; }, C, k, sort_cap(k));
+        topk_cached<true>(S, [=](int i) { return keys[i]; }, C, k, sort_cap(k), 2);
         write_selection(P, S, l, k, out, off, total);
         return;
     }
     const int slice = ((C + TOPK_SLICES - 1) / TOPK_SLICES + 7) & ~7;      // keys per slice
     const int begin = b * slice;
     const int len = max(0, min(slice, C - begin));
-    const bool cached = slice <= CACHE_CAP;                                // else the loop version (levels beyond 262 144 candidates)
+    const bool cached = slice <= CACHE_CAP;                                // else the streamed source (levels beyond 262 144 candidates)
     // survivors of a slice = an unordered superset of its top-k, at most `cap` keys, written over the head of the slice and
     // zero-padded to min(len, cap); a slice that short is its own survivor list.  Sorting here would only be redone below.
     const int cap = (cached && k <= SORT_CAP / 2) ? SORT_CAP / 2 : SORT_CAP;
     if (len > cap) {
         const uint64_t* mine = keys + begin;
         const int n_out = cached ? topk_cached<false>(S, [=](int i) { return mine[i]; }, len, min(k, len), cap, 2)
-                                 : topk_into_lds<false>(S, [=](int i) { return mine[i]; }, len, min(k, len));
+                                 : topk_into_lds<false>(S, [=](int i) { return mine[i]; }, len, min(k, len), 2);
         for (int i = tid; i < cap; i += TOPK_THREADS) keys[begin + i] = i < n_out ? S.keys[i] : 0ull;   // only this workgroup touches the slice
     }
     __threadfence();
@@ -450,7 +411,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) k2_level_topk(const K2Params P) 
     if (TOPK_SLICES * cap <= CACHE_CAP)
         topk_cached<true>(S, survivors, TOPK_SLICES * cap, k, sort_cap(k), 8);
     else
-        topk_into_lds<true>(S, survivors, TOPK_SLICES * cap, k);
+        topk_into_lds<true>(S, survivors, TOPK_SLICES * cap, k, 8);
     write_selection(P, S, l, k, out, off, total);
     if (tid == 0) *ticket = 0;
     K2_STAMP(12);
@@ -497,17 +458,9 @@ extern "C" int pod_gather_candidates(const PodConfig* cfg, const PodLevel* level
         !cand_score || !cand_class || !cand_probs || !cand_delta || !cand_anchor)
         return POD_E_INVALID;
     if (cfg->cov_dims > 0 && !cand_reg_var) return POD_E_INVALID;
-    if (cfg->n_levels * cfg->topk > POD_MAX_CANDIDATES * 4) return POD_E_INVALID;
-    if (2 * cfg->num_classes + 4 + cfg->cov_dims > 64) return POD_E_INVALID;
-    pod::K2bParams P;
-    for (int l = 0; l < cfg->n_levels; ++l) P.lv[l] = levels[l];
-    P.n_levels = cfg->n_levels; P.n_runs = cfg->n_runs; P.A = cfg->num_anchors; P.K = cfg->num_classes; P.D = cfg->cov_dims;
-    P.has_cls_var = cfg->has_cls_var; P.quirk = cfg->merge_quirk; P.cls_samples = cfg->cls_samples; P.topk = cfg->topk;
-    P.seed = cfg->philox_seed; P.anchors = anchors; P.cat_keys = cat_keys; P.cat_level = cat_level; P.n_total = n_total;
-    P.cand_count = cand_count; P.probs_dense = probs_dense;
-    P.cand_anchor_idx = cand_anchor_idx; P.cand_level = cand_level; P.cand_score = cand_score; P.cand_class = cand_class;
-    P.cand_probs = cand_probs; P.cand_delta = cand_delta; P.cand_reg_var = cand_reg_var; P.cand_anchor = cand_anchor;
-    P.cand_run_delta = cfg->n_runs > 1 ? cand_run_delta : nullptr;
+    if (!pod_candidate_cfg_ok(cfg, POD_CHECK_ROWS | POD_CHECK_CHANNELS)) return POD_E_INVALID;
+    const pod::K2bParams P = pod_k2b_params(cfg, levels, anchors, cat_keys, cat_level, n_total, cand_count, probs_dense, cand_anchor_idx, cand_level,
+                                            cand_score, cand_class, cand_probs, cand_delta, cand_reg_var, cand_anchor, cand_run_delta);
     const int slots = cfg->n_levels * cfg->topk;
     hipLaunchKernelGGL(pod::k2b_gather, dim3(slots), dim3(64), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();

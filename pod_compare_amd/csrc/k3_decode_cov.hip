@@ -130,17 +130,12 @@ extern "C" int pod_decode_cov(const PodConfig* cfg, const PodLevel* levels, cons
                               const float* eps_prop, int32_t n_replay, float* boxes, float* cov, pod_stream_t stream) {
     if (!cfg || !levels || !n_total || n_capacity < 1 || !cand_delta || !cand_anchor || !boxes || !cov) return POD_E_INVALID;
     if (cfg->cov_dims > 0 && (!cand_reg_var || !cand_anchor_idx || !cand_level)) return POD_E_INVALID;
-    if (cfg->cov_dims > 0 && (cfg->prop_samples < 2 || cfg->prop_samples > POD_MAX_PROP_SAMPLES)) return POD_E_INVALID;
+    if (!pod_candidate_cfg_ok(cfg, POD_CHECK_PROP_SAMPLES)) return POD_E_INVALID;
     if (cfg->n_runs > 1 && !cand_run_delta) return POD_E_INVALID;
     if (cfg->n_runs > POD_MAX_RUNS) return POD_E_INVALID;
     if (eps_prop && n_replay < 1) return POD_E_INVALID;
-    pod::K3Params P;
-    for (int l = 0; l < cfg->n_levels; ++l) P.anchor_base[l] = levels[l].anchor_base;
-    P.n_runs = cfg->n_runs; P.D = cfg->cov_dims; P.S = cfg->prop_samples; P.n_capacity = n_capacity; P.n_replay = n_replay;
-    for (int c = 0; c < 4; ++c) P.wts[c] = cfg->box_weights[c];
-    P.seed = cfg->philox_seed; P.n_total = n_total; P.cand_delta = cand_delta; P.cand_reg_var = cand_reg_var;
-    P.cand_anchor = cand_anchor; P.cand_run_delta = cand_run_delta; P.cand_anchor_idx = cand_anchor_idx;
-    P.cand_level = cand_level; P.eps_prop = eps_prop; P.boxes = boxes; P.cov = cov;
+    const pod::K3Params P = pod_k3_params(cfg, levels, n_total, n_capacity, cand_delta, cand_reg_var, cand_anchor, cand_run_delta, cand_anchor_idx,
+                                          cand_level, eps_prop, n_replay, boxes, cov);
     hipLaunchKernelGGL(pod::k3_decode_cov, dim3(n_capacity), dim3(64), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     return POD_OK;
@@ -155,29 +150,14 @@ extern "C" int pod_gather_decode(const PodConfig* cfg, const PodLevel* levels, c
         !cand_score || !cand_class || !cand_probs || !cand_delta || !cand_anchor || !boxes || !cov)
         return POD_E_INVALID;
     if (cfg->cov_dims > 0 && !cand_reg_var) return POD_E_INVALID;
-    if (cfg->cov_dims > 0 && (cfg->prop_samples < 2 || cfg->prop_samples > POD_MAX_PROP_SAMPLES)) return POD_E_INVALID;
-    if (cfg->n_levels < 1 || cfg->n_levels > POD_MAX_LEVELS || cfg->n_runs < 1 || cfg->n_runs > POD_MAX_RUNS) return POD_E_INVALID;
-    if (cfg->n_levels * cfg->topk > POD_MAX_CANDIDATES * 4) return POD_E_INVALID;
-    if (2 * cfg->num_classes + 4 + cfg->cov_dims > 64) return POD_E_INVALID;
+    if (!pod_candidate_cfg_ok(cfg, POD_CHECK_LEVELS_RUNS | POD_CHECK_CHANNELS | POD_CHECK_PROP_SAMPLES | POD_CHECK_ROWS)) return POD_E_INVALID;
     for (int l = 0; l < cfg->n_levels; ++l)
         if (levels[l].eps_cls) return POD_E_INVALID;   // native draws only: eps-replay uses pod_gather_candidates + pod_decode_cov
     pod::K23Params P;
-    pod::K2bParams& G = P.g;
-    for (int l = 0; l < cfg->n_levels; ++l) G.lv[l] = levels[l];
-    G.n_levels = cfg->n_levels; G.n_runs = cfg->n_runs; G.A = cfg->num_anchors; G.K = cfg->num_classes; G.D = cfg->cov_dims;
-    G.has_cls_var = cfg->has_cls_var; G.quirk = cfg->merge_quirk; G.cls_samples = cfg->cls_samples; G.topk = cfg->topk;
-    G.seed = cfg->philox_seed; G.anchors = anchors; G.cat_keys = cat_keys; G.cat_level = cat_level; G.n_total = n_total;
-    G.cand_count = cand_count; G.probs_dense = probs_dense;
-    G.cand_anchor_idx = cand_anchor_idx; G.cand_level = cand_level; G.cand_score = cand_score; G.cand_class = cand_class;
-    G.cand_probs = cand_probs; G.cand_delta = cand_delta; G.cand_reg_var = cand_reg_var; G.cand_anchor = cand_anchor;
-    G.cand_run_delta = cfg->n_runs > 1 ? cand_run_delta : nullptr;
-    pod::K3Params& Dp = P.d;
-    for (int l = 0; l < cfg->n_levels; ++l) Dp.anchor_base[l] = levels[l].anchor_base;
-    Dp.n_runs = cfg->n_runs; Dp.D = cfg->cov_dims; Dp.S = cfg->prop_samples; Dp.n_capacity = cfg->n_levels * cfg->topk; Dp.n_replay = 0;
-    for (int c = 0; c < 4; ++c) Dp.wts[c] = cfg->box_weights[c];
-    Dp.seed = cfg->philox_seed; Dp.n_total = n_total; Dp.cand_delta = cand_delta; Dp.cand_reg_var = cand_reg_var;
-    Dp.cand_anchor = cand_anchor; Dp.cand_run_delta = cand_run_delta; Dp.cand_anchor_idx = cand_anchor_idx;
-    Dp.cand_level = cand_level; Dp.eps_prop = nullptr; Dp.boxes = boxes; Dp.cov = cov;
+    P.g = pod_k2b_params(cfg, levels, anchors, cat_keys, cat_level, n_total, cand_count, probs_dense, cand_anchor_idx, cand_level, cand_score,
+                         cand_class, cand_probs, cand_delta, cand_reg_var, cand_anchor, cand_run_delta);
+    P.d = pod_k3_params(cfg, levels, n_total, cfg->n_levels * cfg->topk, cand_delta, cand_reg_var, cand_anchor, cand_run_delta, cand_anchor_idx,
+                        cand_level, nullptr, 0, boxes, cov);
     P.small_max = pod::K23_SMALL_MAX;   // swept 1024 / 2048 / 3072 / 8192 over n = 490 .. 4594 (profiles/r02_candidate_sweep.md): flat up to
                                         // ~2000, above that the one-wavefront shape wins by up to 30 us
     hipLaunchKernelGGL(pod::k23_gather_decode, dim3(cfg->n_levels * cfg->topk), dim3(pod::K23_THREADS), 0, (hipStream_t)stream, P);

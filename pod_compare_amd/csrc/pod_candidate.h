@@ -409,3 +409,53 @@ __device__ __forceinline__ void decode_candidate(const K3Params& P, int i, int l
 }
 
 }  // namespace pod
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+// The cfg ranges the candidate entry points (pod_gather_candidates, pod_decode_cov, pod_gather_decode) rely on.  An entry point
+// names the checks it has always made: none of them checks more, or less, than it did.
+enum : unsigned {
+    POD_CHECK_LEVELS_RUNS = 1u,    // 1 <= n_levels <= POD_MAX_LEVELS, 1 <= n_runs <= POD_MAX_RUNS
+    POD_CHECK_CHANNELS = 2u,       // 2K + 4 + D channels fit the 64 lanes of gather_candidate
+    POD_CHECK_PROP_SAMPLES = 4u,   // 2 <= prop_samples <= POD_MAX_PROP_SAMPLES when there is a reg_var head
+    POD_CHECK_ROWS = 8u,           // n_levels * topk candidate rows
+};
+static inline bool pod_candidate_cfg_ok(const PodConfig* cfg, unsigned checks) {
+    if ((checks & POD_CHECK_LEVELS_RUNS) &&
+        (cfg->n_levels < 1 || cfg->n_levels > POD_MAX_LEVELS || cfg->n_runs < 1 || cfg->n_runs > POD_MAX_RUNS))
+        return false;
+    if ((checks & POD_CHECK_CHANNELS) && 2 * cfg->num_classes + 4 + cfg->cov_dims > 64) return false;
+    if ((checks & POD_CHECK_PROP_SAMPLES) && cfg->cov_dims > 0 && (cfg->prop_samples < 2 || cfg->prop_samples > POD_MAX_PROP_SAMPLES))
+        return false;
+    return !(checks & POD_CHECK_ROWS) || cfg->n_levels * cfg->topk <= POD_MAX_CANDIDATES * 4;
+}
+
+static inline pod::K2bParams pod_k2b_params(const PodConfig* cfg, const PodLevel* levels, const float* anchors, const uint64_t* cat_keys,
+                                            const int32_t* cat_level, const int32_t* n_total, int32_t* cand_count, const float* probs_dense,
+                                            int32_t* cand_anchor_idx, int32_t* cand_level, float* cand_score, int32_t* cand_class,
+                                            float* cand_probs, float* cand_delta, float* cand_reg_var, float* cand_anchor,
+                                            float* cand_run_delta) {
+    pod::K2bParams P;
+    for (int l = 0; l < cfg->n_levels; ++l) P.lv[l] = levels[l];
+    P.n_levels = cfg->n_levels; P.n_runs = cfg->n_runs; P.A = cfg->num_anchors; P.K = cfg->num_classes; P.D = cfg->cov_dims;
+    P.has_cls_var = cfg->has_cls_var; P.quirk = cfg->merge_quirk; P.cls_samples = cfg->cls_samples; P.topk = cfg->topk;
+    P.seed = cfg->philox_seed; P.anchors = anchors; P.cat_keys = cat_keys; P.cat_level = cat_level; P.n_total = n_total;
+    P.cand_count = cand_count; P.probs_dense = probs_dense;
+    P.cand_anchor_idx = cand_anchor_idx; P.cand_level = cand_level; P.cand_score = cand_score; P.cand_class = cand_class;
+    P.cand_probs = cand_probs; P.cand_delta = cand_delta; P.cand_reg_var = cand_reg_var; P.cand_anchor = cand_anchor;
+    P.cand_run_delta = cfg->n_runs > 1 ? cand_run_delta : nullptr;
+    return P;
+}
+
+static inline pod::K3Params pod_k3_params(const PodConfig* cfg, const PodLevel* levels, const int32_t* n_total, int32_t n_capacity,
+                                          const float* cand_delta, const float* cand_reg_var, const float* cand_anchor,
+                                          const float* cand_run_delta, const int32_t* cand_anchor_idx, const int32_t* cand_level,
+                                          const float* eps_prop, int32_t n_replay, float* boxes, float* cov) {
+    pod::K3Params P;
+    for (int l = 0; l < cfg->n_levels; ++l) P.anchor_base[l] = levels[l].anchor_base;
+    P.n_runs = cfg->n_runs; P.D = cfg->cov_dims; P.S = cfg->prop_samples; P.n_capacity = n_capacity; P.n_replay = n_replay;
+    for (int c = 0; c < 4; ++c) P.wts[c] = cfg->box_weights[c];
+    P.seed = cfg->philox_seed; P.n_total = n_total; P.cand_delta = cand_delta; P.cand_reg_var = cand_reg_var;
+    P.cand_anchor = cand_anchor; P.cand_run_delta = cand_run_delta; P.cand_anchor_idx = cand_anchor_idx;
+    P.cand_level = cand_level; P.eps_prop = eps_prop; P.boxes = boxes; P.cov = cov;
+    return P;
+}

@@ -86,6 +86,67 @@ def test_invalid_arguments_are_rejected_without_a_gpu(lib_path):
     assert lib.pod_wino_filter_split_bytes(64, 32) == 2 * 24 * 64 * 32 * 2 + 16 and lib.pod_wino_filter_split_bytes(64, 8) == 0
 
 
+def test_candidate_entry_points_reject_invalid_arguments_without_a_gpu(lib_path):
+    """pod_gather_candidates, pod_decode_cov and pod_gather_decode: every null pointer and every out-of-range cfg field an entry
+    point checks makes it return POD_E_INVALID before anything is launched; each entry point checks what it always did."""
+    lib = hip.load()
+    buf = ctypes.create_string_buffer(64)
+    X = ctypes.addressof(buf)                        # any non-null pointer: never dereferenced on these paths
+    lv = (hip.PodLevel * hip.POD_MAX_LEVELS)()
+
+    def cfg_with(**kw):
+        c = hip.PodConfig()
+        c.n_levels, c.n_runs, c.num_anchors, c.num_classes, c.cov_dims, c.prop_samples, c.topk = 5, 10, 9, 7, 4, 1000, 1000
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    def gather(c, levels=lv, reg_var=X, **null):     # the 15 pointers after `levels`, by position, and a null stream
+        a = [X] * 15 + [None]
+        a[12] = reg_var
+        for i in null.values():
+            a[i] = None
+        return lib.pod_gather_candidates(c, levels, *a)
+
+    def decode(c, n_capacity=8, reg_var=X, run_delta=X, idx=X, level=X, eps=None, n_replay=0, n_total=X, delta=X, anchor=X, boxes=X, cov=X):
+        return lib.pod_decode_cov(c, lv, n_total, n_capacity, delta, reg_var, anchor, run_delta, idx, level, eps, n_replay, boxes, cov, None)
+
+    def fused(c, levels=lv, reg_var=X, **null):      # the 17 pointers after `levels`, by position, and a null stream
+        a = [X] * 17 + [None, None]
+        a[12] = reg_var
+        for i in null.values():
+            a[i] = None
+        return lib.pod_gather_decode(c, levels, *a)
+
+    ok = cfg_with()
+    # pod_gather_candidates: nulls (probs_dense, cand_reg_var without a head, cand_run_delta and the stream may be null), rows, channels
+    assert gather(None) == -1 and gather(ok, levels=None) == -1
+    for i in (0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 13):
+        assert gather(ok, null=i) == -1, i
+    assert gather(ok, reg_var=None) == -1
+    assert gather(cfg_with(n_levels=8, topk=4097)) == -1                       # n_levels * topk > 4 * POD_MAX_CANDIDATES
+    assert gather(cfg_with(num_classes=16, cov_dims=29)) == -1 and gather(cfg_with(num_classes=29, cov_dims=4)) == -1   # 2K + 4 + D = 65
+    # pod_decode_cov: nulls, n_capacity, prop_samples with a reg_var head, n_runs above the maximum, replay without a count
+    assert lib.pod_decode_cov(None, lv, X, 8, X, X, X, X, X, X, None, 0, X, X, None) == -1
+    assert lib.pod_decode_cov(ok, None, X, 8, X, X, X, X, X, X, None, 0, X, X, None) == -1
+    for kw in ({"n_total": None}, {"delta": None}, {"anchor": None}, {"boxes": None}, {"cov": None}, {"n_capacity": 0}, {"reg_var": None},
+               {"idx": None}, {"level": None}, {"run_delta": None}, {"eps": X, "n_replay": 0}):
+        assert decode(ok, **kw) == -1, kw
+    assert decode(cfg_with(prop_samples=1)) == -1 and decode(cfg_with(prop_samples=hip.POD_MAX_PROP_SAMPLES + 1)) == -1
+    assert decode(cfg_with(n_runs=hip.POD_MAX_RUNS + 1)) == -1
+    # pod_gather_decode: the union, plus the n_levels / n_runs ranges and native draws only
+    assert fused(None) == -1 and fused(ok, levels=None) == -1
+    for i in (0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 13, 15, 16):
+        assert fused(ok, null=i) == -1, i
+    assert fused(ok, reg_var=None) == -1
+    for kw in ({"n_levels": 0}, {"n_levels": hip.POD_MAX_LEVELS + 1}, {"n_runs": 0}, {"n_runs": hip.POD_MAX_RUNS + 1}, {"n_levels": 8, "topk": 4097},
+               {"num_classes": 16, "cov_dims": 29}, {"prop_samples": 1}, {"prop_samples": hip.POD_MAX_PROP_SAMPLES + 1}):
+        assert fused(cfg_with(**kw)) == -1, kw
+    replay = (hip.PodLevel * hip.POD_MAX_LEVELS)()
+    replay[4].eps_cls = X
+    assert fused(ok, levels=replay) == -1
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setenv("POD_MI355X_LIB", "/nonexistent/libpod_mi355x.so")
     monkeypatch.setattr(hip, "_lib", None)

@@ -19,7 +19,8 @@ lib = ctypes.CDLL(hip.library_path())
 lib.pod_k2_trace_dump.argtypes = [ctypes.c_void_p]
 assert lib.pod_k2_trace_dump(host.ctypes.data) == 0
 t0 = host[:80, 0][host[:80, 0] > 0].min()
-names = {0: "start", 1: "counts", 2: "slice: keys loaded", 3: "slice: passes", 4: "slice: compacted", 6: "ticket", 7: "fence", 8: "final: keys loaded",
+# a level of at most 16 384 candidates is selected by its slice-0 workgroup alone, which stamps the slice slots and 5 for its sort
+names = {0: "start", 1: "counts", 2: "slice: keys loaded", 3: "slice: passes", 4: "slice: compacted", 5: "slice: sorted", 6: "ticket", 7: "fence", 8: "final: keys loaded",
          9: "final: passes", 10: "final: compacted", 11: "final: sorted", 12: "written"}
 for wg in range(80):
     row = host[wg]
