@@ -361,13 +361,26 @@ __device__ __forceinline__ void wino_dropout8(f32x4& v0, f32x4& v1, int64_t e, u
     v1.w = (r4.w >> 16) >= thresh ? v1.w * scale : 0.f;
 }
 
+// Both store passes take the launch's uniform decisions (ReLU, dropout, abs-max record) ONCE, as template parameters behind one dispatch,
+// and keep their loops straight-line: a thread's arithmetic and Philox calls run for every row, valid or not, only the stores and the
+// abs-max contribution are predicated; the row combination takes the parity as an operand (x - y == fma(-1, y, x), one rounding either
+// way); addresses are stepped, not rebuilt.  (Measured on the ISA of the form before: one exec region and 9 integer multiplies per row,
+// the four Philox chains of a batch one behind the other, ~1 100 instructions per trip of the layers-2-4 form: profiles/store_pass_ab.md.)
+
 // NCHW planes (the predictors: the layout K1 streams): thread -> (channel, row of the block, 4 pixels along x = one tile's columns);
-// 64-byte runs per (channel, row).  No dropout, no replicas.
-__device__ __forceinline__ float wino_store_planes(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
-    const int tid = threadIdx.x;
+// 64-byte runs per (channel, row).  No dropout, no replicas.  Wave w serves channels ks 64 + 4 it + w, it = 0..15, in batches of four
+// (the 48 LDS reads of a batch in one round trip); lane `it` of the wave holds iteration it's bias -- one load in front of the loop,
+// nothing in the loop waits on vmcnt behind its own stores.  Iterations past k_planes (the last batch) compute and store nothing.
+template <bool RELU, bool AMAX>
+__device__ __forceinline__ float wino_store_planes_form(const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float lmax = 0.0f;
     const f32x4 inv = f32x4{S.inv, S.inv, S.inv, S.inv};
-    const int oy = (tid >> 2) & 15, ox = (tid & 3) * 4;
+    const int oy = (tid >> 2) & 15, ox = (tid & 3) * 4, odd = oy & 1;
+    const float sg = odd ? -1.0f : 1.0f;
+    const int kg0 = ks * 64 + wave;
+    const int n_it = (S.k_planes - kg0 + 3) >> 2;     // channels kg0 + 4 it < k_planes: it < n_it
+    const float bias_l = S.bias ? S.bias[kg0 + 4 * (tid & 15)] : 0.0f;
     int m;
     const int gy = wino_cell(B.y0 + oy, B.Hv, B.rHv, m);
     int64_t px0[4];                                   // output pixel (of plane 0) per column, -1: not a pixel of any image
@@ -378,106 +391,162 @@ __device__ __forceinline__ float wino_store_planes(const WinoParams& P, const Wi
         px0[e] = (n < B.gcols && img < B.n_img && gx < B.W && gy < B.H) ? (B.out_px + (int64_t)img * B.HWi) * S.k_planes + (int64_t)gy * B.W + gx : -1;
     }
     const bool vec = px0[0] >= 0 && px0[3] == px0[0] + 3 && (px0[0] & 3) == 0 && (B.HWi & 3) == 0;
-    const int tile = (oy >> 1) * 4 + (tid & 3);
-#pragma unroll 2
-    for (int it = 0; it < 16; ++it) {
-        const int k = it * 4 + (tid >> 6), kg = ks * 64 + k;
-        if (kg >= S.k_planes) continue;
-        const float bias = S.bias ? S.bias[kg] : 0.0f;
-        float y[4];
+    const bool ok[4] = {px0[0] >= 0, px0[1] >= 0, px0[2] >= 0, px0[3] >= 0};
+    int64_t q[4];                                     // the thread's 4 pixels in the plane of the batch's first channel: + 4 planes per iteration
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float* r = lds + tile * WINO_TS + e * 64 + k;                 // Z[a][tile][e][k] at + a * WINO_ZA
-            y[e] = (oy & 1) == 0 ? (r[0] + r[WINO_ZA]) + r[2 * WINO_ZA] : (r[WINO_ZA] - r[2 * WINO_ZA]) - r[3 * WINO_ZA];
+    for (int e = 0; e < 4; ++e) q[e] = (int64_t)kg0 * B.HWi + px0[e];
+    const int64_t q_it = (int64_t)4 * B.HWi;
+    const int tile = (oy >> 1) * 4 + (tid & 3);
+    const float* r = lds + tile * WINO_TS + wave + (odd ? WINO_ZA : 0);     // Z[a][tile][e][k] at + a WINO_ZA + 64 e: rows a = odd .. odd + 2
+#pragma unroll 1
+    for (int it0 = 0; it0 < 16 && it0 < n_it; it0 += 4, r += 16) {
+        float z[4][4][3];
+        f32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int a = 0; a < 3; ++a) z[j][e][a] = r[4 * j + e * 64 + a * WINO_ZA];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float bias = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bias_l), it0 + j));
+            f32x4 y;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) y[e] = __builtin_fmaf(sg, z[j][e][2], __builtin_fmaf(sg, z[j][e][1], z[j][e][0]));      // even rows (Z0 + Z1) + Z2, odd rows (Z1 - Z2) - Z3
+            v[j] = __builtin_elementwise_fma(y, inv, f32x4{bias, bias, bias, bias});
+            if (RELU) wino_relu4(v[j]);
+            if (AMAX) {
+                const float mx = wino_absmax4(0.0f, f32x4{ok[0] ? v[j].x : 0.f, ok[1] ? v[j].y : 0.f, ok[2] ? v[j].z : 0.f, ok[3] ? v[j].w : 0.f});
+                lmax = fmaxf(lmax, it0 + j < n_it ? mx : 0.0f);
+            }
         }
-        f32x4 v = __builtin_elementwise_fma(f32x4{y[0], y[1], y[2], y[3]}, inv, f32x4{bias, bias, bias, bias});
-        if (P.relu) wino_relu4(v);
-        if (S.out_amax)
-            lmax = wino_absmax4(lmax, f32x4{px0[0] >= 0 ? v.x : 0.f, px0[1] >= 0 ? v.y : 0.f, px0[2] >= 0 ? v.z : 0.f, px0[3] >= 0 ? v.w : 0.f});
-        float* plane = S.out + (int64_t)kg * B.HWi;
-        if (vec) {
-            *reinterpret_cast<f32x4*>(plane + px0[0]) = v;
-        } else {
-            if (px0[0] >= 0) plane[px0[0]] = v.x;
-            if (px0[1] >= 0) plane[px0[1]] = v.y;
-            if (px0[2] >= 0) plane[px0[2]] = v.z;
-            if (px0[3] >= 0) plane[px0[3]] = v.w;
+        wino_pin(v[0], v[1], v[2], v[3]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool live = it0 + j < n_it;
+            if (live && vec) {
+                *reinterpret_cast<f32x4*>(S.out + q[0]) = v[j];
+            } else if (live) {
+                if (ok[0]) S.out[q[0]] = v[j].x;
+                if (ok[1]) S.out[q[1]] = v[j].y;
+                if (ok[2]) S.out[q[2]] = v[j].z;
+                if (ok[3]) S.out[q[3]] = v[j].w;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) q[e] += q_it;
         }
     }
     return lmax;
 }
+// (The abs-max forms: wino.py never asks a planes launch for a record, but PodWinoConv accepts out_amax with k_planes > 0 and that stays
+// served -- tests/wino_store_pass covers it through a grouped launch.)
+__device__ __forceinline__ float wino_store_planes(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+    switch ((P.relu ? 1 : 0) | (S.out_amax ? 2 : 0)) {
+        case 0: return wino_store_planes_form<false, false>(B, S, lds, ks);
+        case 1: return wino_store_planes_form<true, false>(B, S, lds, ks);
+        case 2: return wino_store_planes_form<false, true>(B, S, lds, ks);
+        default: return wino_store_planes_form<true, true>(B, S, lds, ks);
+    }
+}
 
-// Channels-last: thread -> 8 consecutive channels (one Philox call) of one pixel column, rows of one parity.
-__device__ __forceinline__ float wino_store_channels_last(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+// Channels-last: thread -> 8 consecutive channels (one Philox call) of one pixel column, rows of one parity (canvas rows y0 + odd + 2 i,
+// i = 0..7).  The element offset e of a row is the one of the row before + 2 W out_stride, + (gcols HWi - Hv W) out_stride when the row
+// leaves its image for the one below (Hv >= 2: at most once per step); the Philox counter stays offset + (e >> 3).
+// The replica form (S.replicas > 0: the first conv of an MC-dropout subnet; its output is the same for every run, so the pass writes the
+// runs' masked replicas itself, replica r = image r of the output canvas under the mask pod_expand_dropout draws for it) is the same
+// loop run S.replicas times over a batch's values, e stepping by one image: four Philox chains in flight there too.
+template <bool RELU, bool DROP>
+__device__ __forceinline__ float wino_store_channels_last_form(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
     const int tid = threadIdx.x;
     float lmax = 0.0f;
     const f32x4 inv = f32x4{S.inv, S.inv, S.inv, S.inv};
     const int k8 = (tid & 7) * 8, kg = ks * 64 + k8, ox = (tid >> 3) & 15, odd = tid >> 7;
+    const float sg1 = odd ? -1.0f : 1.0f;
+    const f32x4 sg = f32x4{sg1, sg1, sg1, sg1};
     f32x4 bias0 = f32x4{0.f, 0.f, 0.f, 0.f}, bias1 = bias0;
     if (S.bias) {
         bias0 = *reinterpret_cast<const f32x4*>(S.bias + kg);
         bias1 = *reinterpret_cast<const f32x4*>(S.bias + kg + 4);
     }
-    const uint64_t drop_key = P.thresh ? dropout_key(P.seed, P.epoch) : 0ull;
-    int n;
+    const uint64_t drop_key = DROP ? dropout_key(P.seed, P.epoch) : 0ull;
+    const int n_rep = S.replicas > 0 ? S.replicas : 1;                           // (0: an ordinary launch; 1: one "replica" under the replicas' mask)
+    const uint32_t word = S.replicas > 0 ? 2u : 0u;
+    int n, m;
     const int gx = wino_cell(B.x0 + ox, B.Wv, B.rWv, n);
     const bool col_ok = n < B.gcols && gx < B.W;
-    int m, gy = wino_cell(B.y0 + odd, B.Hv, B.rHv, m) - 2;                       // canvas row y0 + 2 it + odd: grid row m, image row gy (H: the separator)
+    int gy = wino_cell(B.y0 + odd, B.Hv, B.rHv, m);                              // grid row m, image row gy (H: the separator)
+    int img = m * B.gcols + n;
+    const int64_t e_row = (int64_t)(2 * B.W) * P.out_stride, e_wrap = ((int64_t)B.gcols * B.HWi - (int64_t)B.Hv * B.W) * P.out_stride, e_rep = (int64_t)B.HWi * P.out_stride;
+    int64_t e = (B.out_px + (int64_t)img * B.HWi + (int64_t)gy * B.W + gx) * P.out_stride + kg - e_row;      // a multiple of 8; one row up: every row steps first
+    gy -= 2;
     const float* rbase = lds + (ox >> 2) * WINO_TS + (ox & 3) * 64 + k8 + (odd ? WINO_ZA : 0);      // Z[a][tile][ox & 3][k8] of row a = odd
-    // Rows in BATCHES of four: the 24 LDS reads of a batch are issued together (one round trip, not four behind four branches), then
-    // the four rows' arithmetic, Philox calls and stores run as independent chains (round 5: 12.6 k -> cycles of the workgroup's 81 k)
+    // Rows in BATCHES of four: the 24 LDS reads of a batch are issued together (one round trip), then the four rows' arithmetic and
+    // Philox calls run as independent, interleaved chains; the values are pinned in front of the stores, so that nothing but the
+    // stores sits under a row's exec mask.
 #pragma unroll 1
     for (int g = 0; g < 2; ++g) {
-        f32x4 z[4][6];
-        int gyi[4], imgi[4];
+        f32x4 z[4][6], v[4][2];
+        bool ok[4];
+        int64_t er[4];
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             gy += 2;
-            if (gy >= B.Hv) {
-                gy -= B.Hv;
-                ++m;
-            }
-            gyi[it] = gy;
-            imgi[it] = m * B.gcols + n;
+            const bool wrap = gy >= B.Hv;
+            gy -= wrap ? B.Hv : 0;
+            img += wrap ? B.gcols : 0;
+            e += e_row + (wrap ? e_wrap : 0);
+            ok[it] = col_ok && gy < B.H && img < B.n_img;
+            er[it] = e;
             const float* r = rbase + (4 * g + it) * 4 * WINO_TS;                          // tile (4 g + it, ox >> 2)
             z[it][0] = *reinterpret_cast<const f32x4*>(r); z[it][1] = *reinterpret_cast<const f32x4*>(r + 4);
             z[it][2] = *reinterpret_cast<const f32x4*>(r + WINO_ZA); z[it][3] = *reinterpret_cast<const f32x4*>(r + WINO_ZA + 4);
             z[it][4] = *reinterpret_cast<const f32x4*>(r + 2 * WINO_ZA); z[it][5] = *reinterpret_cast<const f32x4*>(r + 2 * WINO_ZA + 4);
         }
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int gy_ = gyi[it], img = imgi[it];
-            if (!col_ok || gy_ >= B.H || img >= B.n_img) continue;
-            f32x4 v0 = __builtin_elementwise_fma(odd ? (z[it][0] - z[it][2]) - z[it][4] : (z[it][0] + z[it][2]) + z[it][4], inv, bias0);
-            f32x4 v1 = __builtin_elementwise_fma(odd ? (z[it][1] - z[it][3]) - z[it][5] : (z[it][1] + z[it][3]) + z[it][5], inv, bias1);
-            if (P.relu) {
-                wino_relu4(v0);
-                wino_relu4(v1);
+        for (int it = 0; it < 4; ++it) {                                 // even rows (Z0 + Z1) + Z2, odd rows (Z1 - Z2) - Z3
+            v[it][0] = __builtin_elementwise_fma(__builtin_elementwise_fma(sg, z[it][4], __builtin_elementwise_fma(sg, z[it][2], z[it][0])), inv, bias0);
+            v[it][1] = __builtin_elementwise_fma(__builtin_elementwise_fma(sg, z[it][5], __builtin_elementwise_fma(sg, z[it][3], z[it][1])), inv, bias1);
+            if (RELU) {
+                wino_relu4(v[it][0]);
+                wino_relu4(v[it][1]);
             }
-            int64_t e = (B.out_px + (int64_t)img * B.HWi + (int64_t)gy_ * B.W + gx) * P.out_stride + kg;      // a multiple of 8
-            if (S.out_amax) {                                        // (a masked value is 0 or v * scale: v * scale bounds both, whatever the masks)
-                const f32x4 a0v = __builtin_elementwise_abs(v0), a1v = __builtin_elementwise_abs(v1);
-                const float mx = fmaxf(fmaxf(fmaxf(a0v.x, a0v.y), fmaxf(a0v.z, a0v.w)), fmaxf(fmaxf(a1v.x, a1v.y), fmaxf(a1v.z, a1v.w)));
-                lmax = fmaxf(lmax, P.thresh ? mx * P.scale : mx);
+            // (a masked value is 0 or v * scale: v * scale bounds both, whatever the masks)
+            // (computed whether or not the launch keeps a record -- a dozen instructions per row, no form of its own: K11, which has no
+            // record, never uses the result and the compiler drops it there; K12 publishes it only when S.out_amax is set)
+            const float mx = wino_absmax4(wino_absmax4(0.0f, v[it][0]), v[it][1]);
+            lmax = fmaxf(lmax, ok[it] ? (DROP ? mx * P.scale : mx) : 0.0f);
+        }
+#pragma unroll 1
+        for (int rep = 0; rep < n_rep; ++rep) {
+            f32x4 w[4][2];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                w[it][0] = v[it][0];
+                w[it][1] = v[it][1];
+                if (DROP && !(POD_WINO_ELIM & 64)) wino_dropout8(w[it][0], w[it][1], er[it], S.offset, word, drop_key, P.thresh, P.scale);
             }
-            if (S.replicas > 0) {                                    // (0: an ordinary launch; 1: one "replica" under the replicas' mask)
-                // The first conv of an MC-dropout subnet: its output is the same for every run, so the store pass writes the runs'
-                // masked replicas itself (replica r = image r of the output canvas) -- the separate expand pass read this tensor back
-                // and wrote them in a launch of its own.
-                for (int rep = 0; rep < S.replicas; ++rep, e += (int64_t)B.HWi * P.out_stride) {
-                    f32x4 w0 = v0, w1 = v1;
-                    if (P.thresh) wino_dropout8(w0, w1, e, S.offset, 2u, drop_key, P.thresh, P.scale);
-                    *reinterpret_cast<f32x4*>(S.out + e) = w0;
-                    *reinterpret_cast<f32x4*>(S.out + e + 4) = w1;
+#pragma unroll
+            for (int it = 0; it < 4; ++it) wino_pin(w[it][0], w[it][1]);
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                if (ok[it]) {
+                    *reinterpret_cast<f32x4*>(S.out + er[it]) = w[it][0];
+                    *reinterpret_cast<f32x4*>(S.out + er[it] + 4) = w[it][1];
                 }
-                continue;
+                er[it] += e_rep;
             }
-            if (P.thresh && !(POD_WINO_ELIM & 64)) wino_dropout8(v0, v1, e, S.offset, 0u, drop_key, P.thresh, P.scale);
-            *reinterpret_cast<f32x4*>(S.out + e) = v0;
-            *reinterpret_cast<f32x4*>(S.out + e + 4) = v1;
         }
     }
     return lmax;
+}
+__device__ __forceinline__ float wino_store_channels_last(const WinoParams& P, const WinoBlock& B, const WinoStore& S, const float* lds, int ks) {
+    switch ((P.relu ? 1 : 0) | (P.thresh ? 2 : 0)) {
+        case 0: return wino_store_channels_last_form<false, false>(P, B, S, lds, ks);
+        case 1: return wino_store_channels_last_form<true, false>(P, B, S, lds, ks);
+        case 2: return wino_store_channels_last_form<false, true>(P, B, S, lds, ks);
+        default: return wino_store_channels_last_form<true, true>(P, B, S, lds, ks);
+    }
 }
 
 }  // namespace pod
