@@ -362,8 +362,10 @@ int pod_wino_conv3x3(const float* in, float* out, const float* U, const float* b
  * enough (a looser bound costs low-order bits of tiny values only; a bound BELOW the true maximum overflows f16: the outputs are inf /
  * nan, never silently wrong).  Producers publish it: every pod_* convolution takes `out_amax` (NULL, or a device record it max'es
  * atomically with |every value it stores| -- the caller zeroes the record before the launch); pod_absmax computes it for any other tensor
- * (the same max'ing: zero the record first; x may itself be a record: that is how two bounds are joined).  Non-finite values are ignored by the max (they make the consumer's products inf / nan as
- * they would in fp32). */
+ * (the same max'ing: zero the record first; x may itself be a record: that is how two bounds are joined).  A NaN is ignored by the max
+ * (its products are nan in the consumer as they would be in fp32).  An inf is NOT: it enters the record as written, by pod_absmax and
+ * by every producer alike, and the consumer then takes the smallest scale it has -- the products of the inf are inf / nan as they would
+ * be in fp32, and the finite values of that tensor fall below f16's smallest number and are read as 0.0 by that launch. */
 #define POD_AMAX_SLOTS 16
 #define POD_AMAX_STRIDE 32
 #define POD_AMAX_FLOATS (POD_AMAX_SLOTS * POD_AMAX_STRIDE)
