@@ -674,6 +674,52 @@ int pod_resize_frame_u8(const uint8_t* src, int32_t in_h, int32_t in_w, int64_t 
                         int32_t xk, const int32_t* ybounds, const int32_t* ycoeffs, int32_t yk, uint8_t* dst, int32_t out_h, int32_t out_w,
                         int32_t flip_channels, pod_stream_t stream);
 
+/* ---- K21  training objective (csrc/k21_train_loss.hip) ----------------------------------------------
+ * Replaces: the anchor labelling probabilistic_retinanet.py:129-130 calls (detectron2 RetinaNet.label_anchors with
+ * Matcher(IOU_THRESHOLDS, [0, -1, 1], allow_low_quality_matches=True)) and ProbabilisticRetinaNet.losses, PR:168-333, evaluated at the
+ * four head outputs together with their gradients.  No convolution has a backward pass: the gradients stop at the head outputs.
+ * Three new symbols and one new structure under POD_ABI_VERSION 18, as for K20: no entry or structure that existed changed, so the number stands.
+ *
+ * pod_label_anchors: replaces PR:129-130.  anchors dev (R, 4) level-concatenated XYXY; images are concatenated as in pod_match_groundtruth:
+ *   image i owns the boxes [gt_off[i], gt_off[i + 1]) of gt_boxes dev (n_gt, 4) XYXY / gt_classes dev int32[n_gt]; gt_off dev int32[n_images + 1].
+ *   IoU = inter / ((area_gt + area_anchor) - inter) if inter > 0 else 0 (detectron2 pairwise_iou, fp32, that operation order: the labels
+ *   equal a torch evaluation bit for bit).  Per anchor v = max over the image's boxes, m = the first arg-max; match = 1 if v >= iou_high,
+ *   -1 if iou_low <= v < iou_high, else 0; then every anchor whose IoU with a box EQUALS that box's best IoU over all anchors gets match 1
+ *   (literally, also when the best is 0; its m stays).  labels dev int32 (n_images, R): gt_classes[m] | num_classes (background) | -1
+ *   (ignored); matched_gt dev int32 (n_images, R): m as a row of gt_boxes (-1 for an image without boxes, whose labels are all
+ *   num_classes); num_pos dev int32[n_images]: labels in [0, num_classes).  scratch: dev, n_gt 4-byte words (the boxes' best IoUs, taken
+ *   with an unsigned atomic max on the float's bits: IoU >= 0, a max is order-independent). */
+int pod_label_anchors(const float* anchors, int32_t R, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_off,
+                      int32_t n_images, int32_t n_gt, int32_t num_classes, float iou_low, float iou_high, int32_t* labels,
+                      int32_t* matched_gt, int32_t* num_pos, uint32_t* scratch, pod_stream_t stream);
+
+/* pod_train_loss: replaces PR:168-333 (PR:194 get_deltas, PR:223-282 classification, PR:285-331 regression; the normaliser, the annealing
+ *   weight and the division by the sample count, PR:201-203 / 268 / 320-322, are the caller's three weights).
+ *   levels: the head outputs, cfg->n_runs = the IMAGE count and the run strides the image strides; cfg->cov_dims 0 or 4 (10: POD_E_INVALID,
+ *   the reference defines no loss for the full covariance); cfg->num_classes <= 15.  labels / matched_gt dev int32 (n_images, R) as
+ *   pod_label_anchors writes them, gt_boxes dev (n_gt, 4), anchors dev (R, 4), R = the levels' anchors.
+ *   Classification, anchors with label >= 0, one-hot target without the background column: fvcore's sigmoid focal loss
+ *   (p = sigmoid(x), ce = BCE-with-logits, p_t = p t + (1 - p)(1 - t), ce (1 - p_t)^gamma (alpha t + (1 - alpha)(1 - t)); alpha < 0: no
+ *   alpha weight) of the logit, or -- cfg->has_cls_var -- summed over s < cfg->cls_samples at logit + sqrt(exp(logvar)) eps[s] (PR:231-268).
+ *   eps_cls: dev (cls_samples, n_images * R, K) replayed normals, dense by anchor, or NULL: in-kernel Philox4x32-10 draws keyed by
+ *   cfg->philox_seed and (image, anchor, class, sample); eps_out: NULL or a buffer of that shape receiving the normals used (zeros at
+ *   ignored anchors).  Regression, anchors with label in [0, K): d = delta - get_deltas(anchor, gt_boxes[matched_gt]) with
+ *   cfg->box_weights; smooth_l1 = |d| if beta < 1e-5, else 0.5 d^2 / beta below beta, else |d| - 0.5 beta; with cov_dims = 4 also
+ *   0.5 exp(-c) smooth_l1 + 0.5 c, c = clamp(logvar, -7, 7) (PR:295-307).
+ *   sums dev double[4]: classification sum, standard regression sum, NLL regression sum, positives.  fp32 terms accumulated in fp64 through
+ *   per-workgroup partials (partials: dev double[pod_train_loss_partials(cfg, levels)]) added in a fixed order: the same bits every run.
+ *   grads: NULL, or per level the planes (each NULL or laid out and strided exactly as the input of the same name) that receive
+ *   d(w[0] cls_sum + w[1] std_reg_sum + w[2] nll_reg_sum) / d input, w dev float[3]; every element is written, exactly zero where an
+ *   anchor contributes nothing; d clamp = 1 on [-7, 7], 0 outside. */
+typedef struct PodLevelGrad {
+    float* cls;  float* cls_var;  float* delta;  float* reg_var;
+} PodLevelGrad;
+int64_t pod_train_loss_partials(const PodConfig* cfg, const PodLevel* levels);
+int pod_train_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelGrad* grads, const int32_t* labels,
+                   const int32_t* matched_gt, const float* gt_boxes, int32_t n_gt, const float* anchors, int32_t R,
+                   float alpha, float gamma, float smooth_l1_beta, const float* eps_cls, float* eps_out, const float* w,
+                   double* partials, double* sums, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -801,7 +801,8 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
 
 
 class ProbabilisticRetinaNet(_TracksStorage):
-    """PR:20-166 (inference side only; `losses` PR:168-333 is training and out of scope)."""
+    """PR:20-166, and `losses` (PR:168-333 with the labelling of PR:129-130) evaluated on the head outputs of a forward by the K21 kernels
+    (pod_compare_amd/losses.py).  No convolution has a backward pass: the loss gradients exist at the head outputs only."""
 
     def __init__(self, num_classes=7, dropout_rate=0.0, cls_var_loss="none", cls_var_num_samples=3,
                  bbox_cov_loss="none", bbox_cov_type="diagonal", test_score_thresh=0.05, test_topk_candidates=1000,
@@ -855,6 +856,18 @@ class ProbabilisticRetinaNet(_TracksStorage):
             if self.device.type == "cuda":
                 torch.cuda.current_stream(self.device).synchronize()   # made once, then read from any stream
         return self._anchor_cache[padded_hw]
+
+    def losses(self, outputs: HeadOutputs, gt_boxes, gt_classes, eps=None, normalizer=None) -> Dict[str, torch.Tensor]:
+        """PR:129-130 + PR:168-333 on `outputs` (a forward's HeadOutputs; the leading dimension of its tensors is the image): gt_boxes /
+        gt_classes are per-image lists of (G_i, 4) XYXY boxes in network-input pixels and (G_i,) contiguous class ids.  Returns
+        {"loss_cls", "loss_box_reg"} as device scalars.  The state the reference keeps on the model (loss_normalizer, current_step) lives in
+        `self.loss_state` (losses.ProbabilisticLosses); eps / normalizer as in its __call__."""
+        from . import losses as _losses
+        if getattr(self, "loss_state", None) is None:
+            self.loss_state = _losses.ProbabilisticLosses(num_classes=self.num_classes, cls_var_num_samples=self.cls_var_num_samples)
+        labels, matched, _ = _losses.label_anchors(outputs.anchors, gt_boxes, gt_classes, self.num_classes)
+        boxes, _, _ = _losses.concat_ground_truth(gt_boxes, gt_classes, labels.device)
+        return self.loss_state(outputs, labels, matched, boxes, eps=eps, normalizer=normalizer)
 
     # ---- HIP graphs --------------------------------------------------------------------------------------------------------
     # One image's forward is ~200 launches (MIOpen calls, pod_* kernels, torch element-wise ops) issued from Python: 2.3 - 2.5 ms of
