@@ -720,6 +720,31 @@ int pod_train_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelG
                    float alpha, float gamma, float smooth_l1_beta, const float* eps_cls, float* eps_out, const float* w,
                    double* partials, double* sums, pod_stream_t stream);
 
+/* ---- K22  backward of the head's 3x3 convolutions (csrc/k22_conv3x3_wgrad.hip) ----------------------------------------
+ * Serves: the backward pass of the convolutions of ProbabilisticRetinaNetHead (probabilistic_retinanet.py:403-484) under train_net.py's
+ * training loop -- the reference gets it from autograd; here the weight and bias gradients are a kernel, the input gradient is a GEMM
+ * (pod_conv1x1_split) of the gradient's patch matrix with the flipped, transposed filter.  Three new symbols under POD_ABI_VERSION 18, as for K20 / K21: no
+ * entry or structure that existed changed, so the number stands.
+ *
+ * pod_conv3x3_wgrad: x dev (pixels, C) and dy dev (pixels, Kpad), channels-last, the images of a pod_wino_conv3x3 launch: level_hw HOST
+ *   int32 (n_levels, 2) = (H, W) per level, `copies` images per level, level-major.  dW dev fp32 (K, C, 3, 3):
+ *   dW[k][c][ky][kx] = sum over images and pixels of dy[(y, x)][k] x[(y + ky - 1, x + kx - 1)][c], taps outside the image contributing
+ *   zero; db dev fp32 (K): the column sums of dy.  Channels K .. Kpad - 1 of dy are never used and nothing is written for them.
+ *   C % 16 == 0, Kpad % 64 == 0, Kpad <= 512, K <= Kpad.  Every product is formed on the f16 matrix cores from the two-term f16 splits of
+ *   BOTH operands, scaled by the powers of two their abs-max records give (x_amax / dy_amax: operand abs-max words, above), three partial
+ *   products, fp32 accumulate.  The pixel reduction is cut into slices of 256 row segments of 16 pixels, enumerated by the geometry alone
+ *   (level, image, column strip, row); each slice writes partial sums into `partials` (dev, 16-byte aligned,
+ *   pod_conv3x3_wgrad_partials(...) floats; 0 = invalid geometry) and a second launch adds them in slice order in fp64 (db: fp64 column
+ *   sums over chunks of 4096 pixels, added in chunk order): no atomics, two launches give the same bits.
+ * pod_relu_dropout_backward: the gate of conv + bias + ReLU + dropout(p) as pod_wino_conv3x3_split's store pass computes it: the stored
+ *   output is relu(z) keep / (1 - p) with exact zeros where ReLU or the mask killed the element, so d_z = d_out (out > 0) / (1 - p)
+ *   (1.0f / (1.0f - p) in fp32, the forward's factor).  n % 4 == 0; d_z may be d_out; dz_amax: NULL or the zeroed record that receives
+ *   max |d_z|. */
+int64_t pod_conv3x3_wgrad_partials(const int32_t* level_hw, int32_t n_levels, int32_t copies, int32_t C, int32_t K, int32_t Kpad);
+int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t* level_hw, int32_t n_levels, int32_t copies, int32_t C, int32_t K,
+                      int32_t Kpad, const float* x_amax, const float* dy_amax, float* dW, float* db, float* partials, pod_stream_t stream);
+int pod_relu_dropout_backward(const float* out, const float* d_out, float* d_z, int64_t n, float p, float* dz_amax, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -101,7 +101,9 @@ def get_cfg() -> CfgNode:
         "SEED": 0,
         "DATASETS": {"TRAIN": (), "TEST": ()},
         "DATALOADER": {"NUM_WORKERS": 4},
-        "SOLVER": {"IMS_PER_BATCH": 1, "STEPS": (60000, 80000)},
+        # (BASE_LR .. CHECKPOINT_PERIOD: detectron2's defaults, read by train_head)
+        "SOLVER": {"IMS_PER_BATCH": 1, "STEPS": (60000, 80000), "BASE_LR": 0.001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001, "WARMUP_ITERS": 1000,
+                   "WARMUP_FACTOR": 1.0 / 1000, "GAMMA": 0.1, "MAX_ITER": 40000, "CHECKPOINT_PERIOD": 5000},
         "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR"},
         "MODEL": {
             "META_ARCHITECTURE": "ProbabilisticRetinaNet",

@@ -1,0 +1,204 @@
+"""The head with a backward pass: ProbabilisticRetinaNetHead.forward_train (probabilistic_retinanet.py:403-537 in training mode, under
+train_net.py's loop) as ONE torch.autograd.Function over the whole head.
+
+Forward: every trunk layer is one pod_wino_conv3x3_split launch over all levels and all B images (conv + bias + ReLU + dropout in the store
+pass; the cls and the bbox trunk grouped in one grid), the predictors write NCHW planes.  Backward, per layer from the predictors down:
+    the gate         dZ = dOut (out > 0) / (1 - p)       pod_relu_dropout_backward (the stored output is its own mask; trunk layers only)
+    dW, db           pod_conv3x3_wgrad(saved input, dZ)   K22, handed to autograd, which accumulates them into .grad
+    dX               conv3x3(dZ, W'), W'[c][k][ky][kx] = W[k][c][2 - ky][2 - kx], as a GEMM: the patch matrix of dZ (torch) times the split
+                     W' on pod_conv1x1_split (direct sums: the Winograd kernel's transforms round three times as much per layer)
+A predictor's A*K = 63 / 36 gradient channels are zero-padded to 64 (and W' with them): Cin % 16 == 0.  The two predictors
+on a trunk add their dX ahead of the trunk's last gate.  Only the head trains: the features' gradient is computed when they require it,
+and nothing reaches further down.  GPU only -- anything this path cannot take raises (hip.PodError): there is no fallback."""
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import amax, hip, wgrad
+from .synthetic import HeadOutputs
+
+
+def head_convs(head) -> list:
+    """The head's convolutions in the order their parameters enter the autograd function."""
+    return (list(head.cls_subnet) + list(head.bbox_subnet) + [head.cls_score, head.bbox_pred]
+            + [c for c in (head.cls_var, head.bbox_cov) if c is not None])
+
+
+def transposed_weight(weight: torch.Tensor) -> torch.Tensor:
+    """W (K, C, 3, 3) -> W' (C, Kpad, 3, 3), W'[c][k][ky][kx] = W[k][c][2 - ky][2 - kx], K zero-padded to a multiple of 64:
+    conv3x3(dZ, W') is the input gradient of conv3x3(., W)."""
+    K, C = int(weight.shape[0]), int(weight.shape[1])
+    wt = torch.zeros((C, (K + 63) // 64 * 64, 3, 3), dtype=weight.dtype, device=weight.device)
+    wt[:, :K] = weight.detach().flip(2, 3).transpose(0, 1)
+    return wt
+
+
+def input_grad_gemm(conv):
+    """The conv's input gradient as a GEMM: W' laid out (C, ty, tx, Kpad) and split once for pod_conv1x1_split (conv1x1.Conv3x3S2's form,
+    stride 1), cached by the weight's version as modeling.wino_of caches the forward filter."""
+    from . import modeling
+    from .conv1x1 import Conv1x1
+
+    def make(c):
+        wt = transposed_weight(c.weight)
+        try:
+            return Conv1x1(wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1).contiguous(), None, 1)
+        except ValueError as e:
+            raise hip.PodError("head backward: the input gradient of a {} -> {} conv has no pod_conv1x1_split form ({})".format(
+                c.in_channels, c.out_channels, e))
+    return modeling._derived(conv, "_pod_dx_gemm", make)
+
+
+def patch_matrix(dz: torch.Tensor, levels, B: int) -> torch.Tensor:
+    """(pixels, K) channels-last, level-major -> (pixels, 9 K): row (y, x) = the K-vectors of the nine taps in (ty, tx) order, zeros where a
+    tap leaves its image (data movement only, plain torch; the record of dz bounds it)."""
+    K = int(dz.shape[1])
+    cols = torch.empty((int(dz.shape[0]), 9 * K), dtype=dz.dtype, device=dz.device)
+    off = 0
+    for h, w in levels:
+        n = B * h * w
+        v = torch.nn.functional.pad(dz[off:off + n].view(B, h, w, K), (0, 0, 1, 1, 1, 1))
+        torch.cat([v[:, ty:ty + h, tx:tx + w] for ty in range(3) for tx in range(3)], dim=3, out=cols[off:off + n].view(B, h, w, 9 * K))
+        off += n
+    return amax.attach(cols, amax.of(dz))
+
+
+def _planes_to_padded_cl(g: Optional[torch.Tensor], levels, B: int, K: int, device) -> torch.Tensor:
+    """Gradient planes of one predictor -- flat, per level (B, K, H, W), level-major -- as the zero-padded channels-last (pixels, Kpad)."""
+    Kpad, pixels = (K + 63) // 64 * 64, B * sum(h * w for h, w in levels)
+    out = torch.zeros((pixels, Kpad), dtype=torch.float32, device=device)
+    if g is None:
+        return out
+    off = 0
+    for h, w in levels:
+        n = B * h * w
+        out[off:off + n, :K] = g[off * K:(off + n) * K].view(B, K, h, w).permute(0, 2, 3, 1).reshape(n, K)
+        off += n
+    return out
+
+
+class _HeadTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, levels, B, x0, *params):
+        from . import modeling
+        from .wino import block_table, grouped_launch, level_pixel_offsets
+        dev, C, L = x0.device, int(x0.shape[1]), len(head.cls_subnet)
+        p = float(head.dropout_rate)
+        replay = p > 0.0 and head.dropout_replay is not None
+        x0 = x0.detach()
+        pixels = B * sum(h * w for h, w in levels)
+        offs = level_pixel_offsets(levels, B)
+        table = block_table(levels, B, dev, channels=max(C, 64))
+        winos = [modeling.wino_of(c) for c in head_convs(head)]
+        if not all(w.split for w in winos):
+            raise hip.PodError("head.forward_train needs the split Winograd kernel for every conv of the head (C % 16 == 0, POD_WINO_SPLIT=1)")
+        kw = {"relu": True, "dropout_p": 0.0 if replay else p, "seed": head.dropout_seed, "epoch": head._epoch}
+        base = head._drop_calls               # a fresh Philox offset per launch and trunk, as `_trunks` draws them
+        head._drop_calls += 2 * L
+        src, saved = [x0, x0], [[], []]       # saved[sid][l] = (input, output) of trunk layer l
+        for l in range(L):
+            sets = []
+            for sid, sub in enumerate((head.cls_subnet, head.bbox_subnet)):
+                dst = torch.empty((pixels, C), dtype=torch.float32, device=dev)
+                sets.append({"conv": modeling.wino_of(sub[l]), "src": src[sid], "dst": dst, "table": table, "offset": (base + sid * L + l + 1) << 34})
+            grouped_launch(sets, **kw)
+            for sid in range(2):
+                dst = sets[sid]["dst"]
+                if replay:                    # parity mode: the recorded masks, multiplied in with torch; the backward only reads the result
+                    for lv, (h, w) in enumerate(levels):
+                        v = dst[offs[lv]:offs[lv + 1]].view(B, h, w, C)
+                        v.copy_(head._replayed(v.permute(0, 3, 1, 2), sid, l, lv).permute(0, 2, 3, 1))
+                    amax.forget(dst)
+                saved[sid].append((src[sid], dst))
+                src[sid] = dst
+        preds = [(head.cls_score, 0), (head.bbox_pred, 1)] + ([(head.cls_var, 0)] if head.cls_var is not None else []) + \
+                ([(head.bbox_cov, 1)] if head.bbox_cov is not None else [])
+        sets = [{"conv": modeling.wino_of(conv), "src": src[sid], "dst": torch.empty(pixels * conv.out_channels, dtype=torch.float32, device=dev),
+                 "planes": True, "table": table} for conv, sid in preds]
+        if len({s["conv"].Kpad for s in sets}) == 1:
+            grouped_launch(sets)
+        else:
+            for s in sets:
+                s["conv"](s["src"], s["dst"], s["table"], planes=True)
+        tap = getattr(head, "train_tap", None)          # tests: a dict that receives the saved activations (and the gates' outputs)
+        if tap is not None:
+            tap["saved"], tap["dz"] = saved, {}
+        ctx.state = (head, list(levels), int(B), x0, saved, preds, src)
+        ctx.n_params = len(params)
+        return tuple(s["dst"] for s in sets)
+
+    @staticmethod
+    def backward(ctx, *g_planes):
+        head, levels, B, x0, saved, preds, last = ctx.state
+        dev, C, L = x0.device, int(x0.shape[1]), len(head.cls_subnet)
+        pixels = int(x0.shape[0])
+        grads = {}                                             # conv -> (dW, db)
+        need_x = ctx.needs_input_grad[3]
+
+        def input_grad(conv, dz):
+            return input_grad_gemm(conv)(patch_matrix(dz, levels, B), pixels, 1)
+
+        d_trunk = [None, None]
+        for (conv, sid), g in zip(preds, g_planes):
+            dy = _planes_to_padded_cl(None if g is None else g.contiguous(), levels, B, conv.out_channels, dev)
+            grads[conv] = wgrad.conv3x3_wgrad(last[sid], dy, levels, B, conv.out_channels)
+            dx = input_grad(conv, dy)
+            d_trunk[sid] = dx if d_trunk[sid] is None else d_trunk[sid] + dx
+        dx0 = None
+        for sid, sub in enumerate((head.cls_subnet, head.bbox_subnet)):
+            d = d_trunk[sid]
+            for l in range(L - 1, -1, -1):
+                x_in, out = saved[sid][l]
+                dz = wgrad.relu_dropout_backward(out, d, head.dropout_rate)          # in place; publishes dZ's abs-max record
+                grads[sub[l]] = wgrad.conv3x3_wgrad(x_in, dz, levels, B, sub[l].out_channels)
+                if getattr(head, "train_tap", None) is not None:
+                    head.train_tap["dz"][(sid, l)] = dz
+                if l or need_x:
+                    d = input_grad(sub[l], dz)
+            if need_x:
+                dx0 = d if dx0 is None else dx0 + d
+        flat = []
+        for conv in head_convs(head):
+            flat += list(grads[conv])
+        assert len(flat) == ctx.n_params
+        ctx.state = None
+        return (None, None, None, dx0) + tuple(flat)
+
+
+def forward_train(head, features: Sequence[torch.Tensor], anchors: Optional[List[torch.Tensor]] = None, image_size=None) -> HeadOutputs:
+    """features: per-level (B, C, H, W), B images of one padded size.  Returns HeadOutputs whose leading dimension is the image (what
+    losses.ProbabilisticLosses expects); its tensors carry a grad_fn that reaches every parameter of the head and, where they require
+    it, the features."""
+    f0 = features[0]
+    if not (f0.is_cuda and f0.dtype == torch.float32):
+        raise hip.PodError("head.forward_train runs on the GPU in fp32 only (got {} on {}): there is no CPU path".format(f0.dtype, f0.device))
+    B, C = int(f0.shape[0]), int(f0.shape[1])
+    convs = head_convs(head)
+    if C != head.cls_subnet[0].in_channels or C % 16 or C not in (64, 128, 256, 512) or any(c.bias is None for c in convs):
+        raise hip.PodError("head.forward_train: {} input channels (conv {} -> {}) have no pod_wino_conv3x3_split form for both directions "
+                           "(64, 128, 256 or 512 channels, biased convs)".format(C, head.cls_subnet[0].in_channels, head.cls_subnet[0].out_channels))
+    levels = [(int(f.shape[2]), int(f.shape[3])) for f in features]
+    if any(int(f.shape[0]) != B or int(f.shape[1]) != C or f.device != f0.device for f in features):
+        raise hip.PodError("head.forward_train: every level holds the same images and channels")
+    x0 = torch.cat([f.permute(0, 2, 3, 1).reshape(-1, C) for f in features]).contiguous()      # channels-last, level-major (autograd sees it)
+    params = []
+    for c in convs:
+        params += [c.weight, c.bias]
+    flats = _HeadTrain.apply(head, levels, B, x0, *params)
+    A = head.num_anchors
+
+    def per_level(flat, K):
+        out, off = [], 0
+        for h, w in levels:
+            n = B * h * w * K
+            out.append(flat[off:off + n].view(B, K, h, w))
+            off += n
+        return out
+
+    it = iter(flats)
+    cls, delta = per_level(next(it), head.cls_score.out_channels), per_level(next(it), head.bbox_pred.out_channels)
+    cls_var = per_level(next(it), head.cls_var.out_channels) if head.cls_var is not None else None
+    reg_var = per_level(next(it), head.bbox_cov.out_channels) if head.bbox_cov is not None else None
+    h0, w0 = levels[0]
+    return HeadOutputs(cls, delta, cls_var, reg_var, list(anchors) if anchors is not None else [], levels, A, head.num_classes,
+                       tuple(image_size) if image_size is not None else (h0 * 8, w0 * 8))

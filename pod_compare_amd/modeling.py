@@ -751,6 +751,13 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         res = self._expanded(self._predict(self._jobs(1, tb, st), st, live=live, bufs=bufs), st)
         return res[0], (res[1] if self.compute_bbox_cov else None)
 
+    def forward_train(self, features: List[torch.Tensor], anchors=None, image_size=None) -> HeadOutputs:
+        """The training forward (PR:403-537 with dropout after every trunk conv, one evaluation per image): features per level
+        (B, C, H, W), B images of one padded size -> HeadOutputs whose leading dimension is the image and whose tensors carry a grad_fn
+        (pod_compare_amd/head_train.py: the HIP backward of the head's convolutions).  GPU only."""
+        from .head_train import forward_train
+        return forward_train(self, features, anchors, image_size)
+
     def forward(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False):
         """features: per-level (1, 256, H, W).  Returns per-level lists of (num_runs, A*C, H, W).
 
@@ -802,7 +809,8 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
 
 class ProbabilisticRetinaNet(_TracksStorage):
     """PR:20-166, and `losses` (PR:168-333 with the labelling of PR:129-130) evaluated on the head outputs of a forward by the K21 kernels
-    (pod_compare_amd/losses.py).  No convolution has a backward pass: the loss gradients exist at the head outputs only."""
+    (pod_compare_amd/losses.py).  The head's convolutions have a backward pass (head.forward_train, pod_compare_amd/head_train.py); the
+    backbone's and the FPN's have none: they stay frozen."""
 
     def __init__(self, num_classes=7, dropout_rate=0.0, cls_var_loss="none", cls_var_num_samples=3,
                  bbox_cov_loss="none", bbox_cov_type="diagonal", test_score_thresh=0.05, test_topk_candidates=1000,

@@ -33,13 +33,13 @@ from .structures import Boxes, Instances
 from .synthetic import HeadOutputs
 
 
-def build_model(cfg, save_dir: Optional[str] = "", load_weights: bool = True) -> modeling.ProbabilisticRetinaNet:
+def build_model(cfg, save_dir: Optional[str] = "", load_weights: bool = True, fold: bool = True) -> modeling.ProbabilisticRetinaNet:
     """detectron2 `build_model(cfg)` for META_ARCHITECTURE == ProbabilisticRetinaNet (PR:25-65), followed by the
     reference's `DetectionCheckpointer(model, save_dir).resume_or_load(cfg.MODEL.WEIGHTS, resume=True)` (PI:59-84):
     `<save_dir>/last_checkpoint` wins over cfg.MODEL.WEIGHTS, an empty path keeps the random initialisation, a path
     that cannot be read raises (checkpoint.CheckpointError) -- never a silent random-init run.  save_dir "" means
     cfg.OUTPUT_DIR, None means "no directory" (only cfg.MODEL.WEIGHTS is considered).  FrozenBN is folded into the conv
-    weights AFTER loading."""
+    weights AFTER loading (fold=False keeps the (conv, FrozenBN) pairs: the form checkpoint.to_detectron2_state_dict writes)."""
     pm = cfg.MODEL.PROBABILISTIC_MODELING
     model = modeling.ProbabilisticRetinaNet(
         num_classes=cfg.MODEL.RETINANET.NUM_CLASSES, dropout_rate=pm.DROPOUT_RATE, cls_var_loss=pm.CLS_VAR_LOSS.NAME,
@@ -54,7 +54,8 @@ def build_model(cfg, save_dir: Optional[str] = "", load_weights: bool = True) ->
             save_dir = cfg.get("OUTPUT_DIR", None)
         model.loaded_from = checkpoint.load_model_weights(model, save_dir, cfg.MODEL.get("WEIGHTS", ""))
     model = model.to(torch.device(cfg.MODEL.DEVICE)).eval()
-    modeling.fold_frozen_bn(model)      # inference-only algebra: the same affine map, one biased conv per (conv, FrozenBN) pair
+    if fold:
+        modeling.fold_frozen_bn(model)  # inference-only algebra: the same affine map, one biased conv per (conv, FrozenBN) pair
     return model
 
 
