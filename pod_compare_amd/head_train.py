@@ -1,8 +1,8 @@
 """The head with a backward pass: ProbabilisticRetinaNetHead.forward_train (probabilistic_retinanet.py:403-537 in training mode, under
 train_net.py's loop) as ONE torch.autograd.Function over the whole head.
 
-Forward: every trunk layer is one pod_wino_conv3x3_split launch over all levels and all B images (conv + bias + ReLU + dropout in the store
-pass; the cls and the bbox trunk grouped in one grid), the predictors write NCHW planes.  Backward, per layer from the predictors down:
+Forward: the training form of the launch plan the inference head runs (modeling.ProbabilisticRetinaNetHead._trunk_plan, `_predict`), all
+B images in every launch.  Backward, per layer from the predictors down:
     the gate         dZ = dOut (out > 0) / (1 - p)       pod_relu_dropout_backward (the stored output is its own mask; trunk layers only)
     dW, db           pod_conv3x3_wgrad(saved input, dZ)   K22, handed to autograd, which accumulates them into .grad
     dX               conv3x3(dZ, W'), W'[c][k][ky][kx] = W[k][c][2 - ky][2 - kx], as a GEMM: the patch matrix of dZ (torch) times the split
@@ -81,51 +81,22 @@ class _HeadTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, levels, B, x0, *params):
         from . import modeling
-        from .wino import block_table, grouped_launch, level_pixel_offsets
-        dev, C, L = x0.device, int(x0.shape[1]), len(head.cls_subnet)
-        p = float(head.dropout_rate)
-        replay = p > 0.0 and head.dropout_replay is not None
-        x0 = x0.detach()
-        pixels = B * sum(h * w for h, w in levels)
-        offs = level_pixel_offsets(levels, B)
-        table = block_table(levels, B, dev, channels=max(C, 64))
-        winos = [modeling.wino_of(c) for c in head_convs(head)]
-        if not all(w.split for w in winos):
+        if not all(modeling.wino_of(c).split for c in head_convs(head)):
             raise hip.PodError("head.forward_train needs the split Winograd kernel for every conv of the head (C % 16 == 0, POD_WINO_SPLIT=1)")
-        kw = {"relu": True, "dropout_p": 0.0 if replay else p, "seed": head.dropout_seed, "epoch": head._epoch}
-        base = head._drop_calls               # a fresh Philox offset per launch and trunk, as `_trunks` draws them
-        head._drop_calls += 2 * L
-        src, saved = [x0, x0], [[], []]       # saved[sid][l] = (input, output) of trunk layer l
-        for l in range(L):
-            sets = []
-            for sid, sub in enumerate((head.cls_subnet, head.bbox_subnet)):
-                dst = torch.empty((pixels, C), dtype=torch.float32, device=dev)
-                sets.append({"conv": modeling.wino_of(sub[l]), "src": src[sid], "dst": dst, "table": table, "offset": (base + sid * L + l + 1) << 34})
-            grouped_launch(sets, **kw)
-            for sid in range(2):
-                dst = sets[sid]["dst"]
-                if replay:                    # parity mode: the recorded masks, multiplied in with torch; the backward only reads the result
-                    for lv, (h, w) in enumerate(levels):
-                        v = dst[offs[lv]:offs[lv + 1]].view(B, h, w, C)
-                        v.copy_(head._replayed(v.permute(0, 3, 1, 2), sid, l, lv).permute(0, 2, 3, 1))
-                    amax.forget(dst)
-                saved[sid].append((src[sid], dst))
-                src[sid] = dst
+        x0 = x0.detach()
+        # the training form of the head's launch plan (modeling._trunk_plan): B images per level, every layer's output kept
+        st = {"x0": x0, "levels": list(levels), "dropout": False, "grouped": True, "images": int(B), "channels": max(int(x0.shape[1]), 64)}
+        last = [buf for buf, _ in head._trunks([(0, B), (1, B)], st)]
+        saved = st["saved"]                             # saved[sid][l] = (input, output) of trunk layer l
         preds = [(head.cls_score, 0), (head.bbox_pred, 1)] + ([(head.cls_var, 0)] if head.cls_var is not None else []) + \
                 ([(head.bbox_cov, 1)] if head.bbox_cov is not None else [])
-        sets = [{"conv": modeling.wino_of(conv), "src": src[sid], "dst": torch.empty(pixels * conv.out_channels, dtype=torch.float32, device=dev),
-                 "planes": True, "table": table} for conv, sid in preds]
-        if len({s["conv"].Kpad for s in sets}) == 1:
-            grouped_launch(sets)
-        else:
-            for s in sets:
-                s["conv"](s["src"], s["dst"], s["table"], planes=True)
+        planes = head._predict([(conv, last[sid], B, 0, B, B) for conv, sid in preds], st, flat=True)
         tap = getattr(head, "train_tap", None)          # tests: a dict that receives the saved activations (and the gates' outputs)
         if tap is not None:
             tap["saved"], tap["dz"] = saved, {}
-        ctx.state = (head, list(levels), int(B), x0, saved, preds, src)
+        ctx.state = (head, list(levels), int(B), x0, saved, preds, last)
         ctx.n_params = len(params)
-        return tuple(s["dst"] for s in sets)
+        return tuple(planes)
 
     @staticmethod
     def backward(ctx, *g_planes):

@@ -572,69 +572,87 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         return (GROUPED_HEAD and all(1 <= c <= 127 for c in copies)
                 and all(self._wino(c).split for c in list(self.cls_subnet) + list(self.bbox_subnet)))
 
-    def _trunks(self, subnets, st: dict, live=None, bufs=None):
-        """Subnet evaluations on ALL levels, subnets: [(0 = cls / 1 = bbox, copies)].  One pod_wino_conv3x3 launch per conv layer (fp32
-        Winograd on the matrix cores, bias + ReLU + dropout in its store) instead of one MIOpen call + one element-wise pass per level and
-        layer; with st["grouped"] layer l of all the subnets in ONE launch (the kernel runs one workgroup per CU, so a launch costs whole
-        rounds of 256 workgroups: two launches of 1.5 rounds cost 4, one of 3.0 costs 3) -- the same buffers, tables, Philox offsets and
-        therefore the same bits as one launch per subnet.  st: `_plan`'s, x0 = the features as (pixels of all levels, C) channels-last,
-        level after level.  Returns per subnet (buffer, images per level): the last activation as (pixels of all levels x images, C)
-        channels-last, level after level -- `copies` images per level with dropout, one without (every copy would be identical).
-        live (sparse bbox tower, pod_compare_amd/sparse.py): a LiveBlocks -- layer j is launched over the blocks of reach L - j only;
-        bufs: `new(key, shape)` handing out the tower's re-used buffers (only live blocks are written; what dead blocks hold is never read)."""
-        from . import hip
-        from .sparse import DENSE_INPUT, reach_of_subnet_layer
-        from .wino import block_table, grouped_launch, level_pixel_offsets
-        x0, levels, dropout, grouped = st["x0"], st["levels"], st["dropout"], st["grouped"]
-        L, C, dev = len(self.cls_subnet), x0.shape[1], x0.device
-        assert live is None or grouped, "the sparse tower needs the split kernel's grouped launches"
-        copies = [c if dropout else 1 for _, c in subnets]
-        offn = [level_pixel_offsets(levels, c) for c in copies]
+    def _trunk_plan(self, subnets, st: dict, bufs=None) -> dict:
+        """The bookkeeping of the trunks' launches, subnets: [(0 = cls / 1 = bbox, copies)]; touches the device for buffers and
+        `block_table`s only.  st: `_plan`'s, x0 = the features as (pixels of all levels, C) channels-last, level after level, in two forms.
+        Inference: ONE image per level.  With st["dropout"] (MC dropout) a subnet is evaluated `copies` times -- its first activation,
+        identical for every copy, is computed once and stored `copies` times under the copies' masks (`firsts` tables, "replicas") -- and
+        a subnet's layers ping-pong between two buffers (bufs: `new(key, shape)`, the sparse tower's re-used ones); without, one evaluation
+        and no mask arguments.  Training (st["images"] = B, head_train.py): B images per level, evaluated once by every subnet, every layer
+        writes a buffer of its own (the backward reads them), and masks are keyed at p = 0 too.  st["channels"] bounds the tables' canvases.
+        Masked, subnet i's layer l draws the Philox offset base + i L + l + 1, ONE for the whole buffer: an element's mask is keyed by its
+        index in it.  -> layers: per layer the `sets` of wino.grouped_launch ("conv" still the nn.Conv2d, `_launch` looks its WinoConv up);
+        kw: their common arguments; copies: images per level in each subnet's buffers; replay: recorded masks stand in for Philox's."""
+        from . import wino
+        x0, levels, B = st["x0"], st["levels"], st.get("images")
+        L, C, dev, ch = len(self.cls_subnet), x0.shape[1], x0.device, st.get("channels", 512)
+        replicas, masked = st["dropout"] and not B, bool(st["dropout"] or B)
+        copies = [B or (c if replicas else 1) for _, c in subnets]
         new = bufs or (lambda key, shape: torch.empty(shape, dtype=x0.dtype, device=dev))
-        a = [new("a%d" % i, (offs[-1], C)) for i, offs in enumerate(offn)]
-        b = [new("b%d" % i, (offs[-1], C)) for i, offs in enumerate(offn)]
-        tables = [block_table(levels, c, dev) for c in copies]
-        # With dropout the first activation is identical for every copy: computed once, stored `copies` times under the copies' dropout
-        # masks.  One Philox offset for the whole buffer: the mask of an element is keyed by its index in it.
-        firsts = [block_table(levels, 1, dev, out_copies=c) for c in copies] if dropout else tables
-        replay = dropout and self.dropout_replay is not None
+        dsts = [[new("t%d_%d" % (i, j), (wino.level_pixel_offsets(levels, c)[-1], C)) for j in range(L if B else 2)] for i, c in enumerate(copies)]
+        tables = [wino.block_table(levels, c, dev, channels=ch) for c in copies]
+        firsts = [wino.block_table(levels, 1, dev, out_copies=c, channels=ch) for c in copies] if replicas else tables
+        replay = masked and self.dropout_rate > 0.0 and self.dropout_replay is not None
         kw = {"relu": True}
-        if dropout:
+        if masked:
             kw.update(dropout_p=0.0 if replay else float(self.dropout_rate), seed=self.dropout_seed, epoch=self._epoch)
-            base = self._drop_calls               # the offsets of the trunks one after the other: subnet i, layer l draws base + i L + l + 1
+            base = self._drop_calls
             self._drop_calls += len(subnets) * L
-        for l in range(L):
-            sets = []
-            for i, (sid, c) in enumerate(subnets):
-                s = {"conv": self._wino((self.cls_subnet, self.bbox_subnet)[sid][l]), "src": a[i] if l else x0, "dst": b[i] if l else a[i],
-                     "table": tables[i] if l else firsts[i], "offset": (base + i * L + l + 1) << 34 if dropout else 0}
-                if dropout and l == 0:
-                    s["replicas"] = c
-                sets.append(s)
-            if grouped:
-                grouped_launch(sets, live=None if live is None else (lambda t: live(t, reach_of_subnet_layer(l, L), DENSE_INPUT if l == 0 else -1)), **kw)
-            else:
-                for i, s in enumerate(sets):
-                    conv = s["conv"]
-                    if "replicas" not in s:
-                        conv(s["src"], s["dst"], s["table"], offset=s["offset"], **kw)
-                    elif conv.split and s["replicas"] <= 127:     # the copies stored by the conv's own store pass (..._split_replicas)
-                        conv.replicas(s["src"], s["dst"], s["table"], s["replicas"], offset=s["offset"], **kw)
-                    else:                                          # or by a pass of their own per level (the fp32-MFMA kernel; the same masks)
-                        y = conv(x0, torch.empty_like(x0), block_table(levels, 1, dev), relu=True)
-                        off1 = level_pixel_offsets(levels, 1)
-                        for lv, (h, w) in enumerate(levels):
-                            hip.check(hip.load().pod_expand_dropout(y[off1[lv]:].data_ptr(), s["dst"][offn[i][lv]:].data_ptr(), h * w * C, s["replicas"],
-                                                                    kw["dropout_p"], self.dropout_seed, s["offset"] + offn[i][lv] * C // 8,
-                                                                    self._epoch.data_ptr(), hip.current_stream()), "pod_expand_dropout")
-            if replay:                                         # parity mode: the recorded masks on the channels-last images of the layer's output
-                for i, (sid, c) in enumerate(subnets):
+        layers = [[{"conv": (self.cls_subnet, self.bbox_subnet)[sid][l], "src": d[(l - 1) % len(d)] if l else x0, "dst": d[l % len(d)],
+                    "table": tables[i] if l else firsts[i], "offset": (base + i * L + l + 1) << 34 if masked else 0,
+                    **({"replicas": copies[i]} if replicas and l == 0 else {})}
+                   for i, ((sid, _), d) in enumerate(zip(subnets, dsts))] for l in range(L)]
+        return {"layers": layers, "kw": kw, "copies": copies, "replay": replay}
+
+    def _launch(self, sets, st: dict, live=None, **kw) -> None:
+        """Launches `sets` (a layer of the trunks, or the predictors): ONE grid (pod_wino_conv3x3_split, n_sets > 1) when the head's launches
+        are grouped and the convs share a padded width -- the kernel runs one workgroup per CU, so a launch costs whole rounds of 256
+        workgroups: two launches of 1.5 rounds cost 4, one of 3.0 costs 3 -- and one one-set launch each otherwise: the same buffers, tables,
+        Philox offsets and therefore the same bits.  live: a callable (table) -> its live records (the sparse tower), or None."""
+        from . import hip, wino
+        sets = [dict(s, conv=self._wino(s["conv"])) for s in sets]
+        if st["grouped"] and len({s["conv"].Kpad for s in sets}) == 1 and all(s["conv"].split for s in sets):
+            return wino.grouped_launch(sets, live=live, **kw)
+        for s in sets:
+            conv, r = s["conv"], s.get("replicas", 0)
+            if conv.split and r <= 127:                        # (the copies stored by the conv's own store pass)
+                wino.grouped_launch([s], live=live, **kw)
+            elif not r:                                        # the fp32-MFMA kernel
+                conv(s["src"], s["dst"], s["table"], offset=s.get("offset", 0), planes=s.get("planes", False),
+                     **({} if live is None else {"live": live(s["table"])}), **kw)
+            else:                                              # ... its copies stored by a pass of their own per level (the same masks)
+                levels, x0 = st["levels"], s["src"]
+                y = conv(x0, torch.empty_like(x0), wino.block_table(levels, 1, x0.device), relu=True)
+                off1, offr = wino.level_pixel_offsets(levels, 1), wino.level_pixel_offsets(levels, r)
+                for lv, (h, w) in enumerate(levels):
+                    hip.check(hip.load().pod_expand_dropout(y[off1[lv]:].data_ptr(), s["dst"][offr[lv]:].data_ptr(), h * w * conv.C, r,
+                                                            kw["dropout_p"], kw["seed"], s["offset"] + offr[lv] * conv.C // 8,
+                                                            kw["epoch"].data_ptr(), hip.current_stream()), "pod_expand_dropout")
+
+    def _trunks(self, subnets, st: dict, live=None, bufs=None):
+        """Subnet evaluations on ALL levels: `_trunk_plan`'s launches, one per conv layer (fp32 Winograd on the matrix cores, bias + ReLU +
+        dropout in its store) instead of one MIOpen call + one element-wise pass per level and layer.  Returns per subnet (buffer, images
+        per level): the last activation as (pixels of all levels x images, C) channels-last, level after level; in the training form
+        st["saved"][i][l] = (input, output) of layer l besides.
+        live (sparse bbox tower, pod_compare_amd/sparse.py): a LiveBlocks -- layer j is launched over the blocks of reach L - j only; bufs:
+        the tower's buffers (only live blocks are written; what dead blocks hold is never read)."""
+        from .sparse import DENSE_INPUT, reach_of_subnet_layer
+        from .wino import level_pixel_offsets
+        assert live is None or st["grouped"], "the sparse tower needs the split kernel's grouped launches"
+        plan = self._trunk_plan(subnets, st, bufs)
+        levels, L = st["levels"], len(plan["layers"])
+        for l, sets in enumerate(plan["layers"]):
+            self._launch(sets, st, live=None if live is None else (lambda t: live(t, reach_of_subnet_layer(l, L), DENSE_INPUT if l == 0 else -1)),
+                         **plan["kw"])
+            if plan["replay"]:      # parity mode: the recorded masks on the channels-last images of the layer's output (the in-place
+                for s, (sid, _), c in zip(sets, subnets, plan["copies"]):         # copy bumps its version: the launch's abs-max record lapses)
+                    offs = level_pixel_offsets(levels, c)
                     for lv, (h, w) in enumerate(levels):
-                        v = sets[i]["dst"][offn[i][lv]:offn[i][lv + 1]].view(c, h, w, C)
+                        v = s["dst"][offs[lv]:offs[lv + 1]].view(c, h, w, -1)
                         v.copy_(self._replayed(v.permute(0, 3, 1, 2), sid, l, lv).permute(0, 2, 3, 1))
-            if l:
-                a, b = b, a
-        return [(a[i], c) for i, c in enumerate(copies)]
+        if st.get("images"):
+            st["saved"] = [[(sets[i]["src"], sets[i]["dst"]) for sets in plan["layers"]] for i in range(len(subnets))]
+        return [(plan["layers"][-1][i]["dst"], c) for i, c in enumerate(plan["copies"])]
 
     def _jobs(self, side: int, trunk, st: dict):
         """The predictor jobs (`_predict`) of one side -- 0: cls_score (+ cls_var), 1: bbox_pred (+ bbox_cov) -- on its trunk (buffer, images
@@ -648,13 +666,14 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         first = m if side == 0 else n
         return [(mean, buf, copies, 0, first, n)] + ([(var, buf, copies, first, m, n)] if var is not None else [])
 
-    def _predict(self, jobs, st: dict, live=None, bufs=None):
-        """The predictor convs (cls_score / bbox_pred / cls_var / bbox_cov, PR:430-484).  jobs: (conv, trunk buffer, images in it per level,
-        first image, image count, output images).  Returns per job and level an (out_copies, K, H, W) NCHW tensor -- the planes K1 streams --
-        whose images past `count` are zero (never uninitialised memory: a consumer without the quirk merge would read them).  ONE launch when
-        the head's launches are grouped and the convs share a padded width, one launch each otherwise.  live / bufs: the sparse tower (`_trunks`)."""
+    def _predict(self, jobs, st: dict, live=None, bufs=None, flat: bool = False):
+        """The predictor convs (cls_score / bbox_pred / cls_var / bbox_cov, PR:430-484), one `_launch`.  jobs: (conv, trunk buffer, images in
+        it per level, first image, image count, output images) -- inference: `_jobs`'; training: all B images of a trunk, (conv, buf, B, 0,
+        B, B).  Returns per job and level an (out_copies, K, H, W) NCHW tensor -- the planes K1 streams -- whose images past `count` are zero
+        (never uninitialised memory: a consumer without the quirk merge would read them); flat: per job the one buffer those are views of.
+        live / bufs: the sparse tower (`_trunks`)."""
         from .sparse import REACH_PREDICTOR
-        from .wino import block_table, grouped_launch, level_pixel_offsets
+        from .wino import block_table, level_pixel_offsets
         levels = st["levels"]
         sets, outs = [], []
         for ji, (conv, buf, buf_copies, first, count, out_copies) in enumerate(jobs):
@@ -664,15 +683,11 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                 out = bufs("p%d" % ji, (offs[-1] * K,))
             else:
                 out = (torch.zeros if out_copies > count else torch.empty)(offs[-1] * K, dtype=buf.dtype, device=buf.device)
-            sets.append({"conv": self._wino(conv), "src": buf, "dst": out, "planes": True,
-                         "table": block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies)})
-            outs.append([out[offs[i] * K:offs[i + 1] * K].view(out_copies, K, h, w) for i, (h, w) in enumerate(levels)])
-        lv = None if live is None else (lambda table: live(table, REACH_PREDICTOR))
-        if st["grouped"] and len({s["conv"].Kpad for s in sets}) == 1 and all(s["conv"].split for s in sets):
-            grouped_launch(sets, live=lv)
-        else:
-            for s in sets:
-                s["conv"](s["src"], s["dst"], s["table"], planes=True, **({} if lv is None else {"live": lv(s["table"])}))
+            sets.append({"conv": conv, "src": buf, "dst": out, "planes": True,
+                         "table": block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies,
+                                              channels=st.get("channels", 512))})
+            outs.append(out if flat else [out[offs[i] * K:offs[i + 1] * K].view(out_copies, K, h, w) for i, (h, w) in enumerate(levels)])
+        self._launch(sets, st, live=None if live is None else (lambda table: live(table, REACH_PREDICTOR)))
         return outs
 
     @staticmethod

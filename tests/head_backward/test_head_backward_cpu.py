@@ -1,5 +1,5 @@
 """CPU side of the head's backward pass: the fp64 identities the design rests on, the declarations of the new entry points, their
-argument validation, the solver defaults and the learning-rate schedule.  No GPU."""
+argument validation, the solver defaults and the learning-rate schedule; the head's launch plan in its two forms.  No GPU."""
 import ctypes
 
 import pytest
@@ -146,3 +146,69 @@ def test_learning_rate_schedule_at_its_corners():
     assert close(lr(60000), 0.00025) and close(lr(79999), 0.00025)
     assert close(lr(80000), 0.000025) and close(lr(89999), 0.000025)
     assert close(warmup_multistep_lr(10, 0.01, (5, 20), 0.5, 100, 0.1), 0.01 * (0.1 * 0.9 + 0.1) * 0.5)   # a boundary inside the warm-up
+
+
+# ---- the head's launch plan (modeling.ProbabilisticRetinaNetHead._trunk_plan), which the inference and the training forward both run -------
+PLAN_LEVELS, PLAN_C, PLAN_PIXELS = [(12, 20), (6, 10), (3, 5)], 64, 12 * 20 + 6 * 10 + 3 * 5
+
+
+def plan_of(monkeypatch, p, subnets, **st):
+    """-> (head, the plan of a 4-layer head of 64 channels at _drop_calls = 7 on CPU tensors, x0, the block_table calls it made)"""
+    from pod_compare_amd import modeling, wino
+    head = modeling.ProbabilisticRetinaNetHead(in_channels=PLAN_C, num_convs=4, dropout_rate=p, compute_cls_var=True, compute_bbox_cov=True)
+    head._drop_calls = 7
+    tables, real = [], wino.block_table
+
+    def block_table(levels, copies, device, **kw):
+        tables.append((list(levels), copies, kw))
+        return real(levels, copies, device, **kw)
+    monkeypatch.setattr(wino, "block_table", block_table)
+    x0 = torch.zeros(PLAN_PIXELS * st.get("images", 1), PLAN_C)
+    plan = head._trunk_plan(subnets, dict(st, x0=x0, levels=PLAN_LEVELS, grouped=True))
+    assert len(plan["layers"]) == 4 and all(len(sets) == len(subnets) for sets in plan["layers"])
+    assert all(s["conv"] is (head.cls_subnet, head.bbox_subnet)[sid][l] for l, sets in enumerate(plan["layers"]) for s, (sid, _) in zip(sets, subnets))
+    return head, plan, x0, tables
+
+
+def test_inference_plan_with_mc_dropout(monkeypatch):
+    head, plan, x0, tables = plan_of(monkeypatch, 0.1, [(0, 4), (1, 6)], dropout=True)
+    layers = plan["layers"]
+    assert [[s["offset"] for s in sets] for sets in layers] == [[8 << 34, 12 << 34], [9 << 34, 13 << 34], [10 << 34, 14 << 34], [11 << 34, 15 << 34]]
+    assert [[s.get("replicas") for s in sets] for sets in layers] == [[4, 6], [None, None], [None, None], [None, None]]
+    assert head._drop_calls == 7 + 8 and plan["copies"] == [4, 6] and not plan["replay"]
+    assert plan["kw"] == {"relu": True, "dropout_p": 0.1, "seed": head.dropout_seed, "epoch": head._epoch}
+    for i, c in enumerate((4, 6)):
+        a, b = layers[0][i]["dst"], layers[1][i]["dst"]
+        assert layers[0][i]["src"] is x0 and a is not b and tuple(a.shape) == tuple(b.shape) == (c * PLAN_PIXELS, PLAN_C)
+        assert all(sets[i]["src"] is x and sets[i]["dst"] is y for sets, x, y in zip(layers[1:], (a, b, a), (b, a, b)))       # ping-pong
+        assert layers[0][i]["table"].pod_pixels == PLAN_PIXELS and all(sets[i]["table"].pod_pixels == c * PLAN_PIXELS for sets in layers[1:])
+    assert layers[0][0]["dst"] is not layers[0][1]["dst"]
+    assert tables == [(PLAN_LEVELS, 4, {"channels": 512}), (PLAN_LEVELS, 6, {"channels": 512}),
+                      (PLAN_LEVELS, 1, {"out_copies": 4, "channels": 512}), (PLAN_LEVELS, 1, {"out_copies": 6, "channels": 512})]
+
+
+def test_inference_plan_without_dropout(monkeypatch):
+    head, plan, x0, tables = plan_of(monkeypatch, 0.1, [(0, 4), (1, 6)], dropout=False)
+    assert plan["copies"] == [1, 1] and plan["kw"] == {"relu": True} and head._drop_calls == 7
+    assert all(s["offset"] == 0 and "replicas" not in s and tuple(s["dst"].shape) == (PLAN_PIXELS, PLAN_C) for sets in plan["layers"] for s in sets)
+    assert tables == [(PLAN_LEVELS, 1, {"channels": 512})] * 2
+
+
+@pytest.mark.parametrize("p", [0.1, 0.0])
+def test_training_plan(monkeypatch, p):
+    head, plan, x0, tables = plan_of(monkeypatch, p, [(0, 2), (1, 2)], dropout=False, images=2, channels=max(PLAN_C, 64))
+    layers = plan["layers"]
+    assert not any("replicas" in s for sets in layers for s in sets)
+    dsts = [s["dst"] for sets in layers for s in sets]
+    assert len({id(t) for t in dsts}) == 8 and all(tuple(t.shape) == (2 * PLAN_PIXELS, PLAN_C) for t in dsts)
+    for i in range(2):
+        assert layers[0][i]["src"] is x0 and all(layers[l][i]["src"] is layers[l - 1][i]["dst"] for l in range(1, 4))
+    assert tables == [(PLAN_LEVELS, 2, {"channels": 64})] * 2
+    assert [[s["offset"] for s in sets] for sets in layers] == [[8 << 34, 12 << 34], [9 << 34, 13 << 34], [10 << 34, 14 << 34], [11 << 34, 15 << 34]]
+    assert head._drop_calls == 7 + 8 and plan["copies"] == [2, 2]
+    assert plan["kw"] == {"relu": True, "dropout_p": p, "seed": head.dropout_seed, "epoch": head._epoch}
+    if p > 0.0:                                                    # replay: the launches draw no masks, the recorded ones are applied after them
+        head._drop_calls = 7
+        head.dropout_replay = lambda sid, layer, level, copy_: None
+        again = head._trunk_plan([(0, 2), (1, 2)], {"x0": x0, "levels": PLAN_LEVELS, "grouped": True, "dropout": False, "images": 2, "channels": 64})
+        assert again["replay"] and again["kw"]["dropout_p"] == 0.0 and again["layers"][3][1]["offset"] == 15 << 34

@@ -138,6 +138,42 @@ def test_production_dropout_gates_on_the_saved_activation():
     assert all(q.grad is not None and bool(torch.isfinite(q.grad).all()) for c in head_convs(head) for q in (c.weight, c.bias))
 
 
+def test_training_forward_of_one_image_equals_the_inference_forward():
+    """p = 0, B = 1: the two forwards run one launch plan (modeling._trunk_plan) -- the same kernels, tables and abs-max records, so the
+    same bits.  (B > 1 stands the images at other canvas positions: Winograd tiles fall differently and the rounding with them.)"""
+    head = make_head(0.0)
+    g = torch.Generator().manual_seed(4)
+    feats = [torch.randn((1, C, h, w), generator=g).to(DEV) for h, w in LEVELS]
+    out = head.forward_train(feats)
+    with torch.no_grad():
+        want = head(feats, 1)
+    for name, got, ref in zip(("cls", "delta", "cls_var", "reg_var"), (out.cls, out.delta, out.cls_var, out.reg_var), want):
+        assert len(got) == len(ref) == len(LEVELS)
+        for t, r in zip(got, ref):
+            assert t.shape == r.shape and torch.equal(t.detach(), r), name
+
+
+def test_both_forwards_draw_their_philox_offsets_from_one_counter():
+    """p = 0.1, production masks: a training forward and an MC-dropout inference forward each advance head._drop_calls by one offset per
+    trunk layer and subnet, so two successive training forwards draw different masks."""
+    head = make_head(0.1)
+    L = len(head.cls_subnet)
+    g = torch.Generator().manual_seed(5)
+    feats = [torch.randn((B, C, h, w), generator=g).to(DEV) for h, w in LEVELS]
+    head.train_tap = {}
+    patterns = []
+    for _ in range(2):
+        before = head._drop_calls
+        head.forward_train(feats)
+        assert head._drop_calls == before + 2 * L
+        patterns.append([head.train_tap["saved"][sid][l][1] != 0 for sid in range(2) for l in range(L)])
+    assert all(not torch.equal(a, b) for a, b in zip(*patterns))
+    before = head._drop_calls
+    with torch.no_grad():
+        head([f[:1] for f in feats], 3, mc_dropout=True)
+    assert head._drop_calls == before + 2 * L
+
+
 def test_cpu_features_and_untileable_channels_raise():
     from pod_compare_amd import hip
     head = make_head(0.0)
