@@ -1,18 +1,21 @@
-// K5 bayes_fuse, K6 anchor_stats_merge, K7 finalize, reg_nll.
+// The post-NMS tail: K5 bayes_fuse, K6 anchor_stats (also the cluster kernel of the post-NMS ensemble merge), K7 finalize, the ensemble
+// merge's seed sweep and append kernel, reg_nll.
 //
 // Replaces:
 //   K5  probabilistic_inference.py:562-636 (post_processing_bayes_od cluster loop, one host
 //       round-trip per cluster at :591-601) + inference_utils.py:292-334
 //       (bounding_box_bayesian_inference: numpy fp32 LAPACK inv/det).
-//   K6  inference_utils.py:91-154 (general_anchor_statistics_postprocessing cluster loop).
+//   K6  inference_utils.py:91-154 (general_anchor_statistics_postprocessing cluster loop); with ensemble_rule = 1 the cluster
+//       moments of inference_utils.py:216-247, behind k_ensemble_seeds (:203-215) and k_append_rows (torch.cat of :191-196).
 //   K7  inference_utils.py:42-53 (keep-gather of the standard-NMS path) and :374-425
 //       (probabilistic_detector_postprocess), plus the XYWH records of :428-502.
 //   NLL core/evaluation_tools/scoring_rules.py:68-74.
 //
-// One 256-thread workgroup per kept cluster centre.  Only the <= 100 needed rows of the IoU
+// K5 / K6: one 256-thread workgroup per kept cluster centre.  Only the <= 100 needed rows of the IoU
 // matrix are evaluated, members are streamed once per pass, every lane inverts its
 // members' 4x4 covariances in fp64 registers, and the Gaussian moments / precisions are
-// combined with wavefront butterflies plus one LDS hop across the 4 waves.
+// combined with wavefront butterflies plus one LDS hop across the 4 waves.  K6's parts have names (cluster_prologue,
+// FOR_EACH_MEMBER, centre_fallback); K5 is written out (see there); the host checks and fills both through cluster_params.
 #include "pod_device.h"
 
 namespace pod {
@@ -22,41 +25,45 @@ struct M4 {
     double a[16];
 };
 
+// The twelve 2x2 minors of a 4x4 matrix -- s: rows 0, 1; c: rows 2, 3 -- and the Laplace expansion over them.
+struct Minors4 {
+    double s[6], c[6];
+    __device__ __forceinline__ explicit Minors4(const double* a) {
+        s[0] = a[0] * a[5] - a[4] * a[1]; s[1] = a[0] * a[6] - a[4] * a[2]; s[2] = a[0] * a[7] - a[4] * a[3];
+        s[3] = a[1] * a[6] - a[5] * a[2]; s[4] = a[1] * a[7] - a[5] * a[3]; s[5] = a[2] * a[7] - a[6] * a[3];
+        c[5] = a[10] * a[15] - a[14] * a[11]; c[4] = a[9] * a[15] - a[13] * a[11]; c[3] = a[9] * a[14] - a[13] * a[10];
+        c[2] = a[8] * a[15] - a[12] * a[11]; c[1] = a[8] * a[14] - a[12] * a[10]; c[0] = a[8] * a[13] - a[12] * a[9];
+    }
+    __device__ __forceinline__ double det() const {
+        return s[0] * c[5] - s[1] * c[4] + s[2] * c[3] + s[3] * c[2] - s[4] * c[1] + s[5] * c[0];
+    }
+};
+
 __device__ __forceinline__ double inv4(const M4& m, M4& o) {
     const double* a = m.a;
-    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
-    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
-    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
-    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
-    const double det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    const double id = 1.0 / det;
-    o.a[0] = (a[5] * c5 - a[6] * c4 + a[7] * c3) * id;
-    o.a[1] = (-a[1] * c5 + a[2] * c4 - a[3] * c3) * id;
-    o.a[2] = (a[13] * s5 - a[14] * s4 + a[15] * s3) * id;
-    o.a[3] = (-a[9] * s5 + a[10] * s4 - a[11] * s3) * id;
-    o.a[4] = (-a[4] * c5 + a[6] * c2 - a[7] * c1) * id;
-    o.a[5] = (a[0] * c5 - a[2] * c2 + a[3] * c1) * id;
-    o.a[6] = (-a[12] * s5 + a[14] * s2 - a[15] * s1) * id;
-    o.a[7] = (a[8] * s5 - a[10] * s2 + a[11] * s1) * id;
-    o.a[8] = (a[4] * c4 - a[5] * c2 + a[7] * c0) * id;
-    o.a[9] = (-a[0] * c4 + a[1] * c2 - a[3] * c0) * id;
-    o.a[10] = (a[12] * s4 - a[13] * s2 + a[15] * s0) * id;
-    o.a[11] = (-a[8] * s4 + a[9] * s2 - a[11] * s0) * id;
-    o.a[12] = (-a[4] * c3 + a[5] * c1 - a[6] * c0) * id;
-    o.a[13] = (a[0] * c3 - a[1] * c1 + a[2] * c0) * id;
-    o.a[14] = (-a[12] * s3 + a[13] * s1 - a[14] * s0) * id;
-    o.a[15] = (a[8] * s3 - a[9] * s1 + a[10] * s0) * id;
+    const Minors4 k(a);
+    const double *s = k.s, *c = k.c;
+    const double det = k.det(), id = 1.0 / det;
+    o.a[0] = (a[5] * c[5] - a[6] * c[4] + a[7] * c[3]) * id;
+    o.a[1] = (-a[1] * c[5] + a[2] * c[4] - a[3] * c[3]) * id;
+    o.a[2] = (a[13] * s[5] - a[14] * s[4] + a[15] * s[3]) * id;
+    o.a[3] = (-a[9] * s[5] + a[10] * s[4] - a[11] * s[3]) * id;
+    o.a[4] = (-a[4] * c[5] + a[6] * c[2] - a[7] * c[1]) * id;
+    o.a[5] = (a[0] * c[5] - a[2] * c[2] + a[3] * c[1]) * id;
+    o.a[6] = (-a[12] * s[5] + a[14] * s[2] - a[15] * s[1]) * id;
+    o.a[7] = (a[8] * s[5] - a[10] * s[2] + a[11] * s[1]) * id;
+    o.a[8] = (a[4] * c[4] - a[5] * c[2] + a[7] * c[0]) * id;
+    o.a[9] = (-a[0] * c[4] + a[1] * c[2] - a[3] * c[0]) * id;
+    o.a[10] = (a[12] * s[4] - a[13] * s[2] + a[15] * s[0]) * id;
+    o.a[11] = (-a[8] * s[4] + a[9] * s[2] - a[11] * s[0]) * id;
+    o.a[12] = (-a[4] * c[3] + a[5] * c[1] - a[6] * c[0]) * id;
+    o.a[13] = (a[0] * c[3] - a[1] * c[1] + a[2] * c[0]) * id;
+    o.a[14] = (-a[12] * s[3] + a[13] * s[1] - a[14] * s[0]) * id;
+    o.a[15] = (a[8] * s[3] - a[9] * s[1] + a[10] * s[0]) * id;
     return det;
 }
 
-__device__ __forceinline__ double det4(const M4& m) {
-    const double* a = m.a;
-    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
-    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
-    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
-    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
-    return s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-}
+__device__ __forceinline__ double det4(const M4& m) { return Minors4(m.a).det(); }
 
 __device__ __forceinline__ void load_m4(const float* p, M4& m) {
 #pragma unroll
@@ -193,6 +200,74 @@ __global__ void __launch_bounds__(POD_MAX_DETECTIONS) k7_finalize(const K7Params
     finalize_rows(P, threadIdx.x, min(*P.n_rows, P.max_det), s_flag);
 }
 
+// ---- K6's parts, and what K5 and K6 share ---------------------------------------------------------------------------------------
+struct ClusterParams {
+    const int32_t *n_total, *keep, *n_keep, *classes;
+    const float *boxes, *cov, *probs;   // cov: may be null in K6
+    int32_t K, n_capacity;
+    int32_t n_alloc;         // rows the candidate arrays really hold (speculative first loads stay inside)
+    int32_t n_keep_alloc;    // entries of keep[] = workgroups of the grid (the entry point sets it)
+    float aff;
+    float *out_boxes, *out_cov, *out_scores, *out_probs;
+    int32_t* out_classes;
+};
+
+constexpr int RED_SLOTS = 40;   // doubles per wavefront in the reduction buffer: the widest block_sum of either kernel
+
+// What a workgroup knows after round trips 1 and 2: the centre's candidate row and box, the candidate rows to walk, and this
+// thread's first two candidate boxes (rows tid, tid + 256; zeros beyond n_alloc).
+struct Cluster {
+    int ctr, n;
+    Box bc, pre[2];
+};
+
+// K6's round trip 1 -- everything that does not depend on the centre, issued together: the two counts, this cluster's centre index
+// (guarded: the grid may be larger than keep[]) and the first two candidate boxes of this thread (the kernel loads their classes in
+// front of this call).  The kernels are chains of HBM / L2 round trips with a few hundred instructions in between: what counts is how
+// many.  Round trip 2 -- the centre's box.  false: no cluster for this workgroup.
+__device__ __forceinline__ bool cluster_prologue(const ClusterParams& P, Cluster& cl) {
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int n_live = *P.n_keep, n_raw = *P.n_total;
+    cl.ctr = c < P.n_keep_alloc ? P.keep[c] : 0;
+    cl.pre[0] = tid < P.n_alloc ? load_box(P.boxes, tid) : Box{0.f, 0.f, 0.f, 0.f};
+    cl.pre[1] = tid + 256 < P.n_alloc ? load_box(P.boxes, tid + 256) : Box{0.f, 0.f, 0.f, 0.f};
+    if (c >= n_live) return false;
+    cl.n = min(n_raw, P.n_capacity);
+    cl.bc = load_box(P.boxes, cl.ctr);
+    return true;
+}
+
+// Does bj belong to the centre's cluster by IoU?  ge: IoU >= aff (black-box ensembles, IU:211-212), else IoU > aff (PI:565-566, IU:91-92).
+__device__ __forceinline__ bool iou_member(const Box& bc, const Box& bj, bool ge, float aff) {
+    const float iou = iou_pair(bc, bj);
+    return ge ? iou >= aff : iou > aff;
+}
+
+// The member walk of K6's two passes: the block behind it runs for this thread's rows j = tid, tid + 256, ... < n, in that order,
+// whose box bj passes iou_member; `it` counts the rows visited, and `continue` leaves a member.  PREFETCHED: rows 0 and 1 are cl.pre.
+// (A statement macro, like SG_LOAD_FILTER in pod_split_gemm.h: as a template taking the block as a lambda the compiler no longer
+// peels the two prefetched iterations out of pass 1 and the launch measures slower -- profiles/cluster_merge_shared.md.)
+#define FOR_EACH_MEMBER(P, cl, ge, PREFETCHED, j, it, bj)                                                                 \
+    for (int j = threadIdx.x, it = 0; j < (cl).n; j += 256, ++it)                                                        \
+        if (const Box bj = (PREFETCHED) ? (it == 0 ? (cl).pre[0] : (it == 1 ? (cl).pre[1] : load_box((P).boxes, j)))    \
+                                        : load_box((P).boxes, j);                                                       \
+            !iou_member((cl).bc, bj, ge, (P).aff))                                                                       \
+            continue;                                                                                                    \
+        else
+
+// The cluster is empty or degenerate: the centre's own box and covariance (IU:127-133; without candidate covariances 1e-4 I).
+__device__ __forceinline__ void centre_fallback(const ClusterParams& P, int ctr, bool has_cov, float* ob, float* oc) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ob[r] = P.boxes[(size_t)ctr * 4 + r];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) oc[e] = has_cov ? P.cov[(size_t)ctr * 16 + e] : ((e % 5 == 0) ? 1e-4f : 0.0f);
+}
+
+// ---- K5 ------------------------------------------------------------------------------------------------------------------------
+// K5 is the kernel it was before K6's parts got names, statement for statement, on the argument block it had: every form of it that
+// took the shared prologue, the walk macro, centre_fallback or ClusterParams measured 0.05 - 0.3 us slower per launch, and this one
+// compiles to the same instructions as before (profiles/cluster_merge_shared.md).  What it shares: inv4 / det4's minors, the named
+// accumulator slots, the reduction buffer's size and, on the host, cluster_params.
 struct K5Params {
     const int32_t* n_total;
     const int32_t* keep;
@@ -212,8 +287,14 @@ struct K5Params {
     float* out_probs;
 };
 
+// K5's accumulators.  The Gaussian moments: [16] sum of w P, [4] sum of w P mu -- pass A's acc with w = 1, and wsum, which holds these
+// MOM_N slots and no more, with the covariance-intersection weights.  Behind them in acc only: same-class members, IoU members,
+// [POD_MAX_CLASSES] probability sums over the IoU members.
+enum { MOM_P = 0, MOM_PMU = 16, MOM_N = 20 };
+enum { K5_SAME = MOM_N, K5_IOU, K5_PROBS, K5_N = K5_PROBS + POD_MAX_CLASSES };
+
 __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
-    __shared__ double s_red[4 * 40];
+    __shared__ double s_red[4 * RED_SLOTS];
     const int c = blockIdx.x;
     const int tid = threadIdx.x;
     // Round trip 1 -- everything that does not depend on the centre, issued together: the two counts, this cluster's
@@ -236,9 +317,9 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
     const int ccls = argmax_probs(P.probs + (size_t)ctr * K, K);     // PI:578-579
 
     // pass A: total precision, precision-weighted mean, member count, prob sums
-    double acc[16 + 4 + 2 + POD_MAX_CLASSES];   // [0,16) sum of precisions, [16,20) sum P mu, [20] same-class members, [21] IoU members, [22,..) prob sums
+    double acc[K5_N];
 #pragma unroll
-    for (int q = 0; q < 22 + POD_MAX_CLASSES; ++q) acc[q] = 0.0;
+    for (int q = 0; q < K5_N; ++q) acc[q] = 0.0;
     for (int j = tid, it = 0; j < n; j += 256, ++it) {
         const Box bj = it == 0 ? pre[0] : (it == 1 ? pre[1] : load_box(P.boxes, j));
         if (!(iou_pair(bc, bj) > P.aff)) continue;                    // PI:565-566
@@ -246,8 +327,8 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
         if (P.cls_mode == 1) {                                        // PI:583-585: mean over ALL IoU members
 #pragma unroll
             for (int k = 0; k < POD_MAX_CLASSES; ++k)             // static indices: the accumulators stay in registers
-                if (k < K) acc[22 + k] += (double)P.probs[(size_t)j * K + k];
-            acc[21] += 1.0;
+                if (k < K) acc[K5_PROBS + k] += (double)P.probs[(size_t)j * K + k];
+            acc[K5_IOU] += 1.0;
         }
         M4 cv;
         load_m4(P.cov + (size_t)j * 16, cv);                          // issued with the probability loads of argmax_probs
@@ -259,17 +340,17 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
         for (int q = 0; q < 16; ++q) acc[q] += pr.a[q];
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[16 + r] += pr.a[r * 4 + 0] * mu[0] + pr.a[r * 4 + 1] * mu[1] + pr.a[r * 4 + 2] * mu[2] + pr.a[r * 4 + 3] * mu[3];
-        acc[20] += 1.0;
+        acc[K5_SAME] += 1.0;
     }
     // the class-probability sums are only needed (and only accumulated) in cls_mode 1: 22 instead of 38 fp64 butterflies otherwise
-    if (P.cls_mode == 1) block_sum<22 + POD_MAX_CLASSES>(acc, s_red);
-    else block_sum<22>(acc, s_red);
-    const double m_same = acc[20];
+    if (P.cls_mode == 1) block_sum<K5_N>(acc, s_red);
+    else block_sum<K5_PROBS>(acc, s_red);
+    const double m_same = acc[K5_SAME];
     M4 total;
 #pragma unroll
     for (int q = 0; q < 16; ++q) total.a[q] = acc[q];
 
-    double wsum[20];   // weighted precision sum + weighted P*mu (covariance intersection)
+    double wsum[MOM_N];   // weighted precision sum + weighted P*mu (covariance intersection)
     if (P.box_mode == 1 && m_same > 0.0) {
         // IU:313-332: omega_i = (det(T) - det(T - P_i) + det(P_i)) / (m det(T) + sum_i (det(P_i) - det(T - P_i)))
         const double d_tot = det4(total);
@@ -288,7 +369,7 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
         block_sum<1>(dsum, s_red);
         const double denom = m_same * d_tot + dsum[0];
 #pragma unroll
-        for (int q = 0; q < 20; ++q) wsum[q] = 0.0;
+        for (int q = 0; q < MOM_N; ++q) wsum[q] = 0.0;
         for (int j = tid; j < n; j += 256) {
             const Box bj = load_box(P.boxes, j);
             if (!(iou_pair(bc, bj) > P.aff)) continue;
@@ -306,10 +387,10 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
             for (int r = 0; r < 4; ++r)
                 wsum[16 + r] += omega * (pr.a[r * 4 + 0] * mu[0] + pr.a[r * 4 + 1] * mu[1] + pr.a[r * 4 + 2] * mu[2] + pr.a[r * 4 + 3] * mu[3]);
         }
-        block_sum<20>(wsum, s_red);
+        block_sum<MOM_N>(wsum, s_red);
     } else {
 #pragma unroll
-        for (int q = 0; q < 20; ++q) wsum[q] = acc[q];
+        for (int q = 0; q < MOM_N; ++q) wsum[q] = acc[q];
     }
 
     if (tid == 0) {
@@ -332,13 +413,13 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
             for (int q = 0; q < 16; ++q) oc[q] = P.cov[(size_t)ctr * 16 + q];
         }
         float* op = P.out_probs + (size_t)c * K;
-        if (P.cls_mode == 1 && acc[21] > 0.0) {                       // PI:583-585, :609-613
+        if (P.cls_mode == 1 && acc[K5_IOU] > 0.0) {                       // PI:583-585, :609-613
             float best = 0.0f;
             int bk = 0;
 #pragma unroll
             for (int k = 0; k < POD_MAX_CLASSES; ++k) {
                 if (k < K) {
-                    const float p = (float)(acc[22 + k] / acc[21]);
+                    const float p = (float)(acc[K5_PROBS + k] / acc[K5_IOU]);
                     op[k] = p;
                     if (k == 0 || p > best) {
                         best = p;
@@ -356,86 +437,54 @@ __global__ void __launch_bounds__(256) k5_bayes_fuse(const K5Params P) {
     }
 }
 
-struct K6Params {
-    const int32_t* n_total;
-    const int32_t* keep;
-    const int32_t* n_keep;
-    const float* boxes;
-    const float* cov;      // may be null
-    const int32_t* classes;
-    const float* probs;
-    int32_t K, n_capacity;
-    int32_t n_alloc;         // rows the candidate arrays really hold (speculative first loads stay inside)
-    int32_t n_keep_alloc;    // entries of keep[]
+// ---- K6 ------------------------------------------------------------------------------------------------------------------------
+struct K6Params : ClusterParams {
     int32_t ensemble_rule;   // 0: anchor statistics (IoU > aff, IU:102 singleton rule); 1: black-box ensembles (IoU >= aff, IU:211-247)
-    float aff;
-    float* out_boxes;
-    float* out_cov;
-    float* out_scores;
-    int32_t* out_classes;
-    float* out_probs;
 };
 
+// K6's pass-1 accumulators: IoU members, same-class members, then over the latter [4] box sum, [POD_MAX_CLASSES] probability sums,
+// [16] covariance sum.  Pass 2: the K6_RR entries of the upper triangle of the residuals' outer-product sum.
+enum { K6_IOU = 0, K6_SAME, K6_BOX, K6_PROBS = K6_BOX + 4, K6_COV = K6_PROBS + POD_MAX_CLASSES, K6_N = K6_COV + 16, K6_RR = 10 };
+static_assert(K5_N <= RED_SLOTS && K6_N <= RED_SLOTS, "reduction buffer");
+
 __global__ void __launch_bounds__(256) k6_anchor_stats(const K6Params P) {
-    __shared__ double s_red[4 * 40];
-    const int c = blockIdx.x;
-    const int tid = threadIdx.x;
-    // round trip 1: counts, centre index, this thread's first two candidate boxes and classes (see k5_bayes_fuse)
-    const int n_live = *P.n_keep;
-    const int n_raw = *P.n_total;
-    const int ctr = c < P.n_keep_alloc ? P.keep[c] : 0;
-    Box pre[2];
-    int pre_cls[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int j = tid + q * 256;
-        pre[q] = j < P.n_alloc ? load_box(P.boxes, j) : Box{0.f, 0.f, 0.f, 0.f};
-        pre_cls[q] = j < P.n_alloc ? P.classes[j] : -1;
-    }
-    if (c >= n_live) return;
-    const int n = min(n_raw, P.n_capacity);
-    const int K = P.K;
-    const Box bc = load_box(P.boxes, ctr);
+    __shared__ double s_red[4 * RED_SLOTS];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    // round trip 1 also brings the classes of this thread's first two candidate rows
+    const int pre_cls[2] = {tid < P.n_alloc ? P.classes[tid] : -1, tid + 256 < P.n_alloc ? P.classes[tid + 256] : -1};
+    Cluster cl;
+    if (!cluster_prologue(P, cl)) return;
+    const int ctr = cl.ctr, K = P.K;
     const int ccls = P.classes[ctr];                                 // IU:104
     const bool has_cov = P.cov != nullptr;
 
     // pass 1: member counts, box sum, prob sum, covariance sum of same-class members
-    double acc[2 + 4 + POD_MAX_CLASSES + 16];
-#pragma unroll
-    for (int q = 0; q < 22 + POD_MAX_CLASSES; ++q) acc[q] = 0.0;
-    const bool ens = P.ensemble_rule != 0;
-    for (int j = tid, it = 0; j < n; j += 256, ++it) {
-        const Box bj = it == 0 ? pre[0] : (it == 1 ? pre[1] : load_box(P.boxes, j));
-        const float iou = iou_pair(bc, bj);
-        if (!(ens ? iou >= P.aff : iou > P.aff)) continue;            // IU:91-92 (>) / IU:211-212 (>=)
-        acc[0] += 1.0;                                                // IU:102 counts every IoU member
-        const int cj = it == 0 ? pre_cls[0] : (it == 1 ? pre_cls[1] : P.classes[j]);
-        if (cj != ccls) continue;                                     // IU:104-106
-        acc[1] += 1.0;
-        acc[2] += bj.x1; acc[3] += bj.y1; acc[4] += bj.x2; acc[5] += bj.y2;
+    double acc[K6_N] = {};
+    const bool ens = P.ensemble_rule != 0;                           // IU:91-92 (>) / IU:211-212 (>=)
+    FOR_EACH_MEMBER(P, cl, ens, true, j, it, bj) {
+        acc[K6_IOU] += 1.0;                                           // IU:102 counts every IoU member
+        const int cj = it == 0 ? pre_cls[0] : (it == 1 ? pre_cls[1] : P.classes[j]);   // rows 0 and 1: prefetched
+        if (cj != ccls) continue;                                       // IU:104-106
+        acc[K6_SAME] += 1.0;
+        acc[K6_BOX] += bj.x1; acc[K6_BOX + 1] += bj.y1; acc[K6_BOX + 2] += bj.x2; acc[K6_BOX + 3] += bj.y2;
 #pragma unroll
         for (int k = 0; k < POD_MAX_CLASSES; ++k)                 // static indices: the accumulators stay in registers
-            if (k < K) acc[6 + k] += (double)P.probs[(size_t)j * K + k];
+            if (k < K) acc[K6_PROBS + k] += (double)P.probs[(size_t)j * K + k];
         if (has_cov)
 #pragma unroll
-            for (int q = 0; q < 16; ++q) acc[6 + POD_MAX_CLASSES + q] += (double)P.cov[(size_t)j * 16 + q];
+            for (int q = 0; q < 16; ++q) acc[K6_COV + q] += (double)P.cov[(size_t)j * 16 + q];
     }
-    block_sum<22 + POD_MAX_CLASSES>(acc, s_red);
-    const double m_all = acc[0], m = acc[1];
+    block_sum<K6_N>(acc, s_red);
+    const double m_all = acc[K6_IOU], m = acc[K6_SAME];
     const bool cluster = ens ? (m >= 1.0) : (m_all >= 2.0 && m >= 1.0);   // IU:226-247: a 1-member cluster is its own mean
     // the reference forms the mean in fp32 and subtracts it from fp32 boxes (IU:112-114)
     float mu[4] = {0, 0, 0, 0};
     if (cluster)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) mu[r] = (float)(acc[2 + r] / m);
-    double rr[10];
-#pragma unroll
-    for (int q = 0; q < 10; ++q) rr[q] = 0.0;
+        for (int r = 0; r < 4; ++r) mu[r] = (float)(acc[K6_BOX + r] / m);
+    double rr[K6_RR] = {};
     if (cluster) {
-        for (int j = tid; j < n; j += 256) {
-            const Box bj = load_box(P.boxes, j);
-            const float iou = iou_pair(bc, bj);
-            if (!(ens ? iou >= P.aff : iou > P.aff)) continue;
+        FOR_EACH_MEMBER(P, cl, ens, false, j, it, bj) {
             if (P.classes[j] != ccls) continue;
             const float r[4] = {bj.x1 - mu[0], bj.y1 - mu[1], bj.x2 - mu[2], bj.y2 - mu[3]};
             int q = 0;
@@ -445,7 +494,7 @@ __global__ void __launch_bounds__(256) k6_anchor_stats(const K6Params P) {
                 for (int b = a; b < 4; ++b, ++q) rr[q] += (double)(r[a] * r[b]);
         }
     }
-    block_sum<10>(rr, s_red);
+    block_sum<K6_RR>(rr, s_red);
     if (tid == 0) {
         float* ob = P.out_boxes + (size_t)c * 4;
         float* oc = P.out_cov + (size_t)c * 16;
@@ -463,18 +512,15 @@ __global__ void __launch_bounds__(256) k6_anchor_stats(const K6Params P) {
                 }
             if (has_cov)                                              // IU:120-123
 #pragma unroll
-                for (int e = 0; e < 16; ++e) oc[e] = oc[e] + (float)(acc[6 + POD_MAX_CLASSES + e] / m);
+                for (int e = 0; e < 16; ++e) oc[e] = oc[e] + (float)(acc[K6_COV + e] / m);
 #pragma unroll
             for (int r = 0; r < 4; ++r) ob[r] = mu[r];
 #pragma unroll
             for (int k = 0; k < POD_MAX_CLASSES; ++k)
-                if (k < K) op[k] = (float)(acc[6 + k] / m);           // IU:126
+                if (k < K) op[k] = (float)(acc[K6_PROBS + k] / m);    // IU:126
         } else {                                                      // IU:127-133
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ob[r] = P.boxes[(size_t)ctr * 4 + r];
+            centre_fallback(P, ctr, has_cov, ob, oc);
             for (int k = 0; k < K; ++k) op[k] = P.probs[(size_t)ctr * K + k];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) oc[e] = has_cov ? P.cov[(size_t)ctr * 16 + e] : ((e % 5 == 0) ? 1e-4f : 0.0f);
         }
         const int bk = argmax_probs(op, K);                           // IU:146-152 (Q10)
         P.out_scores[c] = op[bk];
@@ -601,23 +647,44 @@ __global__ void __launch_bounds__(256) k_reg_nll(const float* means, const float
 }
 
 }  // namespace pod
+// What pod_bayes_fuse, pod_anchor_stats_merge and pod_ensemble_merge check and fill alike, for ClusterParams or K5Params.  `ensemble`:
+// the rows are an ensemble's concatenated member detections, `capacity` rows and as many centres at most; else the hot path's
+// candidate arrays (n_levels * topk rows) and cfg->max_detections centres.  Returns the number of centres -- the grid, and K6's
+// n_keep_alloc -- or 0 for invalid arguments.  `cov` may be null here: an entry point that needs it says so itself.
+template <typename Params>
+static int32_t cluster_params(Params& P, const PodConfig* cfg, bool ensemble, int32_t capacity, int32_t max_classes,
+                              const int32_t* n_total, const int32_t* keep, const int32_t* n_keep, const float* boxes,
+                              const float* cov, const int32_t* classes, const float* probs, float* out_boxes, float* out_cov,
+                              float* out_scores, int32_t* out_classes, float* out_probs) {
+    if (!cfg || !n_total || !keep || !n_keep || !boxes || !classes || !probs || !out_boxes || !out_cov || !out_scores ||
+        !out_classes || !out_probs)
+        return 0;
+    if (cfg->num_classes < 1 || cfg->num_classes > max_classes) return 0;
+    if (ensemble && (capacity < 1 || capacity > POD_MAX_CANDIDATES)) return 0;
+    if (!ensemble && (cfg->max_detections < 1 || cfg->max_detections > POD_MAX_DETECTIONS)) return 0;
+    P.n_total = n_total; P.keep = keep; P.n_keep = n_keep; P.boxes = boxes; P.cov = cov; P.classes = classes; P.probs = probs;
+    P.K = cfg->num_classes; P.aff = cfg->affinity_thresh;
+    P.n_capacity = ensemble ? capacity : POD_MAX_CANDIDATES;
+    P.n_alloc = ensemble ? capacity : cfg->n_levels * cfg->topk;
+    P.out_boxes = out_boxes; P.out_cov = out_cov; P.out_scores = out_scores; P.out_classes = out_classes; P.out_probs = out_probs;
+    return ensemble ? capacity : cfg->max_detections;
+}
 
 extern "C" int pod_bayes_fuse(const PodConfig* cfg, const int32_t* n_total, const int32_t* keep, const int32_t* n_keep,
                               const float* boxes, const float* cov, const float* scores, const int32_t* classes,
                               const float* probs, int32_t box_mode, int32_t cls_mode, float* out_boxes, float* out_cov,
                               float* out_scores, int32_t* out_classes, float* out_probs, pod_stream_t stream) {
-    if (!cfg || !n_total || !keep || !n_keep || !boxes || !cov || !scores || !classes || !probs || !out_boxes || !out_cov ||
-        !out_scores || !out_classes || !out_probs)
-        return POD_E_INVALID;
+    if (!cov || !scores) return POD_E_INVALID;
     if (box_mode < 0 || box_mode > 1 || cls_mode < 0 || cls_mode > 1) return POD_E_INVALID;
-    if (cfg->num_classes < 1 || cfg->num_classes >= POD_MAX_CLASSES) return POD_E_INVALID;
-    if (cfg->max_detections < 1 || cfg->max_detections > POD_MAX_DETECTIONS) return POD_E_INVALID;
+    // One class fewer than the other two entry points accept.  That is pod_nms_cluster's limit (its prefix scan over POD_MAX_CLASSES
+    // lanes keeps entry num_classes for the total), whose keep list K5 reads.  Nothing in k5_bayes_fuse needs it: its accumulators
+    // and the reduction buffer hold POD_MAX_CLASSES classes.  Kept as it is: what an entry point accepts is part of its contract.
     pod::K5Params P;
-    P.n_total = n_total; P.keep = keep; P.n_keep = n_keep; P.boxes = boxes; P.cov = cov; P.scores = scores;
-    P.classes = classes; P.probs = probs; P.K = cfg->num_classes; P.box_mode = box_mode; P.cls_mode = cls_mode;
-    P.n_capacity = POD_MAX_CANDIDATES; P.aff = cfg->affinity_thresh; P.n_alloc = cfg->n_levels * cfg->topk;
-    P.out_boxes = out_boxes; P.out_cov = out_cov; P.out_scores = out_scores; P.out_classes = out_classes; P.out_probs = out_probs;
-    hipLaunchKernelGGL(pod::k5_bayes_fuse, dim3(cfg->max_detections), dim3(256), 0, (hipStream_t)stream, P);
+    const int32_t centres = cluster_params(P, cfg, false, 0, POD_MAX_CLASSES - 1, n_total, keep, n_keep, boxes, cov, classes, probs,
+                                           out_boxes, out_cov, out_scores, out_classes, out_probs);
+    if (!centres) return POD_E_INVALID;
+    P.scores = scores; P.box_mode = box_mode; P.cls_mode = cls_mode;
+    hipLaunchKernelGGL(pod::k5_bayes_fuse, dim3(centres), dim3(256), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }
@@ -626,17 +693,12 @@ extern "C" int pod_anchor_stats_merge(const PodConfig* cfg, const int32_t* n_tot
                                       const int32_t* n_keep, const float* boxes, const float* cov, const int32_t* classes,
                                       const float* probs, float* out_boxes, float* out_cov, float* out_scores,
                                       int32_t* out_classes, float* out_probs, pod_stream_t stream) {
-    if (!cfg || !n_total || !keep || !n_keep || !boxes || !classes || !probs || !out_boxes || !out_cov || !out_scores ||
-        !out_classes || !out_probs)
-        return POD_E_INVALID;
-    if (cfg->num_classes < 1 || cfg->num_classes > POD_MAX_CLASSES) return POD_E_INVALID;
-    if (cfg->max_detections < 1 || cfg->max_detections > POD_MAX_DETECTIONS) return POD_E_INVALID;
     pod::K6Params P;
-    P.n_total = n_total; P.keep = keep; P.n_keep = n_keep; P.boxes = boxes; P.cov = cov; P.classes = classes; P.probs = probs;
-    P.K = cfg->num_classes; P.n_capacity = POD_MAX_CANDIDATES; P.aff = cfg->affinity_thresh; P.ensemble_rule = 0;
-    P.n_alloc = cfg->n_levels * cfg->topk; P.n_keep_alloc = cfg->max_detections;
-    P.out_boxes = out_boxes; P.out_cov = out_cov; P.out_scores = out_scores; P.out_classes = out_classes; P.out_probs = out_probs;
-    hipLaunchKernelGGL(pod::k6_anchor_stats, dim3(cfg->max_detections), dim3(256), 0, (hipStream_t)stream, P);
+    const int32_t centres = cluster_params(P, cfg, false, 0, POD_MAX_CLASSES, n_total, keep, n_keep, boxes, cov, classes, probs,
+                                           out_boxes, out_cov, out_scores, out_classes, out_probs);
+    if (!centres) return POD_E_INVALID;
+    P.n_keep_alloc = centres; P.ensemble_rule = 0;
+    hipLaunchKernelGGL(pod::k6_anchor_stats, dim3(centres), dim3(256), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }
@@ -660,21 +722,18 @@ extern "C" int pod_ensemble_merge(const PodConfig* cfg, const int32_t* m_total, 
                                   const float* cov, const int32_t* classes, const float* probs, int32_t* seeds, int32_t* n_seeds,
                                   float* out_boxes, float* out_cov, float* out_scores, int32_t* out_classes, float* out_probs,
                                   pod_stream_t stream) {
-    if (!cfg || !m_total || !boxes || !cov || !classes || !probs || !seeds || !n_seeds || !out_boxes || !out_cov || !out_scores ||
-        !out_classes || !out_probs)
-        return POD_E_INVALID;
-    if (capacity < 1 || capacity > POD_MAX_CANDIDATES || cfg->num_classes < 1 || cfg->num_classes > POD_MAX_CLASSES) return POD_E_INVALID;
+    if (!cov) return POD_E_INVALID;
+    pod::K6Params P;   // the seeds are the centres
+    const int32_t centres = cluster_params(P, cfg, true, capacity, POD_MAX_CLASSES, m_total, seeds, n_seeds, boxes, cov, classes, probs,
+                                           out_boxes, out_cov, out_scores, out_classes, out_probs);
+    if (!centres) return POD_E_INVALID;
+    P.n_keep_alloc = centres; P.ensemble_rule = 1;
     pod::KSeedParams S;
     S.m_total = m_total; S.capacity = capacity; S.aff = cfg->affinity_thresh; S.boxes = boxes; S.classes = classes; S.seeds = seeds;
     S.n_seeds = n_seeds;
     hipLaunchKernelGGL(pod::k_ensemble_seeds, dim3(1), dim3(1024), 0, (hipStream_t)stream, S);
     POD_CHECK_LAUNCH();
-    pod::K6Params P;
-    P.n_total = m_total; P.keep = seeds; P.n_keep = n_seeds; P.boxes = boxes; P.cov = cov; P.classes = classes; P.probs = probs;
-    P.K = cfg->num_classes; P.n_capacity = capacity; P.aff = cfg->affinity_thresh; P.ensemble_rule = 1;
-    P.n_alloc = capacity; P.n_keep_alloc = capacity;
-    P.out_boxes = out_boxes; P.out_cov = out_cov; P.out_scores = out_scores; P.out_classes = out_classes; P.out_probs = out_probs;
-    hipLaunchKernelGGL(pod::k6_anchor_stats, dim3(capacity), dim3(256), 0, (hipStream_t)stream, P);
+    hipLaunchKernelGGL(pod::k6_anchor_stats, dim3(centres), dim3(256), 0, (hipStream_t)stream, P);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }

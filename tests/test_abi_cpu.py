@@ -147,6 +147,58 @@ def test_candidate_entry_points_reject_invalid_arguments_without_a_gpu(lib_path)
     assert fused(ok, levels=replay) == -1
 
 
+def test_cluster_merge_entry_points_reject_invalid_arguments_without_a_gpu(lib_path):
+    """pod_bayes_fuse, pod_anchor_stats_merge and pod_ensemble_merge share one validate-and-fill function; each still rejects exactly
+    what it rejected before: its null pointers (cov may be null for anchor statistics only), its class-count limit (BayesOD takes one
+    class fewer) and its count limit (max_detections, or the ensemble's capacity)."""
+    lib = hip.load()
+    buf = ctypes.create_string_buffer(64)
+    X = ctypes.addressof(buf)                        # any non-null pointer: never dereferenced on these paths
+    MC, MD, MN = hip.POD_MAX_CLASSES, hip.POD_MAX_DETECTIONS, hip.POD_MAX_CANDIDATES
+
+    def cfg_with(**kw):
+        c = hip.PodConfig()
+        c.n_levels, c.topk, c.num_classes, c.max_detections = 5, 1000, 7, 100
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    def bayes(c, box_mode=0, cls_mode=0, null=None):      # 8 input pointers, the modes, 5 outputs, a null stream
+        a = [X] * 13
+        if null is not None:
+            a[null] = None
+        return lib.pod_bayes_fuse(c, *a[:8], box_mode, cls_mode, *a[8:], None)
+
+    def anchor(c, null=None):                             # 7 input pointers, 5 outputs
+        a = [X] * 12
+        if null is not None:
+            a[null] = None
+        return lib.pod_anchor_stats_merge(c, *a, None)
+
+    def ensemble(c, capacity=300, null=None):             # m_total, then capacity, 4 inputs, seeds, n_seeds, 5 outputs
+        a = [X] * 12
+        if null is not None:
+            a[null] = None
+        return lib.pod_ensemble_merge(c, a[0], capacity, *a[1:], None)
+
+    ok = cfg_with()
+    assert bayes(None) == -1 and anchor(None) == -1 and ensemble(None) == -1
+    for i in range(13):
+        assert bayes(ok, null=i) == -1, i
+    for i in range(12):
+        assert ensemble(ok, null=i) == -1, i
+        if i != 4:                                        # cov
+            assert anchor(ok, null=i) == -1, i
+    for kw in ({"box_mode": -1}, {"box_mode": 2}, {"cls_mode": -1}, {"cls_mode": 2}):
+        assert bayes(ok, **kw) == -1, kw
+    assert bayes(cfg_with(num_classes=0)) == -1 and bayes(cfg_with(num_classes=MC)) == -1
+    for call in (anchor, ensemble):
+        assert call(cfg_with(num_classes=0)) == -1 and call(cfg_with(num_classes=MC + 1)) == -1
+    for call in (bayes, anchor):
+        assert call(cfg_with(max_detections=0)) == -1 and call(cfg_with(max_detections=MD + 1)) == -1
+    assert ensemble(ok, capacity=0) == -1 and ensemble(ok, capacity=MN + 1) == -1
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setenv("POD_MI355X_LIB", "/nonexistent/libpod_mi355x.so")
     monkeypatch.setattr(hip, "_lib", None)

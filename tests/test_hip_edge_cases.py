@@ -141,3 +141,73 @@ def test_threshold_monotonicity():
         n = int(hp.n_total.item())
         keys.append(set(zip(hp.cand_level[:n].cpu().tolist(), hp.cand_anchor_idx[:n].cpu().tolist())))
     assert keys[2] <= keys[1] <= keys[0] and len(keys[2]) < len(keys[0])
+
+
+# ---------------------------------------------------------------------------------------------------
+# K5 / K6 cluster merges at a size where every thread's member walk goes past its two prefetched boxes (n > 512)
+# ---------------------------------------------------------------------------------------------------
+
+MERGE_SIZE = (256, 320)
+BOX_MERGES = ("bayesian_inference", "covariance_intersection")
+CLS_MERGES = ("max_score", "bayesian_inference")
+_merge_cache = {}
+
+
+def _merge_inputs(runs=3, **kw):
+    key = ("ho", runs, tuple(sorted(kw.items())))
+    if key not in _merge_cache:
+        _merge_cache[key] = synthetic.planted_head_outputs(MERGE_SIZE, runs, seed=5, num_boxes=40, **kw)
+    return _merge_cache[key]
+
+
+def _bayes_od_merge(box_merge, cls_merge):
+    """One oracle-checked run per combination, shared by the tests below (765 candidates, 39 finite detections on the CPU oracle)."""
+    key = (box_merge, cls_merge)
+    if key not in _merge_cache:
+        hp, det, ref = hip_vs_oracle(_merge_inputs(), "bayes_od", MERGE_SIZE, MERGE_SIZE, seed=5, runs=3,
+                                     box_merge_mode=box_merge, cls_merge_mode=cls_merge)
+        m = det.count()
+        assert int(hp.n_total.item()) > 512      # the walk leaves the prefetched boxes behind in every thread
+        assert_close(det.probs[:m].cpu(), ref.pred_cls_probs, "probs", 2e-6, 1e-7)
+        _merge_cache[key] = (m, det.boxes[:m].clone(), det.cov[:m].clone(), det.scores[:m].clone(), det.classes[:m].clone(), det.probs[:m].clone())
+    return _merge_cache[key]
+
+
+@pytest.mark.parametrize("cls_merge", CLS_MERGES)
+@pytest.mark.parametrize("box_merge", BOX_MERGES)
+def test_bayes_od_every_merge_combination(box_merge, cls_merge):
+    """BOX_MERGE_MODE x CLS_MERGE_MODE (PI:583-617, IU:292-334) against the oracle; the goldens hold two of the four."""
+    assert _bayes_od_merge(box_merge, cls_merge)[0] > 0
+
+
+def test_bayes_od_box_and_class_merges_do_not_touch_each_other():
+    """Boxes and covariances depend on the box merge alone, scores / classes / probabilities on the class merge alone: bit for bit."""
+    runs = {(b, c): _bayes_od_merge(b, c) for b in BOX_MERGES for c in CLS_MERGES}
+    assert len({r[0] for r in runs.values()}) == 1
+    for b in BOX_MERGES:
+        for q in (1, 2):
+            assert torch.equal(runs[(b, CLS_MERGES[0])][q], runs[(b, CLS_MERGES[1])][q]), (b, q)
+    for c in CLS_MERGES:
+        for q in (3, 4, 5):
+            assert torch.equal(runs[(BOX_MERGES[0], c)][q], runs[(BOX_MERGES[1], c)][q]), (c, q)
+    assert not torch.equal(runs[(BOX_MERGES[0], CLS_MERGES[0])][1], runs[(BOX_MERGES[1], CLS_MERGES[0])][1])     # the modes do differ
+    assert not torch.equal(runs[(BOX_MERGES[0], CLS_MERGES[0])][5], runs[(BOX_MERGES[0], CLS_MERGES[1])][5])
+
+
+def test_anchor_statistics_adds_the_members_covariance_sum():
+    """3 MC runs, both variance heads: K6 with candidate covariances (IU:120-123), on the geometry of the BayesOD cases."""
+    hp, det, ref = hip_vs_oracle(_merge_inputs(), "anchor_statistics", MERGE_SIZE, MERGE_SIZE, seed=5, runs=3)
+    assert hp.has_covariance and int(hp.n_total.item()) > 512 and det.count() > 0
+
+
+def test_anchor_statistics_without_candidate_covariances():
+    """One run, no variance head: K6's cov == nullptr path.  Clusters sum no covariances, and a centre without a second IoU member
+    falls back to its own box with 1e-4 I (IU:127-133): at least one row of this input does, bit for bit."""
+    ho = _merge_inputs(1, with_cls_var=False, with_reg_var=False)
+    hp, det, ref = hip_vs_oracle(ho, "anchor_statistics", MERGE_SIZE, MERGE_SIZE, seed=5, runs=1)
+    assert not hp.has_covariance and det.count() > 0
+    nk = int(hp.n_keep.item())
+    own_box = (hp.m_boxes[:nk] == hp.boxes[hp.keep[:nk].long()]).all(dim=1)
+    unit_cov = (hp.m_cov[:nk] == 1e-4 * torch.eye(4, device="cuda")).all(dim=2).all(dim=1)
+    print("fallback rows:", int((own_box & unit_cov).sum()), "of", nk)
+    assert bool((own_box & unit_cov).any())
