@@ -286,8 +286,7 @@ extern "C" int pod_wino_conv3x3(const float* in, float* out, const float* U, con
     pod::WinoParams P{};
     const int64_t grid = pod::wino_params_launch(P, blocks, n_blocks, C, K, relu, p, seed, epoch);
     if (grid < 0) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(U) |
-          reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(blocks)) & 15u) != 0)
+    if (!pod_aligned(16, in, out, U, bias, blocks))
         return POD_E_INVALID;
     if (n_blocks == 0) return POD_OK;
     if (pod_lds_opt_in<pod::k_wino_conv3x3>(pod::WINO_LDS_BYTES) != POD_OK) return POD_E_LAUNCH;

@@ -437,7 +437,7 @@ extern "C" int64_t pod_wino_filter_split_bytes(int32_t K, int32_t C) {          
 }
 
 extern "C" int pod_wino_filter_transform_split(const float* weight, void* Us, int32_t K, int32_t C, pod_stream_t stream) {
-    if (!weight || !Us || K < 1 || C < 16 || (C & 15) != 0 || (reinterpret_cast<uintptr_t>(Us) & 15u) != 0) return POD_E_INVALID;
+    if (!weight || !Us || K < 1 || C < 16 || (C & 15) != 0 || !pod_aligned(16, Us)) return POD_E_INVALID;
     const int32_t Kpad = (K + 63) / 64 * 64;
     const int64_t n = (int64_t)Kpad * C;
     float* amax = reinterpret_cast<float*>(reinterpret_cast<char*>(Us) + pod_wino_filter_split_bytes(K, C) - 16);
@@ -455,7 +455,7 @@ extern "C" int pod_wino_filter_transform_split(const float* weight, void* Us, in
 // convolution cut over its input channels into partial sums.  See include/pod_mi355x.h: PodWinoConv.
 extern "C" int pod_wino_conv3x3_split(const PodWinoConv* d, pod_stream_t stream) {
     if (!d || d->n_sets < 1 || d->n_sets > 4 || !d->blocks || d->n_blocks < 0 || d->C < 16 || (d->C & 15) != 0 || d->K < 64 || (d->K & 63) != 0 ||
-        !(d->p >= 0.0f && d->p < 1.0f) || d->sets[0].first_block != 0 || (reinterpret_cast<uintptr_t>(d->blocks) & 15u) != 0 ||
+        !(d->p >= 0.0f && d->p < 1.0f) || d->sets[0].first_block != 0 || !pod_aligned(16, d->blocks) ||
         d->reserved != 0)
         return POD_E_INVALID;
     const int32_t C = d->C, K = d->K;
@@ -475,8 +475,7 @@ extern "C" int pod_wino_conv3x3_split(const PodWinoConv* d, pod_stream_t stream)
             if (!q.in || !q.out || q.in == q.out || !q.Us || !q.in_amax || q.replicas < 0 || q.replicas > 127 || q.k_planes < 0 || q.k_planes > K ||
                 (q.k_planes > 0 && (d->p != 0.0f || q.replicas != 0)) || (s > 0 && q.first_block < d->sets[s - 1].first_block) || q.first_block > d->n_blocks)
                 return POD_E_INVALID;
-            if (((reinterpret_cast<uintptr_t>(q.in) | reinterpret_cast<uintptr_t>(q.out) | reinterpret_cast<uintptr_t>(q.Us) | reinterpret_cast<uintptr_t>(q.bias)) & 15u) != 0 ||
-                ((reinterpret_cast<uintptr_t>(q.in_amax) | reinterpret_cast<uintptr_t>(q.out_amax)) & 3u) != 0)
+            if (!pod_aligned(16, q.in, q.out, q.Us, q.bias) || !pod_aligned(4, q.in_amax, q.out_amax))
                 return POD_E_INVALID;
         }
         pod::wino_params_set(P, s, s < d->n_sets ? q.first_block : INT32_MAX, q.in, q.out, q.Us, q.bias, q.in_amax, q.out_amax, q.offset, q.replicas, q.k_planes);

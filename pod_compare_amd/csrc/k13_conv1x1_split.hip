@@ -384,11 +384,7 @@ __global__ void __launch_bounds__(256) k_conv1x1_reduce(const float* __restrict_
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     float lmax = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        f32x4 v = *reinterpret_cast<const f32x4*>(partials + 4 * i);
-        for (int s = 1; s < n_splits; ++s) v += *reinterpret_cast<const f32x4*>(partials + (int64_t)s * split_stride + 4 * i);
-        if (bias) v += *reinterpret_cast<const f32x4*>(bias + (int)((4 * i) % Cout));
-        if (residual) v += *reinterpret_cast<const f32x4*>(residual + 4 * i);
-        if (relu) wino_relu4(v);
+        const f32x4 v = sg_split_sum4(partials, 4 * i, n_splits, split_stride, bias, [&](int64_t e) { return (int)(e % Cout); }, residual, relu);
         *reinterpret_cast<f32x4*>(y + 4 * i) = v;
         lmax = wino_absmax4(lmax, v);
     }
@@ -403,7 +399,7 @@ extern "C" int64_t pod_conv1x1_filter_split_bytes(int32_t Cout, int32_t Cin) {  
 }
 
 extern "C" int pod_conv1x1_filter_split(const float* weight, void* Ws, int32_t Cout, int32_t Cin, pod_stream_t stream) {
-    if (!weight || !Ws || Cout < 32 || (Cout & 31) != 0 || Cin < 16 || (Cin & 15) != 0 || (reinterpret_cast<uintptr_t>(Ws) & 15u) != 0) return POD_E_INVALID;
+    if (!weight || !Ws || Cout < 32 || (Cout & 31) != 0 || Cin < 16 || (Cin & 15) != 0 || !pod_aligned(16, Ws)) return POD_E_INVALID;
     const int64_t n = (int64_t)Cout * (Cin / 2);
     return pod::sg_filter_prepare(weight, (int64_t)Cout * Cin, Ws, (int64_t)Cout * Cin * 2, (hipStream_t)stream, [&](const float* amax) {
         hipLaunchKernelGGL(pod::k_conv1x1_filter_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax,
@@ -436,10 +432,7 @@ extern "C" int pod_conv1x1_split(const float* x, float* y, const void* Ws, const
         }
         if (waves > 1 && (per_split % (2 * waves) != 0)) return POD_E_INVALID;
     }
-    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(Ws) | reinterpret_cast<uintptr_t>(bias) |
-          reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(partials)) & 15u) != 0 ||
-        ((reinterpret_cast<uintptr_t>(in_amax) | reinterpret_cast<uintptr_t>(out_amax)) & 3u) != 0)
-        return POD_E_INVALID;
+    if (!pod_aligned(16, x, y, Ws, bias, residual, partials) || !pod_aligned(4, in_amax, out_amax)) return POD_E_INVALID;
     pod::C1Params P;
     P.x = x; P.y = n_splits > 1 ? partials : y; P.Ws = reinterpret_cast<const uint16_t*>(Ws); P.bias = bias; P.residual = residual;
     P.in_amax = in_amax; P.out_amax = out_amax;
@@ -463,9 +456,7 @@ extern "C" int pod_conv1x1_split(const float* x, float* y, const void* Ws, const
     POD_CHECK_LAUNCH();
     if (n_splits > 1) {
         const int64_t n4 = P_out * Cout / 4;
-        int64_t blocks = (n4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(pod::k_conv1x1_reduce, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, partials, n_splits, P_out * Cout, bias, residual, y, n4,
+        hipLaunchKernelGGL(pod::k_conv1x1_reduce, dim3(pod_grid_stride_blocks(n4, 2048)), dim3(256), 0, (hipStream_t)stream, partials, n_splits, P_out * Cout, bias, residual, y, n4,
                            Cout, relu, out_amax);
         POD_CHECK_LAUNCH();
     }
@@ -478,12 +469,9 @@ extern "C" int pod_reduce_partials(const float* partials, int32_t n_splits, int6
                                    int32_t Cout, int32_t relu, float* out_amax, pod_stream_t stream) {
     if (!partials || !y || n_splits < 1 || n_splits > 16 || n < 0 || (n & 3) != 0 || Cout < 4 || (Cout & 3) != 0 || n % Cout != 0) return POD_E_INVALID;
     if (n_splits > 1 && (split_stride < n || (split_stride & 3) != 0)) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 15u) != 0)
-        return POD_E_INVALID;
+    if (!pod_aligned(16, partials, y, bias, residual)) return POD_E_INVALID;
     if (n == 0) return POD_OK;
-    int64_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pod::k_conv1x1_reduce, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, partials, n_splits, split_stride, bias, residual, y, n / 4,
+    hipLaunchKernelGGL(pod::k_conv1x1_reduce, dim3(pod_grid_stride_blocks(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, partials, n_splits, split_stride, bias, residual, y, n / 4,
                        Cout, relu, out_amax);
     POD_CHECK_LAUNCH();
     return POD_OK;

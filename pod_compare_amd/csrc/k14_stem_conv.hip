@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(256) k_im2col3x3s2_cl(const float* __restrict_
 }  // namespace pod
 
 extern "C" int pod_stem7x7_filter_split(const float* weight, void* Ws, pod_stream_t stream) {
-    if (!weight || !Ws || (reinterpret_cast<uintptr_t>(Ws) & 15u) != 0) return POD_E_INVALID;
+    if (!weight || !Ws || !pod_aligned(16, Ws)) return POD_E_INVALID;
     return pod::sg_filter_prepare(weight, 64 * 3 * 49, Ws, 2 * 64 * 192, (hipStream_t)stream, [&](const float* amax) {      // (the trailer: behind the 2 x 64 x 192 f16 terms)
         hipLaunchKernelGGL(pod::k_stem_filter_split, dim3((64 * 96 + 255) / 256), dim3(256), 0, (hipStream_t)stream, weight, reinterpret_cast<uint16_t*>(Ws), amax);
     });
@@ -167,11 +167,10 @@ extern "C" int pod_stem7x7_filter_split(const float* weight, void* Ws, pod_strea
 
 extern "C" int pod_stem7x7_split(const void* x, int32_t x_is_u8, int32_t H_img, int32_t W_img, const float* mean, const float* stddev, float* y, const void* Ws,
                                  const float* bias, int32_t H, int32_t W, int32_t relu, const float* in_amax, float* out_amax, pod_stream_t stream) {
-    if (!x || !y || !Ws || !in_amax || ((reinterpret_cast<uintptr_t>(in_amax) | reinterpret_cast<uintptr_t>(out_amax)) & 3u) != 0 || x == static_cast<const void*>(y) || H < 1 || W < 1 || H > 16384 || W > 16384 || H_img < 1 || W_img < 1 || H_img > H || W_img > W)
+    if (!x || !y || !Ws || !in_amax || !pod_aligned(4, in_amax, out_amax) || x == static_cast<const void*>(y) || H < 1 || W < 1 || H > 16384 || W > 16384 || H_img < 1 || W_img < 1 || H_img > H || W_img > W)
         return POD_E_INVALID;
     if ((mean == nullptr) != (stddev == nullptr)) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(Ws) | reinterpret_cast<uintptr_t>(bias)) & 15u) != 0 ||
-        (!x_is_u8 && (reinterpret_cast<uintptr_t>(x) & 3u) != 0))
+    if (!pod_aligned(16, y, Ws, bias) || (!x_is_u8 && !pod_aligned(4, x)))
         return POD_E_INVALID;
     pod::StemParams P;
     P.x = x; P.x_u8 = x_is_u8 ? 1 : 0; P.Hi = H_img; P.Wi = W_img; P.mean = mean; P.std_ = stddev;
@@ -187,7 +186,7 @@ extern "C" int pod_stem7x7_split(const void* x, int32_t x_is_u8, int32_t H_img, 
 
 extern "C" int pod_maxpool3x3s2_cl(const float* x, float* y, int32_t H, int32_t W, int32_t C, pod_stream_t stream) {
     if (!x || !y || x == y || H < 1 || W < 1 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, x, y)) return POD_E_INVALID;
     const int32_t Hp = (H - 1) / 2 + 1, Wp = (W - 1) / 2 + 1;
     const int64_t n = (int64_t)Hp * Wp * (C / 4);
     int64_t blocks = (n + 255) / 256;
@@ -199,7 +198,7 @@ extern "C" int pod_maxpool3x3s2_cl(const float* x, float* y, int32_t H, int32_t 
 
 extern "C" int pod_im2col3x3s2_cl(const float* x, float* y, int32_t H, int32_t W, int32_t C, int32_t relu, pod_stream_t stream) {
     if (!x || !y || x == y || H < 1 || W < 1 || H > 16384 || W > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, x, y)) return POD_E_INVALID;
     const int32_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int64_t n = (int64_t)Ho * Wo * 9 * (C / 4);
     int64_t blocks = (n + 255) / 256;

@@ -158,7 +158,7 @@ extern "C" int pod_sparse_reach(const PodConfig* cfg, const PodLevel* levels, co
 extern "C" int pod_sparse_live_blocks(const PodConfig* cfg, const PodLevel* levels, const int32_t* records, const int32_t* rec_level, int32_t n_records,
                                       const uint8_t* reach, int32_t max_reach, int32_t in_reach, int32_t* live, pod_stream_t stream) {
     if (!cfg || !levels || !records || !rec_level || !reach || !live || n_records < 0 || max_reach < 0 || max_reach > pod::SPARSE_MAX_REACH ||
-        in_reach < max_reach || in_reach > 255 || (reinterpret_cast<uintptr_t>(records) & 15u) != 0 || (reinterpret_cast<uintptr_t>(live) & 15u) != 0)
+        in_reach < max_reach || in_reach > 255 || !pod_aligned(16, records, live))
         return POD_E_INVALID;
     const int L = cfg->n_levels;
     if (L < 1 || L > POD_MAX_LEVELS) return POD_E_INVALID;

@@ -404,7 +404,6 @@ __global__ void __launch_bounds__(256) k1b_score_maybe(const K1bParams P) {
 
 }  // namespace pod
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 extern "C" int pod_abi_version(void) { return POD_ABI_VERSION; }
 
@@ -438,11 +437,11 @@ extern "C" int pod_mc_merge_score(const PodConfig* cfg, const PodLevel* levels, 
         if ((int64_t)A * (K > 4 + D ? K : 4 + D) * HW >= (int64_t)1 << 31) return POD_E_INVALID;   // 32-bit plane arithmetic
         P.chunks[l] = (int32_t)((HW + 255) / 256);
         const bool hw4 = (HW % 4) == 0;
-        P.vec_cls[l] = hw4 && aligned16(lv.cls) && (lv.run_stride_cls % 4 == 0) && (!cfg->has_cls_var || aligned16(lv.cls_var)) &&
-                       ((int64_t)lv.anchor_base * K % 4 == 0) && aligned16(mean_cls) && aligned16(mean_cls_var);
-        P.vec_delta[l] = aligned16(lv.delta) && (lv.run_stride_delta % 4 == 0) && aligned16(mean_delta);
-        P.vec_reg[l] = D > 0 && aligned16(lv.reg_var) && (lv.run_stride_reg % 4 == 0) && ((int64_t)A * D * HW % 4 == 0) &&
-                       ((int64_t)lv.anchor_base * D % 4 == 0) && aligned16(mean_reg_var);
+        P.vec_cls[l] = hw4 && pod_aligned(16, lv.cls) && (lv.run_stride_cls % 4 == 0) && (!cfg->has_cls_var || pod_aligned(16, lv.cls_var)) &&
+                       ((int64_t)lv.anchor_base * K % 4 == 0) && pod_aligned(16, mean_cls) && pod_aligned(16, mean_cls_var);
+        P.vec_delta[l] = pod_aligned(16, lv.delta) && (lv.run_stride_delta % 4 == 0) && pod_aligned(16, mean_delta);
+        P.vec_reg[l] = D > 0 && pod_aligned(16, lv.reg_var) && (lv.run_stride_reg % 4 == 0) && ((int64_t)A * D * HW % 4 == 0) &&
+                       ((int64_t)lv.anchor_base * D % 4 == 0) && pod_aligned(16, mean_reg_var);
     }
     int32_t nb = 0, s = 0;
     for (int l = 0; l < L; ++l) {   // cls role

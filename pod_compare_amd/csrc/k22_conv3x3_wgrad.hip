@@ -281,7 +281,7 @@ extern "C" int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t*
     int64_t pixels;
     if (!x || !dy || !x_amax || !dy_amax || !dW || !db || !partials) return POD_E_INVALID;
     if (!pod::wgrad_geometry(level_hw, n_levels, copies, C, K, Kpad, G, pixels)) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(partials)) & 15u) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, x, dy, partials)) return POD_E_INVALID;
     const int64_t n_slices = (G.first_step[n_levels] + pod::WG_STEPS - 1) / pod::WG_STEPS;
     const int64_t n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
     if (n_slices > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return POD_E_INVALID;
@@ -301,12 +301,10 @@ extern "C" int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t*
 
 extern "C" int pod_relu_dropout_backward(const float* out, const float* d_out, float* d_z, int64_t n, float p, float* dz_amax, pod_stream_t stream) {
     if (!out || !d_out || !d_z || n < 0 || (n & 3) != 0 || !(p >= 0.0f && p < 1.0f)) return POD_E_INVALID;
-    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_z)) & 15u) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, out, d_out, d_z)) return POD_E_INVALID;
     if (n == 0) return POD_OK;
     const int64_t n4 = n / 4;
-    int64_t blocks = (n4 + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(pod::k_relu_dropout_backward, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, d_out, d_z, n4, 1.0f / (1.0f - p), dz_amax);
+    hipLaunchKernelGGL(pod::k_relu_dropout_backward, dim3(pod_grid_stride_blocks(n4, 4096)), dim3(256), 0, (hipStream_t)stream, out, d_out, d_z, n4, 1.0f / (1.0f - p), dz_amax);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }

@@ -440,7 +440,7 @@ extern "C" int pod_nms_cluster(const PodConfig* cfg, const int32_t* n_total, int
     if (n_capacity < 1 || n_capacity > POD_MAX_CANDIDATES) return POD_E_INVALID;
     if (cfg->max_detections < 1 || cfg->max_detections > POD_MAX_DETECTIONS) return POD_E_INVALID;
     if (cfg->num_classes < 1 || cfg->num_classes >= POD_MAX_CLASSES) return POD_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(scratch) & 15u) != 0 || (reinterpret_cast<uintptr_t>(boxes) & 15u) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, scratch, boxes)) return POD_E_INVALID;
     pod::K4Params P;
     P.n_total = n_total; P.n_capacity = n_capacity; P.max_det = cfg->max_detections; P.num_classes = cfg->num_classes;
     P.thr = cfg->nms_thresh;

@@ -32,6 +32,17 @@ static int pod_lds_opt_in(int bytes) {
     return attr[dev] == hipSuccess ? POD_OK : POD_E_LAUNCH;
 }
 
+// Host: every pointer is a multiple of `bytes` (a power of two); null pointers pass -- whether one may be null is the caller's own check.
+template <typename... P>
+static inline bool pod_aligned(unsigned bytes, const P*... p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & (bytes - 1u)) == 0;
+}
+// Host: workgroups of a grid-stride launch over n4 thread-quads (256 threads, 16 B per lane and trip), at least 1 and at most `cap`.
+static inline unsigned pod_grid_stride_blocks(int64_t n4, int64_t cap) {
+    const int64_t blocks = (n4 + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
+}
+
 // -DPOD_TRACE (python -m pod_compare_amd.build with POD_TRACE=1; diagnostics only, never the shipped library): phase
 // time stamps of the first workgroups of a kernel, constant 100 MHz clock, dumped by pod_trace_dump() of the same file.
 #ifdef POD_TRACE
@@ -72,22 +83,43 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1
     return c;
 }
 
-// Dropout masks of the model-side kernels (k8_model_ops.hip, k11_wino_conv.hip): 16 random bits per element, 8 elements per
-// Philox4x32-10 call.  Float4 group g (elements 4g .. 4g+3 of the flat tensor a kernel writes) owns words 2 (g & 1) and
-// 2 (g & 1) + 1 of the call with counter base + (g >> 1); element j of the group keeps its value iff field j -- low / high half
-// of the two words -- is >= thresh16 = (uint32_t)(p * 2^16) (0: no dropout), and is scaled by 1 / (1 - p).
-// Philox key of a dropout launch: `seed`, or with a device-resident epoch word (launches replayed from a HIP graph) seed ^ mix(epoch)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Dropout masks of the model-side kernels (k8_model_ops.hip, the store pass of pod_wino.h) -- the WHOLE rule, written here once:
+//   * 16 random bits per element, 8 elements per Philox4x32-10 call, counter words {ctr lo, ctr hi, c2, STREAM_DROPOUT}, key `seed` -- or,
+//     with a device-resident epoch word (launches replayed from a HIP graph), seed ^ mix(epoch): dropout_key.
+//   * Float4 group g (elements 4g .. 4g+3 of the flat tensor a kernel writes) owns words 2 (g & 1) and 2 (g & 1) + 1 of the call with
+//     counter base + (g >> 1) (dropout_words; a thread with 8 consecutive floats makes the call itself: (r.x, r.y) are the first quad's
+//     words, (r.z, r.w) the second's).  Element j of the group keeps its value iff field j -- low / high half of the two words -- is
+//     >= thresh16 = (uint32_t)(p * 2^16) (0: no dropout), and is then scaled by 1 / (1 - p): dropout_mask4.
+//   * c2 = 0: the mask of a tensor in place (pod_relu_dropout, pod_bias_act, pod_bias_act_to_nchw, a convolution's store pass);
+//     c2 = 2: the replicas (pod_expand_dropout, group index copy * n4 + g; the store pass with replicas > 0).
+//   * c2 = 1: the n % 4 tail elements of a flat tensor.  Tail element t (0 .. 2) takes the low half of word 0 of the call with counter
+//     base + n4 + t (n4 = n / 4 whole groups): dropout_tail_keep.
+constexpr uint32_t STREAM_DROPOUT = 0x64726f70u;   // the counter's 4th word ("drop")
+#define POD_DROPOUT_THRESH16(p) ((uint32_t)((double)(p) * 65536.0))
+
 __device__ __forceinline__ uint64_t dropout_key(uint64_t seed, const uint64_t* epoch) {
     return epoch ? seed ^ (*epoch * 0x9E3779B97F4A7C15ull) : seed;
 }
-
-__device__ __forceinline__ void dropout_words(uint64_t base, uint64_t g, uint32_t c2, uint32_t stream, uint64_t seed, uint32_t& w0, uint32_t& w1) {
+__device__ __forceinline__ void dropout_words(uint64_t base, uint64_t g, uint32_t c2, uint64_t seed, uint32_t& w0, uint32_t& w1) {
     const uint64_t ctr = base + (g >> 1);
-    const u32x4 r = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), c2, stream}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const u32x4 r = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), c2, STREAM_DROPOUT}, (uint32_t)seed, (uint32_t)(seed >> 32));
     w0 = (g & 1) ? r.z : r.x;
     w1 = (g & 1) ? r.w : r.y;
 }
-#define POD_DROPOUT_THRESH16(p) ((uint32_t)((double)(p) * 65536.0))
+template <typename V4>      // f32x4 or float4, whichever the site holds: no conversion for the compiler to see through
+__device__ __forceinline__ void dropout_mask4(V4& v, uint32_t w0, uint32_t w1, uint32_t thresh, float scale) {
+    v.x = (w0 & 0xFFFFu) >= thresh ? v.x * scale : 0.f;
+    v.y = (w0 >> 16) >= thresh ? v.y * scale : 0.f;
+    v.z = (w1 & 0xFFFFu) >= thresh ? v.z * scale : 0.f;
+    v.w = (w1 >> 16) >= thresh ? v.w * scale : 0.f;
+}
+__device__ __forceinline__ bool dropout_tail_keep(uint64_t base, int64_t n4, uint32_t t, uint64_t seed, uint32_t thresh) {
+    const uint64_t ctr = base + (uint64_t)n4 + t;
+    const u32x4 r = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), 1u, STREAM_DROPOUT}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (r.x & 0xFFFFu) >= thresh;
+}
 
 // Native-RNG normals: Box-Muller on two 16-bit uniforms (one 32-bit Philox word per pair of normals,
 // 8 normals per Philox4x32-10 call).  u1 = (a + 0.5) / 2^16 >= 2^-17 bounds the radius, so

@@ -1,6 +1,6 @@
 // The split GEMM's shared home: an fp32 product formed on the f16 matrix cores from the two-term f16 split of the power-of-two-scaled
 // operands.  First what every split kernel uses (k12 through pod_wino.h; k8 / k10 for the abs-max records and the test hook): the f16
-// split, the abs-max records, the four-lane ReLU and abs-max.  Then the 64-pixel x 64-channel GEMM TILE of k13_conv1x1_split.hip and
+// split, the abs-max records, the four-lane ReLU and abs-max, the fixed-order sum of a split convolution's partials.  Then the 64-pixel x 64-channel GEMM TILE of k13_conv1x1_split.hip and
 // k14_stem_conv.hip, each part written once: constants and types, the activation and inverse scales, the filter ring's load, the k-step
 // (split + three partial products), the whole-line epilogue through LDS, and the filter preparation (abs-max kernel, term store, host
 // sequence).  A kernel keeps what is its own: where its activations come from, and where its pixels go.
@@ -13,8 +13,7 @@
 namespace pod {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));      // (f32x4: pod_device.h)
 
 // ---- an fp32 value as the sum of two FP16 values (round 5: k12 / k13 / k14; pod_debug_f16_split2 exposes the same code to the tests)
 // The f16 matrix cores run at the bf16 rate, and two f16 terms carry 11 + 1 (the sign of the residual) + 11 = 23 of an fp32's 24
@@ -116,6 +115,22 @@ __device__ __forceinline__ void wino_relu4(f32x4& v) {
 }
 __device__ __forceinline__ float wino_absmax4(float lmax, const f32x4& v) {
     return fmaxf(fmaxf(lmax, fabsf(v.x)), fmaxf(fmaxf(fabsf(v.y), fabsf(v.z)), fabsf(v.w)));
+}
+
+// ---- the end of a convolution cut over its input channels (k13's own reduce, pod_reduce_partials, pod_wino_reduce): the four values at
+// element e of the n_splits channels-last partial sums, `split_stride` floats apart, added in a FIXED order -- split 0 first, then
+// 1 .. n - 1, then the bias, then the residual (either may be null) -- so that the result does not depend on scheduling; then ReLU.
+// channel(e) -> the first of the four channels of element e: asked for only with a bias (k13 pays a division for it; as a plain argument
+// the division leaves `if (bias)` and k_conv1x1_reduce comes out as other code than before -- profiles/model_ops_shared.md).
+template <typename Channel>
+__device__ __forceinline__ f32x4 sg_split_sum4(const float* partials, int64_t e, int n_splits, int64_t split_stride, const float* bias, Channel&& channel,
+                                               const float* residual, int relu) {
+    f32x4 v = *reinterpret_cast<const f32x4*>(partials + e);
+    for (int s = 1; s < n_splits; ++s) v += *reinterpret_cast<const f32x4*>(partials + (int64_t)s * split_stride + e);
+    if (bias) v += *reinterpret_cast<const f32x4*>(bias + channel(e));
+    if (residual) v += *reinterpret_cast<const f32x4*>(residual + e);
+    if (relu) wino_relu4(v);
+    return v;
 }
 
 // ==== The split-GEMM tile of k13 / k14 ================================================================================================

@@ -10,8 +10,6 @@
 
 namespace pod {
 
-constexpr uint32_t STREAM_DROPOUT_CONV = 0x64726f70u;   // = STREAM_DROPOUT of k8_model_ops.hip: same mask as pod_bias_act
-
 constexpr int WINO_U_FLOATS = 24 * 2 * 64 * 4;          // filter slab of a chunk: [24 positions][h][j][4 channels]  48 KB
 constexpr int WINO_SB_FLOATS = 384 * 32;                 // raw patch stage of a SUPER-CHUNK (32 input channels): [pixel slot 360 (+24: 48 whole DMA instructions)][8 parts of 16 B], 48 KB
 constexpr int WINO_LDS_BYTES = 4 * 32 * 4 * 65 * 4;      // 133 120 B of the CU's 160 KB: the output staging (the K loop needs 24 KB)
@@ -346,19 +344,13 @@ struct WinoStore {
     uint64_t offset;          // Philox counter of the set's first 8 floats
     int replicas, k_planes;
 };
-// Dropout of the 8 consecutive floats at e (a multiple of 8): ONE Philox call, 16 mask bits per element -- pod_bias_act's mask with
-// counter word 0, pod_expand_dropout's (the replicas) with word 2.
+// Dropout of the 8 consecutive floats at e (a multiple of 8): ONE Philox call for the two quads (pod_device.h: the mask rule) --
+// pod_bias_act's mask with counter word 0, pod_expand_dropout's (the replicas) with word 2.
 __device__ __forceinline__ void wino_dropout8(f32x4& v0, f32x4& v1, int64_t e, uint64_t offset, uint32_t word, uint64_t key, uint32_t thresh, float scale) {
     const uint64_t ctr = offset + (uint64_t)(e >> 3);
-    const u32x4 r4 = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), word, STREAM_DROPOUT_CONV}, (uint32_t)key, (uint32_t)(key >> 32));
-    v0.x = (r4.x & 0xFFFFu) >= thresh ? v0.x * scale : 0.f;
-    v0.y = (r4.x >> 16) >= thresh ? v0.y * scale : 0.f;
-    v0.z = (r4.y & 0xFFFFu) >= thresh ? v0.z * scale : 0.f;
-    v0.w = (r4.y >> 16) >= thresh ? v0.w * scale : 0.f;
-    v1.x = (r4.z & 0xFFFFu) >= thresh ? v1.x * scale : 0.f;
-    v1.y = (r4.z >> 16) >= thresh ? v1.y * scale : 0.f;
-    v1.z = (r4.w & 0xFFFFu) >= thresh ? v1.z * scale : 0.f;
-    v1.w = (r4.w >> 16) >= thresh ? v1.w * scale : 0.f;
+    const u32x4 r4 = philox4x32_10(u32x4{(uint32_t)ctr, (uint32_t)(ctr >> 32), word, STREAM_DROPOUT}, (uint32_t)key, (uint32_t)(key >> 32));
+    dropout_mask4(v0, r4.x, r4.y, thresh, scale);
+    dropout_mask4(v1, r4.z, r4.w, thresh, scale);
 }
 
 // Both store passes take the launch's uniform decisions (ReLU, dropout, abs-max record) ONCE, as template parameters behind one dispatch,

@@ -199,6 +199,69 @@ def test_cluster_merge_entry_points_reject_invalid_arguments_without_a_gpu(lib_p
     assert ensemble(ok, capacity=0) == -1 and ensemble(ok, capacity=MN + 1) == -1
 
 
+def test_model_op_entry_points_reject_invalid_arguments_without_a_gpu(lib_path):
+    """The seven entry points of k8_model_ops.hip, pod_reduce_partials and pod_relu_dropout_backward: every null pointer, misalignment,
+    range and divisibility condition an entry point checks makes it return POD_E_INVALID, and an empty tensor (n == 0 / N == 0) returns
+    POD_OK where the entry point has that exit -- all before anything is launched.  Every rejected call differs from a valid one in
+    exactly the argument under test."""
+    lib = hip.load()
+    buf = ctypes.create_string_buffer(128)
+    X = (ctypes.addressof(buf) + 63) & ~63           # 64-byte aligned, never dereferenced on these paths
+    M, M2 = X + 4, X + 2                             # misaligned for 16 bytes; for 4 bytes
+    Y = X + 64                                       # a second aligned pointer (src != dst)
+    nan = float("nan")
+
+    def rejects(fn, base, bad, empty=None):
+        """base: a valid argument list; empty: {position: value} that makes it an empty, accepted call; bad: (position, value) pairs."""
+        if empty is not None:
+            a = list(base)
+            for i, v in empty.items():
+                a[i] = v
+            assert fn(*a) == 0, (fn.__name__, "empty")
+        for i, v in bad:
+            a = list(base)
+            if empty is not None:                    # checks come before the empty exit: the rejected call stays launch-free either way
+                for j, w in empty.items():
+                    a[j] = w
+            a[i] = v
+            assert fn(*a) == -1, (fn.__name__, i, v)
+
+    bad_p = [-0.1, 1.0, 1.5, nan]
+    # pod_bias_act_to_nhwc(src, dst, bias, N, C, HW, relu, stream)
+    rejects(lib.pod_bias_act_to_nhwc, [X, Y, X, 1, 8, 6, 1, None],
+            [(0, None), (1, None), (1, X), (3, -1), (4, 0), (4, 3), (4, 6), (5, 0), (0, M), (1, M), (3, 1 << 31)], empty={3: 0})
+    assert lib.pod_bias_act_to_nhwc(X, Y, X, 1, 8, 1 << 38, 1, None) == -1                # more workgroups than a grid holds
+    # pod_bias_act_to_nchw(src, dst, bias, N, C, HW, relu, p, seed, offset, stream)
+    rejects(lib.pod_bias_act_to_nchw, [X, Y, X, 1, 8, 8, 1, 0.3, 1, 0, None],
+            [(0, None), (1, None), (1, X), (3, -1), (4, 0), (4, 3), (4, 6), (5, 0), (5, 3), (5, 6), (0, M), (1, M), (2, M), (3, 1 << 31)]
+            + [(7, p) for p in bad_p], empty={3: 0})
+    assert lib.pod_bias_act_to_nchw(X, Y, X, 1, 8, 1 << 38, 1, 0.3, 1, 0, None) == -1
+    # pod_absmax(x, n, amax, stream)
+    rejects(lib.pod_absmax, [X, 5, Y, None], [(0, None), (2, None), (1, -1), (0, M), (2, M2)], empty={1: 0})
+    # pod_wino_reduce(partials, n_splits, split_stride, bias, planes, HW, Kpad, K, relu, out_amax, stream): no empty exit
+    rejects(lib.pod_wino_reduce, [X, 2, 80, X, Y, 10, 8, 6, 1, None, None],
+            [(0, None), (4, None), (1, 0), (1, 17), (5, 0), (6, 0), (6, 3), (6, 6), (7, 0), (7, 9), (2, 79), (2, 76), (2, 82), (0, M), (4, M), (3, M)])
+    # pod_expand_dropout(src, dst, n, copies, p, seed, offset, epoch, stream)
+    rejects(lib.pod_expand_dropout, [X, Y, 8, 2, 0.3, 1, 0, None, None],
+            [(0, None), (1, None), (2, -4), (2, 6), (3, 0), (0, M), (1, M)] + [(4, p) for p in bad_p], empty={2: 0})
+    # pod_bias_act(x, bias, residual, res_bias, n, C, HW, relu, p, seed, offset, stream)
+    rejects(lib.pod_bias_act, [X, X, Y, X, 12, 2, 3, 1, 0.3, 1, 0, None],
+            [(0, None), (4, -12), (5, 0), (6, 0), (0, M), (2, M), (2, None)] + [(8, p) for p in bad_p], empty={4: 0})
+    assert lib.pod_bias_act(X, X, Y, X, 12, 5, 1, 1, 0.3, 1, 0, None) == -1            # n is not a multiple of C * HW
+    assert lib.pod_bias_act(X, X, Y, X, 12, 2, 4, 1, 0.3, 1, 0, None) == -1
+    # pod_relu_dropout(x, n, p, seed, offset, stream)
+    rejects(lib.pod_relu_dropout, [X, 5, 0.3, 1, 0, None], [(0, None), (1, -1), (0, M)] + [(2, p) for p in bad_p], empty={1: 0})
+    # pod_reduce_partials(partials, n_splits, split_stride, bias, residual, y, n, Cout, relu, out_amax, stream)
+    rejects(lib.pod_reduce_partials, [X, 2, 16, X, X, Y, 16, 8, 1, None, None],
+            [(0, None), (5, None), (1, 0), (1, 17), (7, 0), (7, 3), (7, 6), (0, M), (5, M), (3, M), (4, M)], empty={6: 0})
+    for a in ([X, 2, 16, X, X, Y, -8, 8, 1, None, None], [X, 2, 32, X, X, Y, 18, 8, 1, None, None], [X, 2, 16, X, X, Y, 12, 8, 1, None, None],
+              [X, 2, 12, X, X, Y, 16, 8, 1, None, None], [X, 2, 18, X, X, Y, 16, 8, 1, None, None]):
+        assert lib.pod_reduce_partials(*a) == -1, a                                      # n < 0, n % 4, n % Cout, a short / odd split stride
+    # pod_relu_dropout_backward(out, d_out, d_z, n, p, dz_amax, stream)
+    rejects(lib.pod_relu_dropout_backward, [X, X, Y, 8, 0.3, None, None],
+            [(0, None), (1, None), (2, None), (3, -4), (3, 6), (0, M), (1, M), (2, M)] + [(4, p) for p in bad_p], empty={3: 0})
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setenv("POD_MI355X_LIB", "/nonexistent/libpod_mi355x.so")
     monkeypatch.setattr(hip, "_lib", None)

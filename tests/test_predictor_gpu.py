@@ -509,3 +509,44 @@ def test_bias_act_to_nchw_is_transpose_then_bias_act(shape):
                                    hip.current_stream()), "bias_act")
         assert out.is_contiguous() and torch.equal(out, ref), (relu, p)
     assert lib.pod_bias_act_to_nchw(x.data_ptr(), x.data_ptr(), None, N, C, H * W, 1, 0.0, 0, 0, hip.current_stream()) == -1
+
+
+NHWC_SHAPES = [(2, 64, 8, 8), (1, 8, 3, 5), (2, 68, 9, 28), (1, 132, 7, 9)]     # full tiles / H*W % 4 != 0, C < 64 / ragged both ways / H*W = 63, three channel tiles
+
+
+@pytest.mark.parametrize("shape", NHWC_SHAPES)
+def test_bias_act_to_nhwc_is_bias_relu_then_permute(shape):
+    """pod_bias_act_to_nhwc == relu?(src + b[c]) permuted to (N, H*W, C): one add and one max per element, so exactly."""
+    from pod_compare_amd import hip
+    lib = hip.load()
+    N, C, H, W = shape
+    g = torch.Generator(device="cuda").manual_seed(N * C + H)
+    x = torch.randn(shape, device="cuda", generator=g)
+    b = torch.randn(C, device="cuda", generator=g)
+    for bias in (b, None):
+        for relu in (0, 1):
+            out = torch.full((N, H * W, C), float("nan"), device="cuda")
+            hip.check(lib.pod_bias_act_to_nhwc(x.data_ptr(), out.data_ptr(), hip.ptr(bias), N, C, H * W, relu, hip.current_stream()), "to_nhwc")
+            ref = x if bias is None else x + b.view(1, -1, 1, 1)
+            ref = torch.relu(ref) if relu else ref
+            assert torch.equal(out, ref.reshape(N, C, H * W).permute(0, 2, 1).contiguous()), (bias is not None, relu)
+    assert lib.pod_bias_act_to_nhwc(x.data_ptr(), x.data_ptr(), None, N, C, H * W, 1, hip.current_stream()) == -1      # src == dst
+    out = torch.empty(N * H * W * (C + 2), device="cuda")
+    assert lib.pod_bias_act_to_nhwc(x.data_ptr(), out.data_ptr(), None, N, C + 2, H * W, 1, hip.current_stream()) == -1   # C % 4 != 0
+
+
+@pytest.mark.parametrize("n, views", [(240, [(4, 1), (1, 240), (80, 3)]), (242, [(2, 121), (242, 1)])])     # NHWC, planes, per-element / with the tail
+def test_one_dropout_mask_whichever_variant(n, views):
+    """One flat buffer, one (p, seed, offset), neither bias nor residual: every layout of pod_bias_act -- (C, H*W) picks it -- draws
+    the mask pod_relu_dropout draws, the n % 4 tail included."""
+    from pod_compare_amd import hip
+    lib = hip.load()
+    x = torch.randn(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(n))
+    p, seed, off = 0.3, 77, 3 << 34
+    want = x.clone()
+    hip.check(lib.pod_relu_dropout(want.data_ptr(), n, p, seed, off, hip.current_stream()), "pod_relu_dropout")
+    assert 0 < int((want != 0).sum()) < int((x > 0).sum())                  # a mask was drawn
+    for C, HW in views:
+        y = x.clone()
+        hip.check(lib.pod_bias_act(y.data_ptr(), None, None, None, n, C, HW, 1, p, seed, off, hip.current_stream()), "pod_bias_act")
+        assert torch.equal(y, want), (C, HW)
