@@ -745,6 +745,37 @@ int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t* level_hw, 
                       int32_t Kpad, const float* x_amax, const float* dy_amax, float* dW, float* db, float* partials, pod_stream_t stream);
 int pod_relu_dropout_backward(const float* out, const float* d_out, float* d_z, int64_t n, float p, float* dz_amax, pod_stream_t stream);
 
+/* ---- K23  backward of the FPN (csrc/k23_fpn_backward.hip) ------------------------------------------------------------
+ * Serves: the backward pass of detectron2's FPN + LastLevelP6P7 under train_net.py's training loop (the reference gets it from autograd).
+ * The output convolutions are K22's; their input gradients and p7's run on pod_conv1x1_split.  What is new: a weight gradient whose
+ * reduction runs over pixels with no taps, and the two gathers of the top-down path and of p7's input.  Four new symbols under
+ * POD_ABI_VERSION 18, as for K20 - K22: no entry or structure that existed changed, so the number stands.
+ *
+ * pod_conv1x1_wgrad: x dev (pixels, C) and dy dev (pixels, K), channels-last fp32.  dW dev fp32 (K, C): dW[k][c] = sum over pixels of
+ *   dy[p][k] x[p][c]; db dev fp32 (K) or NULL: the column sums of dy.  The weight gradient of a 1x1 convolution -- and, with x the patch
+ *   matrix of pod_im2col3x3s2_cl, of a 3x3 / stride-2 one, laid out (K, ty, tx, Cin).  C % 16 == 0, C <= 18432, K % 64 == 0, K <= 512,
+ *   pixels >= 1.  Arithmetic as pod_conv3x3_wgrad: every product on the f16 matrix cores from the two-term f16 splits of BOTH operands,
+ *   scaled by the powers of two their abs-max records give (x_amax / dy_amax), three partial products, fp32 accumulate.  The pixels are cut
+ *   into slices of 1024 pixels, halved down to 128 while slices x (K / 64) x ceil(C / 128) < 512 -- the geometry alone; each slice writes
+ *   partial sums into `partials` (dev, 16-byte aligned, pod_conv1x1_wgrad_partials(...) floats; 0 = invalid geometry) and a second launch
+ *   adds them in slice order in fp64 (db: fp64 column sums over chunks of 4096 pixels, added in chunk order): no atomics, two launches
+ *   give the same bits.
+ * pod_col2im3x3s2_cl: the input gradient of pod_im2col3x3s2_cl for one image.  dcols dev (Ho * Wo, 9 C), Ho = (H - 1) / 2 + 1,
+ *   Wo = (W - 1) / 2 + 1, taps in (ty, tx) order; dx dev (H * W, C):
+ *   dx[(y, x)][c] = (gate == NULL or gate[(y, x)][c] > 0 ? sum of dcols[(oy, ox)][(ty, tx, c)] over the taps with 2 oy + ty - 1 == y and
+ *   2 ox + tx - 1 == x : 0) + (add == NULL ? 0 : add[(y, x)][c]) -- at most four terms, ty then tx ascending.  gate, add: dev (H * W, C);
+ *   add may be dx.  C % 4 == 0.  dx_amax: NULL or the zeroed record that receives max |dx|.
+ * pod_upsample2_sum_cl: the backward of `lateral + F.interpolate(top_down, scale_factor=2, mode="nearest")` towards top_down (the
+ *   inverse of POD_C1_RESIDUAL_UP2).  d_child dev (h * w, C); add, d_top dev (((h + 1) / 2) * ((w + 1) / 2), C):
+ *   d_top[(Y, X)] = add[(Y, X)] + sum of d_child[(y, x)] over y >> 1 == Y, x >> 1 == X, y < h, x < w, y then x ascending.  add may be
+ *   d_top.  C % 4 == 0.  d_top_amax: NULL or the zeroed record that receives max |d_top|. */
+int64_t pod_conv1x1_wgrad_partials(int64_t pixels, int32_t C, int32_t K);
+int pod_conv1x1_wgrad(const float* x, const float* dy, int64_t pixels, int32_t C, int32_t K, const float* x_amax, const float* dy_amax, float* dW,
+                      float* db, float* partials, pod_stream_t stream);
+int pod_col2im3x3s2_cl(const float* dcols, const float* gate, const float* add, float* dx, int32_t H, int32_t W, int32_t C, float* dx_amax,
+                       pod_stream_t stream);
+int pod_upsample2_sum_cl(const float* d_child, int32_t h, int32_t w, const float* add, float* d_top, int32_t C, float* d_top_amax, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

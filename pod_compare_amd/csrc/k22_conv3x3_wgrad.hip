@@ -21,13 +21,12 @@
 //
 // pod_relu_dropout_backward: the gate of a trunk layer.  The layer's stored output is relu(z) keep / (1 - p) (pod_wino.h's store pass:
 // scale = 1.0f / (1.0f - p), exact zeros where dropped), so it is its own mask: dZ = dOut (out > 0) / (1 - p).
-#include "pod_split_gemm.h"
+#include "pod_wgrad.h"
 
 namespace pod {
 
 constexpr int WG_STEPS = 256;      // steps (16-pixel row segments) of one slice: a function of nothing
 constexpr int WG_LS = 18;          // LDS row stride, floats
-constexpr int WG_DB_CHUNK = 4096;  // pixels of one db partial
 
 struct WgradGeom {
     int32_t n_levels, copies, total_steps, reserved;
@@ -185,43 +184,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad(const float* __restric
     }
 }
 
-// fp64 column sums of dY over one chunk of pixels: dbp[chunk][k < Kpad]
-__global__ void __launch_bounds__(256) k_wgrad_db(const float* __restrict__ dY, const int64_t pixels, const int Kpad, double* __restrict__ dbp) {
-    __shared__ double red[16][64];
-    const int t = threadIdx.x, q4 = t & 15, pr = t >> 4, k0 = blockIdx.y * 64;
-    const int64_t p0 = (int64_t)blockIdx.x * WG_DB_CHUNK;
-    const int64_t p1 = p0 + WG_DB_CHUNK < pixels ? p0 + WG_DB_CHUNK : pixels;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int64_t p = p0 + pr; p < p1; p += 16) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(dY + p * Kpad + k0 + 4 * q4);
-        s0 += (double)v.x; s1 += (double)v.y; s2 += (double)v.z; s3 += (double)v.w;
-    }
-    red[pr][4 * q4 + 0] = s0; red[pr][4 * q4 + 1] = s1; red[pr][4 * q4 + 2] = s2; red[pr][4 * q4 + 3] = s3;
-    __syncthreads();
-    if (t < 64) {
-        double a = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) a += red[q][t];
-        dbp[(int64_t)blockIdx.x * Kpad + k0 + t] = a;
-    }
-}
-
-// the slices' partials in slice order -> dW (K, C, 3, 3); the chunks' column sums in chunk order -> db (K)
-__global__ void __launch_bounds__(256) k_wgrad_reduce(const float* __restrict__ partials, const int n_slices, const double* __restrict__ dbp, const int n_chunks,
-                                                      const int C, const int K, const int Kpad, float* __restrict__ dW, float* __restrict__ db) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_w = (int64_t)9 * K * C;
-    if (i < n_w) {
-        const int c = (int)(i % C), k = (int)((i / C) % K), tap = (int)(i / ((int64_t)C * K));
-        double a = 0.0;
-        for (int s = 0; s < n_slices; ++s) a += (double)partials[(((int64_t)s * 9 + tap) * Kpad + k) * C + c];
-        dW[((int64_t)k * C + c) * 9 + tap] = (float)a;
-    } else if (i - n_w < K) {
-        const int k = (int)(i - n_w);
-        double a = 0.0;
-        for (int ch = 0; ch < n_chunks; ++ch) a += dbp[(int64_t)ch * Kpad + k];
-        db[k] = (float)a;
-    }
-}
+// (the db partials and the second launch that adds the slices in order: pod_wgrad.h, shared with k23_fpn_backward.hip)
 
 __global__ void __launch_bounds__(256) k_relu_dropout_backward(const float* __restrict__ out, const float* d_out, float* d_z, const int64_t n4, const float scale,
                                                                float* __restrict__ amax) {
@@ -288,13 +251,13 @@ extern "C" int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t*
     double* dbp = reinterpret_cast<double*>(partials);
     float* wp = partials + 2 * n_chunks * Kpad;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pod::k_wgrad_db, dim3((unsigned)n_chunks, (unsigned)(Kpad / 64)), dim3(256), 0, s, dy, pixels, Kpad, dbp);
+    hipLaunchKernelGGL(pod::k_wgrad_db<pod::WG_DB_CHUNK>, dim3((unsigned)n_chunks, (unsigned)(Kpad / 64)), dim3(256), 0, s, dy, pixels, Kpad, dbp);
     POD_CHECK_LAUNCH();
     hipLaunchKernelGGL(pod::k_conv3x3_wgrad, dim3((unsigned)n_slices, (unsigned)(Kpad / 64), (unsigned)((C + 63) / 64)), dim3(256), 0, s, x, dy, G, C, K, Kpad,
                        x_amax, dy_amax, wp);
     POD_CHECK_LAUNCH();
     const int64_t n_out = (int64_t)9 * K * C + K;
-    hipLaunchKernelGGL(pod::k_wgrad_reduce, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, Kpad, dW, db);
+    hipLaunchKernelGGL(pod::k_wgrad_reduce<9>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, Kpad, dW, db);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }

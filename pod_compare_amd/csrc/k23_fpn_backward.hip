@@ -1,0 +1,251 @@
+// K23: what the FPN's backward pass needs beyond K22 and the forward GEMM (include/pod_mi355x.h).
+//
+// pod_conv1x1_wgrad: dW[k][c] = sum over pixels of dY[p][k] X[p][c], db[k] = sum dY[.][k] -- the weight gradient of a 1x1 convolution
+// (the laterals) and, on the patch matrix of pod_im2col3x3s2_cl, of the stride-2 convolutions p6 / p7.  K22's arithmetic without its taps:
+// a GEMM with M = K, N = C and the PIXELS as the reduction on v_mfma_f32_32x32x16_f16, both operands split at run time into two f16
+// terms of their power-of-two-scaled values (scales from their abs-max records), three partial products, small ones first, fp32 accumulate.
+//
+// A workgroup of four wavefronts owns 64 k x 128 c: wave (kb, cw) keeps two 32 x 32 accumulator blocks, k block kb against the two c
+// blocks of c half cw, so a split dY fragment meets two X fragments (K22 has nine blocks per fragment pair, one per tap; here the width
+// of the c tile is what a staged dY fragment is spread over).  The reduction unit is a STEP of 32 consecutive pixels: the step's rows come
+// from memory as they lie there -- whole 256-byte (dY) and 512-byte (X) runs, 16 bytes a lane -- into LDS [pixel 32][channel + pad], and
+// the MFMA's operand, 8 consecutive pixels of one channel per lane, is read back down the columns (8 ds_read_b32: the 32 lanes of a
+// half-wave read 32 consecutive channels of one pixel, conflict-free whatever the row stride).  The next step's rows are asked for ahead of
+// the current step's products.  A pixel tail and a channel-tile edge are zero-filled in the staging, never read.
+//
+// Parallelism and determinism: the pixels are cut into SLICES of c1w_slice_pixels(pixels, C, K) consecutive pixels -- the geometry alone:
+// 1024, halved down to 128 while the launch has fewer than 512 workgroups; grid = slices x k tiles x c tiles.  A slice writes its
+// partial sums [slice][k][c], and pod_wgrad.h's second launch adds them in slice order, in fp64 (db: fp64 column sums over chunks of
+// 4096 pixels).  No atomics: two launches give the same bits.
+//
+// pod_col2im3x3s2_cl, pod_upsample2_sum_cl: the two gathers of the backward pass -- the input gradient of pod_im2col3x3s2_cl (with the
+// ReLU gate of p7's input and the gradient p6 already has), and the backward of the nearest top-down sum at factor two.  One thread per
+// 16 bytes of the result, a fixed order of at most four terms, the result's abs-max record published by the same pass.
+#include "pod_wgrad.h"
+
+namespace pod {
+
+constexpr int C1W_STEP = 32;            // pixels of one step
+constexpr int C1W_KT = 64, C1W_CT = 128;
+constexpr int C1W_DS = C1W_KT + 4;      // LDS row strides, floats (16-byte rows; any stride serves the column reads)
+constexpr int C1W_XS = C1W_CT + 4;
+constexpr int C1W_MAX_C = 18432;        // p6's patch matrix: 9 x 2048
+
+// Host and device agree on the slices through this function of the geometry alone.
+static inline int c1w_slice_pixels(int64_t pixels, int C, int K) {
+    const int64_t tiles = (int64_t)(K / C1W_KT) * ((C + C1W_CT - 1) / C1W_CT);
+    int s = 1024;
+    while (s > 128 && ((pixels + s - 1) / s) * tiles < 512) s >>= 1;
+    return s;
+}
+
+__global__ void __launch_bounds__(256, 2) k_conv1x1_wgrad(const float* __restrict__ X, const float* __restrict__ dY, const int64_t pixels, const int C, const int K,
+                                                       const int slice_px, const float* __restrict__ x_amax, const float* __restrict__ dy_amax,
+                                                       float* __restrict__ partials) {
+    __shared__ __attribute__((aligned(16))) float ds[C1W_STEP * C1W_DS];
+    __shared__ __attribute__((aligned(16))) float xs[C1W_STEP * C1W_XS];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i32 = lane & 31, h = lane >> 5, kb = wave & 1, cw = wave >> 1;
+    const int slice = blockIdx.x, k0 = blockIdx.y * C1W_KT, c0 = blockIdx.z * C1W_CT;
+    const float sx = sg_activation_scale(x_amax), sd = sg_activation_scale(dy_amax);
+    const int64_t p_begin = (int64_t)slice * slice_px;
+    const int64_t p_end = p_begin + slice_px < pixels ? p_begin + slice_px : pixels;
+    // staging: dY 32 pixels x 16 channel quads = 2 quads a thread, X 32 pixels x 32 quads = 4 quads a thread
+    const int dq = t & 15, dp = t >> 4;          // dY: quad, pixel (+ 16 for the second)
+    const int xq = t & 31, xp = t >> 5;          // X: quad, pixel (+ 8 j)
+    const bool x_in = c0 + 4 * xq < C;           // (C % 16 == 0: a quad is inside or outside as a whole)
+
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dreg[2], xreg[4];
+    auto load = [&](int64_t p0) {                // the step's rows -> registers, zeros past the slice's last pixel and past C
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t p = p0 + dp + 16 * j;
+            dreg[j] = p < p_end ? *reinterpret_cast<const f32x4*>(dY + p * K + k0 + 4 * dq) : zero4;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t p = p0 + xp + 8 * j;
+            xreg[j] = (p < p_end && x_in) ? *reinterpret_cast<const f32x4*>(X + p * C + c0 + 4 * xq) : zero4;
+        }
+    };
+
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 acc[2] = {zero16, zero16};
+
+    load(p_begin);
+    for (int64_t p0 = p_begin; p0 < p_end; p0 += C1W_STEP) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(ds + (dp + 16 * j) * C1W_DS + 4 * dq) = dreg[j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(xs + (xp + 8 * j) * C1W_XS + 4 * xq) = xreg[j];
+        __syncthreads();
+        if (p0 + C1W_STEP < p_end) load(p0 + C1W_STEP);      // (uniform) in flight behind the products below
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (p0 + 16 * s >= p_end) break;                 // (uniform) a half step of zeros
+            // the lane's 8 pixels 16 s + 8 h .. + 7 of channel 32 kb + i32 of dY, split
+            sg_u32x4 dyf[2];
+            {
+                const float* p = ds + (16 * s + 8 * h) * C1W_DS + 32 * kb + i32;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    uint32_t w[2];
+                    wino_f16_split2(p[(2 * m) * C1W_DS], p[(2 * m + 1) * C1W_DS], sd, w);
+                    dyf[0][m] = w[0];
+                    dyf[1][m] = w[1];
+                }
+            }
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                sg_u32x4 xf[2];
+                const float* p = xs + (16 * s + 8 * h) * C1W_XS + 64 * cw + 32 * cb + i32;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    uint32_t w[2];
+                    wino_f16_split2(p[(2 * m) * C1W_XS], p[(2 * m + 1) * C1W_XS], sx, w);
+                    xf[0][m] = w[0];
+                    xf[1][m] = w[1];
+                }
+                // small products first (as k12 / k13 / k22)
+                f32x16 a = acc[cb];
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[1]), a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[1]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
+                acc[cb] = a;
+            }
+        }
+        __syncthreads();
+    }
+
+    // partial sums [slice][k < K][c < C]: accumulator register j of a lane is row (j & 3) + 8 (j >> 2) + 4 h, column i32
+    const float inv = wino_pow2_inverse(sx) * wino_pow2_inverse(sd);
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        const int c = c0 + 64 * cw + 32 * cb + i32;
+        if (c < C) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = k0 + 32 * kb + (j & 3) + 8 * (j >> 2) + 4 * h;
+                partials[((int64_t)slice * K + k) * C + c] = acc[cb][j] * inv;
+            }
+        }
+    }
+}
+
+// dx[(y, x)][c] = gate(sum of the entries of dcols that read pixel (y, x)) + add: tap (ty, tx) of output pixel (oy, ox) read input pixel
+// (2 oy + ty - 1, 2 ox + tx - 1), so pixel (y, x) is met by oy = (y + 1 - ty) / 2 where that is integral and in range -- ty, tx ascending.
+__global__ void __launch_bounds__(256) k_col2im3x3s2_cl(const float* __restrict__ dcols, const float* __restrict__ gate, const float* add, float* dx, const int H,
+                                                        const int W, const int Ho, const int Wo, const int C4, float* __restrict__ amax) {
+    const int64_t n = (int64_t)H * W * C4, stride = (int64_t)gridDim.x * blockDim.x;
+    float m = 0.0f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int c4 = (int)(i % C4);
+        const int64_t pix = i / C4;
+        const int x = (int)(pix % W), y = (int)(pix / W);
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ty = 0; ty < 3; ++ty) {
+            const int ny = y + 1 - ty, oy = ny >> 1;
+            if (ny < 0 || (ny & 1) || oy >= Ho) continue;
+#pragma unroll
+            for (int tx = 0; tx < 3; ++tx) {
+                const int nx = x + 1 - tx, ox = nx >> 1;
+                if (nx < 0 || (nx & 1) || ox >= Wo) continue;
+                v += *reinterpret_cast<const f32x4*>(dcols + ((((int64_t)oy * Wo + ox) * 9 + ty * 3 + tx) * C4 + c4) * 4);
+            }
+        }
+        if (gate) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(gate + i * 4);
+            v.x = g.x > 0.f ? v.x : 0.f;
+            v.y = g.y > 0.f ? v.y : 0.f;
+            v.z = g.z > 0.f ? v.z : 0.f;
+            v.w = g.w > 0.f ? v.w : 0.f;
+        }
+        if (add) v += *reinterpret_cast<const f32x4*>(add + i * 4);
+        *reinterpret_cast<f32x4*>(dx + i * 4) = v;
+        m = wino_absmax4(m, v);
+    }
+    if (amax) wino_publish_amax_block(amax, m);      // (uniform: every thread of the workgroup calls it)
+}
+
+// d_top[(Y, X)] = add[(Y, X)] + the children (2 Y + dy, 2 X + dx) of d_child that exist, dy then dx ascending
+__global__ void __launch_bounds__(256) k_upsample2_sum_cl(const float* __restrict__ d_child, const int h, const int w, const float* add, float* d_top, const int Ht,
+                                                          const int Wt, const int C4, float* __restrict__ amax) {
+    const int64_t n = (int64_t)Ht * Wt * C4, stride = (int64_t)gridDim.x * blockDim.x;
+    float m = 0.0f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int c4 = (int)(i % C4);
+        const int64_t pix = i / C4;
+        const int X = (int)(pix % Wt), Y = (int)(pix / Wt);
+        f32x4 v = *reinterpret_cast<const f32x4*>(add + i * 4);
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int y = 2 * Y + dy, x = 2 * X + dx;
+                if (y < h && x < w) v += *reinterpret_cast<const f32x4*>(d_child + (((int64_t)y * w + x) * C4 + c4) * 4);
+            }
+        *reinterpret_cast<f32x4*>(d_top + i * 4) = v;
+        m = wino_absmax4(m, v);
+    }
+    if (amax) wino_publish_amax_block(amax, m);      // (uniform)
+}
+
+// Host: false = outside what the kernel addresses.
+static bool c1w_geometry(int64_t pixels, int32_t C, int32_t K) {
+    return pixels >= 1 && pixels <= 0x3FFFFFFF && C >= 16 && (C & 15) == 0 && C <= C1W_MAX_C && K >= 64 && (K & 63) == 0 && K <= 512;
+}
+
+}  // namespace pod
+
+extern "C" int64_t pod_conv1x1_wgrad_partials(int64_t pixels, int32_t C, int32_t K) {
+    if (!pod::c1w_geometry(pixels, C, K)) return 0;
+    const int sp = pod::c1w_slice_pixels(pixels, C, K);
+    const int64_t n_slices = (pixels + sp - 1) / sp, n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
+    return 2 * n_chunks * K + n_slices * K * C;
+}
+
+extern "C" int pod_conv1x1_wgrad(const float* x, const float* dy, int64_t pixels, int32_t C, int32_t K, const float* x_amax, const float* dy_amax, float* dW,
+                                 float* db, float* partials, pod_stream_t stream) {
+    if (!x || !dy || !x_amax || !dy_amax || !dW || !partials) return POD_E_INVALID;
+    if (!pod::c1w_geometry(pixels, C, K)) return POD_E_INVALID;
+    if (!pod_aligned(16, x, dy, partials)) return POD_E_INVALID;
+    const int sp = pod::c1w_slice_pixels(pixels, C, K);
+    const int64_t n_slices = (pixels + sp - 1) / sp, n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
+    double* dbp = reinterpret_cast<double*>(partials);
+    float* wp = partials + 2 * n_chunks * K;
+    hipStream_t s = (hipStream_t)stream;
+    if (db) {
+        hipLaunchKernelGGL(pod::k_wgrad_db<pod::WG_DB_CHUNK>, dim3((unsigned)n_chunks, (unsigned)(K / 64)), dim3(256), 0, s, dy, pixels, K, dbp);
+        POD_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(pod::k_conv1x1_wgrad, dim3((unsigned)n_slices, (unsigned)(K / pod::C1W_KT), (unsigned)((C + pod::C1W_CT - 1) / pod::C1W_CT)), dim3(256), 0, s, x, dy,
+                       pixels, C, K, sp, x_amax, dy_amax, wp);
+    POD_CHECK_LAUNCH();
+    const int64_t n_out = (int64_t)K * C + (db ? K : 0);
+    hipLaunchKernelGGL(pod::k_wgrad_reduce<1>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, K, dW, db);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}
+
+extern "C" int pod_col2im3x3s2_cl(const float* dcols, const float* gate, const float* add, float* dx, int32_t H, int32_t W, int32_t C, float* dx_amax,
+                                  pod_stream_t stream) {
+    if (!dcols || !dx || dcols == dx || gate == dx || H < 1 || W < 1 || H > 16384 || W > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, dcols, gate, add, dx) || !pod_aligned(4, dx_amax)) return POD_E_INVALID;
+    const int32_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int64_t n4 = (int64_t)H * W * (C / 4);
+    hipLaunchKernelGGL(pod::k_col2im3x3s2_cl, dim3(pod_grid_stride_blocks(n4, 4096)), dim3(256), 0, (hipStream_t)stream, dcols, gate, add, dx, H, W, Ho, Wo, C / 4, dx_amax);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}
+
+extern "C" int pod_upsample2_sum_cl(const float* d_child, int32_t h, int32_t w, const float* add, float* d_top, int32_t C, float* d_top_amax, pod_stream_t stream) {
+    if (!d_child || !add || !d_top || d_child == d_top || h < 1 || w < 1 || h > 16384 || w > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, d_child, add, d_top) || !pod_aligned(4, d_top_amax)) return POD_E_INVALID;
+    const int32_t Ht = (h + 1) / 2, Wt = (w + 1) / 2;
+    const int64_t n4 = (int64_t)Ht * Wt * (C / 4);
+    hipLaunchKernelGGL(pod::k_upsample2_sum_cl, dim3(pod_grid_stride_blocks(n4, 4096)), dim3(256), 0, (hipStream_t)stream, d_child, h, w, add, d_top, Ht, Wt, C / 4, d_top_amax);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}

@@ -1,0 +1,185 @@
+"""The FPN with a backward pass: detectron2's FPN + LastLevelP6P7 (probabilistic_retinanet.py:96-100, `self.backbone(images.tensor)`) in
+training mode under train_net.py's loop, as ONE torch.autograd.Function over the whole FPN.
+
+Forward: FPN.forward_cl's own launches, per image, unchanged; the summed laterals l3, l4, l5 and p6 of every image are kept, the two
+patch matrices are re-formed in backward.  Backward, on the B images at once (a weight gradient sums over pixels, whichever image
+they are of):
+    p7               dW, db = pod_conv1x1_wgrad(cols(relu p6), dP7); dcols = dP7 W9 on pod_conv1x1_split; dP6 = pod_col2im3x3s2_cl(dcols,
+                     gate = p6, add = the gradient p6 has from the head)
+    p6               dW, db = pod_conv1x1_wgrad(cols(c5), dP6) -- c5 is the frozen backbone's: no input gradient
+    output convs     dW, db = pod_conv3x3_wgrad(l_i, dP_i) (K22); dL_i = the GEMM of dP_i's patch matrix with the flipped, transposed filter
+                     (head_train.input_grad_gemm)
+    top-down         dL4 += up2_sum(dL3), dL5 += up2_sum(dL4) (pod_upsample2_sum_cl), l3 first
+    laterals         dW, db = pod_conv1x1_wgrad(c_i, dL_i); nothing reaches below them
+GPU only -- anything this path cannot take raises (hip.PodError): there is no fallback."""
+from typing import List, Sequence, Tuple
+
+import torch
+
+from . import amax, hip, wgrad
+from .head_train import input_grad_gemm, patch_matrix
+
+
+def fpn_convs(fpn) -> list:
+    """The FPN's eight convolutions in the order their parameters enter the autograd function."""
+    return list(fpn.lateral) + list(fpn.output) + [fpn.p6, fpn.p7]
+
+
+def _require(fpn) -> None:
+    from . import modeling, wino
+    from .conv1x1 import Conv3x3S2
+    K = fpn.p6.out_channels
+    ok = (len(fpn.lateral) == 3 and fpn.cl_eligible() and modeling.HIP_P6P7 and modeling.WINO_BACKBONE and bool(wino.SPLIT_BF16)
+          and Conv3x3S2.eligible(fpn.p6) and Conv3x3S2.eligible(fpn.p7) and fpn.p6.bias is not None and fpn.p7.bias is not None
+          and all(c.out_channels == K for c in fpn_convs(fpn)) and fpn.p7.in_channels == K and 9 * fpn.p6.in_channels <= 18432)
+    if not ok:
+        raise hip.PodError("fpn_forward_train: this FPN has no HIP training path (three biased 1x1 laterals of Cin % 16 == 0, 3x3 output convs and "
+                           "stride-2 p6 / p7 of one width in (64, 128, 256, 512), the split kernels selected)")
+
+
+def _dcols_gemm(conv):
+    """dcols = dY W9, W9 (K, ty, tx, Cin) the stride-2 conv's filter in the patch matrix's column order: a GEMM with the transposed filter on
+    pod_conv1x1_split, split once and cached by the weight's version (modeling._derived)."""
+    from . import modeling
+    from .conv1x1 import Conv1x1
+
+    def make(c):
+        K, C = c.out_channels, c.in_channels
+        w9 = c.weight.detach().permute(0, 2, 3, 1).reshape(K, 9 * C)
+        try:
+            return Conv1x1(w9.t().reshape(9 * C, K, 1, 1).contiguous(), None, 1)
+        except ValueError as e:
+            raise hip.PodError("FPN backward: the input gradient of a stride-2 {} -> {} conv has no pod_conv1x1_split form ({})".format(C, K, e))
+    return modeling._derived(conv, "_pod_dcols_gemm", make)
+
+
+def _cols(x: torch.Tensor, h: int, w: int, relu: bool, out: torch.Tensor) -> None:
+    hip.check(hip.load().pod_im2col3x3s2_cl(x.data_ptr(), out.data_ptr(), int(h), int(w), int(x.shape[1]), 1 if relu else 0, hip.current_stream()),
+              "pod_im2col3x3s2_cl")
+
+
+def _batched_cols(maps: Sequence[torch.Tensor], h: int, w: int, relu: bool) -> torch.Tensor:
+    """The patch matrices of B maps of one size, image after image (the images' own abs-max records bound them: entries are theirs or zero)."""
+    ho, wo, C = (h - 1) // 2 + 1, (w - 1) // 2 + 1, int(maps[0].shape[1])
+    cols = torch.empty((len(maps) * ho * wo, 9 * C), dtype=torch.float32, device=maps[0].device)
+    for b, m in enumerate(maps):
+        _cols(m, h, w, relu, cols[b * ho * wo:(b + 1) * ho * wo])
+    return amax.joined(cols, *maps)
+
+
+def _stacked(maps: Sequence[torch.Tensor]) -> torch.Tensor:
+    return amax.joined(torch.cat(list(maps)), *maps)
+
+
+def _grad_cl(g, B: int, K: int, h: int, w: int, device) -> torch.Tensor:
+    """A level's gradient (B, K, h, w), any strides, or None -> channels-last (B h w, K), a tensor of this pass's own."""
+    if g is None:
+        return torch.zeros((B * h * w, K), dtype=torch.float32, device=device)
+    out = torch.empty((B * h * w, K), dtype=torch.float32, device=device)
+    out.view(B, h, w, K).copy_(g.permute(0, 2, 3, 1))
+    return out
+
+
+class _FpnTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fpn, feats, *params):
+        saved, per_image = [], []
+        for f in feats:
+            keep = {}
+            outs = fpn.forward_cl(f, keep=keep)
+            if not keep.get("hip_p6p7"):
+                raise hip.PodError("fpn_forward_train: p6 / p7 did not take the pod_im2col3x3s2_cl + pod_conv1x1_split path")
+            hw = [tuple(int(s) for s in o.shape[-2:]) for o in outs]
+            p6 = outs[3].permute(0, 2, 3, 1).reshape(hw[3][0] * hw[3][1], -1).clone()  # (a copy: a view would hold the image's five-level buffer until backward)
+            saved.append(dict(c=[t for t, _, _ in f], l=[keep["l3"], keep["l4"], keep["l5"]], p6=p6))
+            per_image.append(outs)
+        ctx.state = (fpn, saved, hw)
+        ctx.n_params = len(params)
+        return tuple(torch.cat([o[l] for o in per_image]).contiguous() for l in range(5))
+
+    @staticmethod
+    def backward(ctx, *g_levels):
+        fpn, saved, hw = ctx.state
+        B, K, dev = len(saved), fpn.p6.out_channels, saved[0]["p6"].device
+        dP = [_grad_cl(g, B, K, h, w, dev) for g, (h, w) in zip(g_levels, hw)]
+        (h5, w5), (h6, w6), (h7, w7) = hw[2], hw[3], hw[4]
+        grads = {}
+
+        # p7 on relu(p6): weight gradient on the patch matrix, dcols = dP7 W9, gathered back onto p6 behind the gate, plus p6's own gradient
+        p6s = [s["p6"] for s in saved]
+        dW, db = wgrad.conv1x1_wgrad(_batched_cols(p6s, h6, w6, True), dP[4])
+        grads[fpn.p7] = (dW.view(K, 3, 3, K).permute(0, 3, 1, 2).contiguous(), db)
+        dcols = _dcols_gemm(fpn.p7)(dP[4], B * h7 * w7, 1)
+        rec, n6, n7 = amax.word(dev), h6 * w6, h7 * w7
+        for b in range(B):
+            wgrad.col2im3x3s2_cl(dcols[b * n7:(b + 1) * n7], h6, w6, gate=p6s[b], add=dP[3][b * n6:(b + 1) * n6], out=dP[3][b * n6:(b + 1) * n6], record=rec)
+        amax.attach(dP[3], rec)
+        # p6 on c5
+        C5 = fpn.p6.in_channels
+        dW, db = wgrad.conv1x1_wgrad(_batched_cols([s["c"][2] for s in saved], h5, w5, False), dP[3])
+        grads[fpn.p6] = (dW.view(K, 3, 3, C5).permute(0, 3, 1, 2).contiguous(), db)
+        # output convs: K22 for the weights, the GEMM of the gradient's patch matrix for the summed laterals' gradient
+        dL = []
+        for i in range(3):
+            level, conv = [hw[i]], fpn.output[i]
+            grads[conv] = wgrad.conv3x3_wgrad(_stacked([s["l"][i] for s in saved]), dP[i], level, B, K)
+            dL.append(input_grad_gemm(conv)(patch_matrix(dP[i], level, B), int(dP[i].shape[0]), 1))
+        # top-down, l3 first: a summed lateral's gradient also reaches the coarser one it was upsampled from
+        for i in (0, 1):
+            (h, w), rec = hw[i], amax.word(dev)
+            n, nt = h * w, ((h + 1) // 2) * ((w + 1) // 2)
+            for b in range(B):
+                wgrad.upsample2_sum_cl(dL[i][b * n:(b + 1) * n], h, w, dL[i + 1][b * nt:(b + 1) * nt], record=rec)
+            amax.attach(dL[i + 1], rec)
+        # laterals
+        for i in range(3):
+            dW, db = wgrad.conv1x1_wgrad(_stacked([s["c"][i] for s in saved]), dL[i])
+            grads[fpn.lateral[i]] = (dW.view(K, -1, 1, 1), db)
+        flat = []
+        for conv in fpn_convs(fpn):
+            flat += list(grads[conv])
+        assert len(flat) == ctx.n_params
+        ctx.state = None
+        return (None, None) + tuple(flat)
+
+
+def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int]]]) -> List[torch.Tensor]:
+    """feats: per image the [(c3, h, w), (c4, h, w), (c5, h, w)] of ResNet50.forward_cl, B images of one padded size.  Returns the per-level
+    (B, K, H, W) features; they carry a grad_fn that reaches every parameter of the FPN (and nothing below it)."""
+    feats = [list(f) for f in feats]
+    if not feats or any(len(f) != 3 for f in feats):
+        raise hip.PodError("fpn_forward_train: per image the three maps (c3, h, w), (c4, h, w), (c5, h, w)")
+    dev = feats[0][0][0].device
+    for f in feats:
+        for (t, h, w), (_, h0, w0), conv in zip(f, feats[0], fpn.lateral):
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+                    and tuple(t.shape) == (int(h) * int(w), conv.in_channels) and (int(h), int(w)) == (int(h0), int(w0))):
+                raise hip.PodError("fpn_forward_train runs on contiguous fp32 channels-last (h * w, C) maps of one size on one GPU: there is no CPU path")
+    _require(fpn)
+    (h3, w3), (h4, w4), (h5, w5) = [(int(h), int(w)) for _, h, w in feats[0]]
+    for (ht, wt), (h, w) in (((h4, w4), (h3, w3)), ((h5, w5), (h4, w4))):
+        if (ht, wt) != ((h + 1) // 2, (w + 1) // 2):
+            raise hip.PodError("fpn_forward_train: a top-down step from {} x {} to {} x {} is not a factor of two".format(ht, wt, h, w))
+    if fpn.p6.weight.device != dev:
+        raise hip.PodError("fpn_forward_train: the FPN is on {}, the maps on {}".format(fpn.p6.weight.device, dev))
+    params = []
+    for c in fpn_convs(fpn):
+        params += [c.weight, c.bias]
+    with torch.cuda.device(dev):
+        return list(_FpnTrain.apply(fpn, feats, *params))
+
+
+def backbone_maps(model, image: torch.Tensor):
+    """The frozen backbone of one frame, channels-last: ([(c3, h, w), (c4, h, w), (c5, h, w)], padded (h, w)) -- the part of
+    ProbabilisticRetinaNet._trunk_eager ahead of the FPN."""
+    from . import anchors
+    with torch.no_grad():
+        if (image.is_cuda and image.device == model.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
+                and image.dtype in (torch.uint8, torch.float32) and model._cl_backbone(model.pixel_mean) and model.bottom_up.hip_stem_ok()):
+            padded = anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
+            return model.bottom_up.forward_cl(None, frame=(image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded)), tuple(padded)
+        if image.is_cuda:
+            x = model.preprocess_image(image)
+            if model._cl_backbone(x):
+                return model.bottom_up.forward_cl(x), tuple(x.shape[-2:])
+    raise hip.PodError("training the FPN needs the channels-last HIP backbone (a frame on the model's GPU, FrozenBN folded, the split kernels selected)")

@@ -438,10 +438,11 @@ class FPN(_TracksStorage):
     def cl_eligible(self) -> bool:
         return all(_c1_ok(m) for m in self.lateral) and all(_w3_ok(m) for m in self.output)
 
-    def forward_cl(self, feats):
+    def forward_cl(self, feats, keep: Optional[dict] = None):
         """feats: [(c3, h, w), (c4, h, w), (c5, h, w)] channels-last buffers.  Lateral 1x1 convs on pod_conv1x1_split, top-down sums on
         channels-last views, output 3x3 convs on pod_wino_conv3x3[_split]; p6 / p7 (stride-2 3x3) as a patch matrix on pod_conv1x1_split (round 5; POD_HIP_P6P7=0: MIOpen on channels_last views).
-        Returns (1, 256, h, w) tensors with channels_last strides: the head lays them out channels-last anyway."""
+        Returns (1, 256, h, w) tensors with channels_last strides: the head lays them out channels-last anyway.  keep: a dict that receives
+        what a backward pass needs of this forward (fpn_train.py): the summed laterals l3, l4, l5 and whether the one-buffer path ran."""
         (c3, h3, w3), (c4, h4, w4), (c5, h5, w5) = feats
         l5 = c1_of(self.lateral[2])(c5, h5, w5)
         def lateral(conv, c, h, w, top, ht, wt):               # lateral + nearest-upsampled top-down map in one store
@@ -450,6 +451,8 @@ class FPN(_TracksStorage):
             return c1_of(conv)(c, h, w, residual=nchw_as_cl(F.interpolate(cl_as_nchw(top, ht, wt), size=(h, w), mode="nearest")))
         l4 = lateral(self.lateral[1], c4, h4, w4, l5, h5, w5)
         l3 = lateral(self.lateral[0], c3, h3, w3, l4, h4, w4)
+        if keep is not None:
+            keep.update(l3=l3, l4=l4, l5=l5, hip_p6p7=False)
         from . import amax
         from .conv1x1 import Conv3x3S2
         if HIP_P6P7 and Conv3x3S2.eligible(self.p6) and Conv3x3S2.eligible(self.p7) and self.output[0].out_channels == self.p6.out_channels == self.p7.out_channels:
@@ -472,6 +475,8 @@ class FPN(_TracksStorage):
             amax.attach(buf, rec)
             outs = [cl_as_nchw(t, h, w) for t, (h, w) in zip(parts, hw)]
             outs[0]._pod_cl_levels, outs[0]._pod_cl_version = buf, buf._version
+            if keep is not None:
+                keep["hip_p6p7"] = True
             return outs
         p3 = cl_as_nchw(wino_cl(self.output[0], l3, h3, w3, relu=False), h3, w3)
         p4 = cl_as_nchw(wino_cl(self.output[1], l4, h4, w4, relu=False), h4, w4)
@@ -824,8 +829,8 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
 
 class ProbabilisticRetinaNet(_TracksStorage):
     """PR:20-166, and `losses` (PR:168-333 with the labelling of PR:129-130) evaluated on the head outputs of a forward by the K21 kernels
-    (pod_compare_amd/losses.py).  The head's convolutions have a backward pass (head.forward_train, pod_compare_amd/head_train.py); the
-    backbone's and the FPN's have none: they stay frozen."""
+    (pod_compare_amd/losses.py).  The head's convolutions have a backward pass (head.forward_train, pod_compare_amd/head_train.py), and
+    so have the FPN's (pod_compare_amd/fpn_train.py); the ResNet's have none: it stays frozen."""
 
     def __init__(self, num_classes=7, dropout_rate=0.0, cls_var_loss="none", cls_var_num_samples=3,
                  bbox_cov_loss="none", bbox_cov_type="diagonal", test_score_thresh=0.05, test_topk_candidates=1000,

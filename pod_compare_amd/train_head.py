@@ -1,7 +1,7 @@
-"""Fine-tunes the HEAD of a ProbabilisticRetinaNet against its frozen backbone and FPN, on the GPU.
+"""Fine-tunes the HEAD of a ProbabilisticRetinaNet -- with --train-fpn, the FPN with it -- against its frozen backbone, on the GPU.
 
     python -m pod_compare_amd.train_head --coco-json <gt.json> --image-root <dir> --data-dir <checkpoints root> \
-        --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N]
+        --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
 shape together; a shape's frames wait until a batch of them is complete), the frozen backbone + FPN per image under no_grad through the
@@ -12,7 +12,11 @@ under detectron2's WarmupMultiStepLR; the solver settings are SOLVER.*.  Checkpo
 at the end: `apply_net --data-dir` loads them.  A checkpoint without variance predictors (retinanet_R_50_FPN_1x) under a config that has
 them fine-tunes into one that does: the predictors the file lacks start from their seeded initialisation.
 
-NOT the reference's full trainer: ResNet and FPN have no backward pass here and stay frozen (detectron2 trains everything above
+--train-fpn: the FPN's eight convolutions join the parameters.  The backbone still runs per image under no_grad, up to c3 - c5; the FPN
+then runs with a backward pass of its own (pod_compare_amd/fpn_train.py: K22 for its output convolutions, K23 for the laterals, p6 / p7
+and the top-down path), fed by the feature gradient the head's backward hands down, and a checkpoint carries the FPN that moved.
+
+NOT the reference's full trainer: the ResNet has no backward pass here and stays frozen (detectron2 trains everything above
 FREEZE_AT=2); the optimiser state is not checkpointed.  The loss line is the only host read-back, on log steps only.
 """
 import argparse
@@ -24,6 +28,7 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import checkpoint, losses
+from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import head_convs
 
 
@@ -41,11 +46,13 @@ class HeadTrainer:
     """The step function of train_head: optimiser, schedule and the iteration count around model.head.forward_train + model.losses."""
 
     def __init__(self, model, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, steps: Sequence[int] = (60000, 80000),
-                 gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0):
-        self.model = model
+                 gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0, train_fpn: bool = False):
+        self.model, self.train_fpn = model, bool(train_fpn)
         self.params = [p for c in head_convs(model.head) for p in (c.weight, c.bias)]
+        if self.train_fpn:
+            self.params += [p for c in fpn_convs(model.fpn) for p in (c.weight, c.bias)]
         for p in model.parameters():
-            p.requires_grad_(False)               # backbone and FPN are frozen: they have no backward pass
+            p.requires_grad_(False)               # what is frozen (the backbone; the FPN unless train_fpn) has no backward pass here
         for p in self.params:
             p.requires_grad_(True)
         self.schedule = dict(base_lr=float(base_lr), steps=tuple(int(s) for s in steps), gamma=float(gamma), warmup_iters=int(warmup_iters),
@@ -54,8 +61,17 @@ class HeadTrainer:
         self.iteration = int(iteration)
 
     def features(self, images: Sequence[torch.Tensor]):
-        """The frozen backbone + FPN per image -> (per-level (B, 256, H, W) features, padded (h, w))."""
+        """The frozen backbone + FPN per image -> (per-level (B, 256, H, W) features, padded (h, w)).  train_fpn: only the backbone is
+        frozen; the FPN runs on the batch's c3 - c5 with grad (fpn_train.fpn_forward_train)."""
         per_image, padded = [], None
+        if self.train_fpn:
+            for im in images:
+                maps, pad = backbone_maps(self.model, im)
+                if padded is not None and tuple(pad) != tuple(padded):
+                    raise ValueError("a batch holds frames of one padded size, got {} and {}".format(padded, pad))
+                padded = tuple(pad)
+                per_image.append(maps)
+            return fpn_forward_train(self.model.fpn, per_image), padded
         with torch.no_grad():
             for im in images:
                 feats, pad = self.model._trunk_eager(im)
@@ -81,12 +97,16 @@ class HeadTrainer:
         return res
 
 
-def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int) -> str:
+def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, train_fpn: bool = False) -> str:
     """`shadow`: the same model unfolded (conv + FrozenBN pairs) on the CPU -- the form detectron2's names describe; it receives the
-    trained head and is written as <out_dir>/<name>.pth, named in <out_dir>/last_checkpoint."""
+    trained head (train_fpn: and the trained FPN, which has no norm to unfold) and is written as <out_dir>/<name>.pth, named in
+    <out_dir>/last_checkpoint."""
     os.makedirs(out_dir, exist_ok=True)
+    pairs = list(zip(head_convs(shadow.head), head_convs(model.head)))
+    if train_fpn:
+        pairs += list(zip(fpn_convs(shadow.fpn), fpn_convs(model.fpn)))
     with torch.no_grad():
-        for dst, src in zip(head_convs(shadow.head), head_convs(model.head)):
+        for dst, src in pairs:
             dst.weight.copy_(src.weight.detach().cpu())
             dst.bias.copy_(src.bias.detach().cpu())
     path = os.path.join(out_dir, name + ".pth")
@@ -104,7 +124,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
                                  epilog="A step takes SOLVER.IMS_PER_BATCH frames of ONE resized shape: the sampler batches frames of equal shape "
                                         "together, in data-set order; frames of a shape wait until a batch of them is complete.  Only the head "
-                                        "trains; backbone and FPN stay frozen.")
+                                        "trains, and with --train-fpn the FPN; the ResNet stays frozen.")
     here = os.path.dirname(os.path.abspath(__file__))
     ap.add_argument("--config-file", default=os.path.join(here, "configs/BDD-Detection/retinanet/retinanet_R_50_FPN_1x_reg_cls_var_dropout.yaml"))
     ap.add_argument("--coco-json", required=True, help="COCO-format ground truth: `images` and `annotations`")
@@ -120,6 +140,7 @@ def main(argv=None):
     ap.add_argument("--min-size-test", type=int, default=0, help="overrides INPUT.MIN_SIZE_TEST")
     ap.add_argument("--max-size-test", type=int, default=0, help="overrides INPUT.MAX_SIZE_TEST")
     ap.add_argument("--loader-workers", type=int, default=-1, help="host threads of the loader; -1 = the config's value")
+    ap.add_argument("--train-fpn", action="store_true", help="train the FPN's eight convolutions together with the head (the ResNet stays frozen)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     cfg = setup_config(args.config_file, "", args.random_seed, data_dir=args.data_dir)
@@ -158,7 +179,7 @@ def main(argv=None):
                                                   box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=int(s.STEPS[1]),
                                                   seed=args.random_seed)
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
-                          warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR)
+                          warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=args.train_fpn)
     max_iter = args.max_iter if args.max_iter >= 0 else int(s.MAX_ITER)
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
@@ -185,14 +206,14 @@ def main(argv=None):
                                                                                   trainer.opt.param_groups[0]["lr"])
                 print(last_line, flush=True)
             if period > 0 and it % period == 0 and it < max_iter:
-                written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_%07d" % (it - 1), it))
+                written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_%07d" % (it - 1), it, args.train_fpn))
             if it >= max_iter:
                 break
         stalled = 0 if progressed else stalled + 1      # (an incomplete batch carries over into the next pass over the data set)
         if stalled >= batch:
             raise SystemExit("no batch of {} frames of one resized shape can be formed from {} frames".format(batch, len(dataset)))
-    written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_final", trainer.iteration))
-    print("trained the head for %d iterations; wrote %s" % (trainer.iteration, written[-1]))
+    written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_final", trainer.iteration, args.train_fpn))
+    print("trained the head%s for %d iterations; wrote %s" % (" and the FPN" if args.train_fpn else "", trainer.iteration, written[-1]))
     return {"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line}
 
 
