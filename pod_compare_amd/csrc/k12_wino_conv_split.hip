@@ -7,6 +7,7 @@
 // instructions of rounds 3-4's 3-way bf16 split (six products), two thirds of its filter bytes and 4/7 of its split arithmetic -- and,
 // measured on the matrix cores against fp64 (tools/f16_split_numerics.hip), a SMALLER error than both the bf16 x 6 form and the fp32
 // MFMA: the fp32 accumulation chain, not the products, is where these kernels lose bits, and it is half as long.
+// The end of the K loop is peeled (chunk counts that are multiples of 4): its last four chunks prepare nothing for a chunk that never comes.
 #include "pod_wino.h"
 
 namespace pod {
@@ -15,6 +16,7 @@ typedef uint32_t vu32x4 __attribute__((ext_vector_type(4)));
 constexpr int WINO_US_BYTES = 24 * 2 * 2 * 64 * 16;      // pre-split filter terms of a 16-channel chunk: [24 positions][kb][term][h][j][8 f16]  96 KB
 constexpr int WINO_U_TOP = 14, WINO_V_TOP = 9;           // scaled filter abs-max in [2^14, 2^15); activations: 2^9 <= s amax < 2^10, x gain of Bt4 (x) Bt6 < 32
 constexpr int WINO_WAIT_VM24 = 0x4078;                    // lgkmcnt(0) vmcnt(24)
+constexpr int WINO_TAIL_NO_LOAD = 1, WINO_TAIL_NO_PARK = 2, WINO_TAIL_LAST = 4;      // what a chunk at the end of the K loop leaves out (`chunk` in k_wino_conv3x3_split)
 
 // Filter transform U = G4 g G6t (wino_filter_values).  Two passes: the abs-max of U (-> the trailer word of Us, behind the terms), then
 // every value times the power of two that puts that abs-max into [2^14, 2^15) split into two f16 terms (round to nearest even) and
@@ -345,8 +347,14 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
     //   mode 0: the first chunk (accumulators start from zero; nothing of the next chunk behind its MFMAs: stage 0 is still landing)
     //   mode 1: chunk 1 (operands made back to back after chunk 0; runs units R0 .. C4 for chunk 2)
     //   mode 2: steady state (units A .. C4)
-    auto chunk = [&](auto mode_t, auto c16_t, auto par_t, int q) {
-        constexpr int mode = decltype(mode_t)::value, c16 = decltype(c16_t)::value, par = decltype(par_t)::value;
+    // tail (the end of the loop, peeled below): what a chunk near the end leaves out because nothing behind the last chunk wants it --
+    //   WINO_TAIL_NO_LOAD: no stage loads (the pieces would be of a super-chunk past the last one)
+    //   WINO_TAIL_NO_PARK: no stage parks (the registers hold no such pieces), and no barrier at its end: nobody parks into a stage any more
+    //   WINO_TAIL_LAST:    the last chunk: the filter terms of its own positions 3..5, the A units and the MFMAs, nothing of a next chunk
+    auto chunk = [&](auto mode_t, auto c16_t, auto par_t, auto tail_t, int q) {
+        constexpr int mode = decltype(mode_t)::value, c16 = decltype(c16_t)::value, par = decltype(par_t)::value, tail = decltype(tail_t)::value;
+        constexpr bool do_load = !(tail & WINO_TAIL_NO_LOAD), do_park = !(tail & WINO_TAIL_NO_PARK), is_last = (tail & WINO_TAIL_LAST) != 0;
+        static_assert((tail == 0 || mode == 2) && (!is_last || (!do_load && !do_park)), "tail forms are steady-state chunks; the last one has no stage traffic");
         constexpr int n16 = c16 ^ 1, npar = c16 == 1 ? par ^ 1 : par;             // the NEXT chunk's half and stage
         const int qn = q + 1 <= last ? q + 1 : last;
         // stage traffic: chunk (s, 0) parks pieces 6..11 of super-chunk s + 1 (other stage) and loads 0..5 of s + 2; chunk (s, 1) parks those in
@@ -360,9 +368,9 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
                 acc[p * 2 + kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, uP[p][kb * 2 + sa]), __builtin_bit_cast(wino_f16x8, Vb[p][sb]), zero16, 0, 0, 0);
             else
                 acc[p * 2 + kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, uP[p][kb * 2 + sa]), __builtin_bit_cast(wino_f16x8, Vb[p][sb]), acc[p * 2 + kb], 0, 0, 0);
-            if constexpr (m < 4) { if (!(POD_WINO_ELIM & 2)) filter_piece(p + WINO_U_LEAD >= 6 ? qn : q, (p + WINO_U_LEAD) % 6, uP[(p + WINO_U_LEAD) % 6], m); }
-            else if constexpr (m == 4) { if (!(POD_WINO_ELIM & 4)) stage_write(c16 == 0 ? par ^ 1 : par, p, c16 == 0 ? 6 + p : p); }
-            if constexpr (p == 5 && m >= 4) {                    // the 6 stage loads (HBM) sit BEHIND the chunk's last filter loads: loads return in
+            if constexpr (m < 4 && (!is_last || p + WINO_U_LEAD < 6)) { if (!(POD_WINO_ELIM & 2)) filter_piece(p + WINO_U_LEAD >= 6 ? qn : q, (p + WINO_U_LEAD) % 6, uP[(p + WINO_U_LEAD) % 6], m); }
+            if constexpr (m == 4 && do_park) { if (!(POD_WINO_ELIM & 4)) stage_write(c16 == 0 ? par ^ 1 : par, p, c16 == 0 ? 6 + p : p); }
+            if constexpr (p == 5 && m >= 4 && do_load) {                    // the 6 stage loads (HBM) sit BEHIND the chunk's last filter loads: loads return in
                 if (!(POD_WINO_ELIM & 4)) {                      // order, and every filter term ahead is needed soon
                     stage_load(3 * (m - 4), ls, 6 * c16 + 3 * (m - 4));
                     stage_load(3 * (m - 4) + 1, ls, 6 * c16 + 3 * (m - 4) + 1);
@@ -372,17 +380,22 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
             if constexpr (mode != 0) {
                 constexpr int u0 = j * N_UNITS / N_SLOTS, u1 = (j + 1) * N_UNITS / N_SLOTS;
                 wino_static_for([&](auto K) __attribute__((always_inline)) {
-                    unit(std::integral_constant<int, u0 + decltype(K)::value>{}, std::integral_constant<int, npar>{}, std::integral_constant<int, n16>{},
-                         std::integral_constant<bool, mode == 2>{});
+                    constexpr int u = u0 + decltype(K)::value;
+                    if constexpr (!is_last || (u >= 3 && u < 7))          // (the last chunk: its own A units only)
+                        unit(std::integral_constant<int, u>{}, std::integral_constant<int, npar>{}, std::integral_constant<int, n16>{}, std::integral_constant<bool, mode == 2>{});
                 }, std::make_integer_sequence<int, u1 - u0>{});
             }
             __builtin_amdgcn_sched_barrier(0);
         }, std::make_integer_sequence<int, N_SLOTS>{});
         // No vmcnt wait: the pieces this chunk parked were loaded a chunk ago (hipcc waits for them where they are stored), the DMA pieces of
         // the prologue were issued before filter terms this chunk's MFMAs have consumed, and loads return in order.  The barrier publishes the
-        // stage and retires this chunk's LDS reads.
-        __builtin_amdgcn_s_waitcnt(WINO_WAIT_LGKM0);
-        __builtin_amdgcn_s_barrier();
+        // stage and retires this chunk's LDS reads.  A chunk that parks nothing, in a tail where no later chunk parks either, publishes nothing and
+        // protects no stage: its LDS reads were waited for where their values were used (WINO_READS_LANDED), and the stage the next chunk reads
+        // was published by the last chunk that parked.  Behind the last chunk stands the __syncthreads() of the loop's end.
+        if constexpr (do_park) {
+            __builtin_amdgcn_s_waitcnt(WINO_WAIT_LGKM0);
+            __builtin_amdgcn_s_barrier();
+        }
         if constexpr (mode == 0) {
             if (q >= last) return;
             // chunk 1's operands, back to back (stage 0 has landed and was published just now)
@@ -400,15 +413,35 @@ __global__ void __launch_bounds__(256, 1) k_wino_conv3x3_split(const WinoParams 
             __builtin_amdgcn_s_barrier();               // chunk 1 parks pieces in stage 0: every wave must have read its operands out of it
         }
     };
+    // THE END OF THE LOOP IS PEELED when the chunk count is a multiple of 4 (every count the model runs: C = 64 .. 512 whole or cut into
+    // partial sums): the last four chunks then have the static (half, stage) of loop instances 4, 5, 2, 3 and follow the loop as straight-line
+    // tail forms that issue nothing for data past the last chunk -- chunk n - 4 loads no stage pieces (super-chunk s + 2 does not exist),
+    // n - 3 and n - 2 neither load nor park, n - 1 is the last form.  With 4 chunks only n - 2 and n - 1 are tail forms: chunks 0 and 1 keep
+    // their (clamped) stage traffic -- a second instance of either, or a run-time switch inside them, costs registers: 512 and scratch, or 480
+    // against 440.  Every other count (1, 2, 3, 5, 6, 7, ...) keeps the clamped path throughout: the same instances, re-loading the last
+    // super-chunk and the last chunk's filter terms instead of skipping.  Same arithmetic in the same order either way.
     using std::integral_constant;
-    chunk(integral_constant<int, 0>{}, integral_constant<int, 0>{}, integral_constant<int, 0>{}, 0);
-    if (nchunk > 1) chunk(integral_constant<int, 1>{}, integral_constant<int, 1>{}, integral_constant<int, 0>{}, 1);
+    constexpr integral_constant<int, 0> I0{};
+    constexpr integral_constant<int, 1> I1{};
+    constexpr integral_constant<int, 2> I2{};
+    const bool peel = (nchunk & 3) == 0;
+    const int nloop = peel ? nchunk - 4 : nchunk;                        // the chunks in front of the tail
+    chunk(I0, I0, I0, I0, 0);
+    if (nchunk > 1) chunk(I1, I1, I0, I0, 1);
     for (int base = 0;; base += 4) {
 #define WINO_CHUNK(t)                                                                                                              \
-    if (base + (t) >= nchunk) break;                                                                                               \
-    chunk(integral_constant<int, 2>{}, integral_constant<int, (t) & 1>{}, integral_constant<int, ((t) >> 1) & 1>{}, base + (t));
+    if (base + (t) >= nloop) break;                                                                                                \
+    chunk(I2, integral_constant<int, (t) & 1>{}, integral_constant<int, ((t) >> 1) & 1>{}, I0, base + (t));
         WINO_CHUNK(2) WINO_CHUNK(3) WINO_CHUNK(4) WINO_CHUNK(5)
 #undef WINO_CHUNK
+    }
+    if (peel) {
+        if (nchunk > 4) {
+            chunk(I2, I0, I0, integral_constant<int, WINO_TAIL_NO_LOAD>{}, nchunk - 4);
+            chunk(I2, I1, I0, integral_constant<int, WINO_TAIL_NO_LOAD | WINO_TAIL_NO_PARK>{}, nchunk - 3);
+        }
+        chunk(I2, I0, I1, integral_constant<int, WINO_TAIL_NO_LOAD | WINO_TAIL_NO_PARK>{}, nchunk - 2);
+        chunk(I2, I1, I1, integral_constant<int, WINO_TAIL_NO_LOAD | WINO_TAIL_NO_PARK | WINO_TAIL_LAST>{}, nchunk - 1);
     }
     __syncthreads();                                   // every wave is done reading the stages, no DMA in flight: they become the output staging
     WINO_STAMP(3);
