@@ -16,7 +16,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import amax, hip, wgrad
+from . import amax, conv1x1, conv_forms, hip, modeling, wgrad, wino
 from .head_train import input_grad_gemm, patch_matrix
 
 
@@ -26,11 +26,9 @@ def fpn_convs(fpn) -> list:
 
 
 def _require(fpn) -> None:
-    from . import modeling, wino
-    from .conv1x1 import Conv3x3S2
-    K = fpn.p6.out_channels
+    K, S2 = fpn.p6.out_channels, conv1x1.Conv3x3S2
     ok = (len(fpn.lateral) == 3 and fpn.cl_eligible() and modeling.HIP_P6P7 and modeling.WINO_BACKBONE and bool(wino.SPLIT_BF16)
-          and Conv3x3S2.eligible(fpn.p6) and Conv3x3S2.eligible(fpn.p7) and fpn.p6.bias is not None and fpn.p7.bias is not None
+          and S2.eligible(fpn.p6) and S2.eligible(fpn.p7) and fpn.p6.bias is not None and fpn.p7.bias is not None
           and all(c.out_channels == K for c in fpn_convs(fpn)) and fpn.p7.in_channels == K and 9 * fpn.p6.in_channels <= 18432)
     if not ok:
         raise hip.PodError("fpn_forward_train: this FPN has no HIP training path (three biased 1x1 laterals of Cin % 16 == 0, 3x3 output convs and "
@@ -39,18 +37,15 @@ def _require(fpn) -> None:
 
 def _dcols_gemm(conv):
     """dcols = dY W9, W9 (K, ty, tx, Cin) the stride-2 conv's filter in the patch matrix's column order: a GEMM with the transposed filter on
-    pod_conv1x1_split, split once and cached by the weight's version (modeling._derived)."""
-    from . import modeling
-    from .conv1x1 import Conv1x1
-
+    pod_conv1x1_split, split once and cached by the weight's version (conv_forms.derived)."""
     def make(c):
         K, C = c.out_channels, c.in_channels
         w9 = c.weight.detach().permute(0, 2, 3, 1).reshape(K, 9 * C)
         try:
-            return Conv1x1(w9.t().reshape(9 * C, K, 1, 1).contiguous(), None, 1)
+            return conv1x1.Conv1x1(w9.t().reshape(9 * C, K, 1, 1).contiguous(), None, 1)
         except ValueError as e:
             raise hip.PodError("FPN backward: the input gradient of a stride-2 {} -> {} conv has no pod_conv1x1_split form ({})".format(C, K, e))
-    return modeling._derived(conv, "_pod_dcols_gemm", make)
+    return conv_forms.derived(conv, "_pod_dcols_gemm", make)
 
 
 def _cols(x: torch.Tensor, h: int, w: int, relu: bool, out: torch.Tensor) -> None:
@@ -171,15 +166,9 @@ def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int
 
 def backbone_maps(model, image: torch.Tensor):
     """The frozen backbone of one frame, channels-last: ([(c3, h, w), (c4, h, w), (c5, h, w)], padded (h, w)) -- the part of
-    ProbabilisticRetinaNet._trunk_eager ahead of the FPN."""
-    from . import anchors
+    ProbabilisticRetinaNet._trunk_eager ahead of the FPN (`_backbone_cl`)."""
     with torch.no_grad():
-        if (image.is_cuda and image.device == model.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
-                and image.dtype in (torch.uint8, torch.float32) and model._cl_backbone(model.pixel_mean) and model.bottom_up.hip_stem_ok()):
-            padded = anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
-            return model.bottom_up.forward_cl(None, frame=(image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded)), tuple(padded)
-        if image.is_cuda:
-            x = model.preprocess_image(image)
-            if model._cl_backbone(x):
-                return model.bottom_up.forward_cl(x), tuple(x.shape[-2:])
-    raise hip.PodError("training the FPN needs the channels-last HIP backbone (a frame on the model's GPU, FrozenBN folded, the split kernels selected)")
+        maps = model._backbone_cl(image) if image.is_cuda else None
+    if maps is None:
+        raise hip.PodError("training the FPN needs the channels-last HIP backbone (a frame on the model's GPU, FrozenBN folded, the split kernels selected)")
+    return maps

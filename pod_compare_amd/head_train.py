@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import amax, hip, wgrad
+from . import amax, conv1x1, conv_forms, hip, modeling, wgrad
 from .synthetic import HeadOutputs
 
 
@@ -35,18 +35,15 @@ def transposed_weight(weight: torch.Tensor) -> torch.Tensor:
 
 def input_grad_gemm(conv):
     """The conv's input gradient as a GEMM: W' laid out (C, ty, tx, Kpad) and split once for pod_conv1x1_split (conv1x1.Conv3x3S2's form,
-    stride 1), cached by the weight's version as modeling.wino_of caches the forward filter."""
-    from . import modeling
-    from .conv1x1 import Conv1x1
-
+    stride 1), cached by the weight's version as conv_forms.wino_of caches the forward filter."""
     def make(c):
         wt = transposed_weight(c.weight)
         try:
-            return Conv1x1(wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1).contiguous(), None, 1)
+            return conv1x1.Conv1x1(wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1).contiguous(), None, 1)
         except ValueError as e:
             raise hip.PodError("head backward: the input gradient of a {} -> {} conv has no pod_conv1x1_split form ({})".format(
                 c.in_channels, c.out_channels, e))
-    return modeling._derived(conv, "_pod_dx_gemm", make)
+    return conv_forms.derived(conv, "_pod_dx_gemm", make)
 
 
 def patch_matrix(dz: torch.Tensor, levels, B: int) -> torch.Tensor:
@@ -80,14 +77,13 @@ def _planes_to_padded_cl(g: Optional[torch.Tensor], levels, B: int, K: int, devi
 class _HeadTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, levels, B, x0, *params):
-        from . import modeling
-        if not all(modeling.wino_of(c).split for c in head_convs(head)):
+        if not all(conv_forms.wino_of(c).split for c in head_convs(head)):
             raise hip.PodError("head.forward_train needs the split Winograd kernel for every conv of the head (C % 16 == 0, POD_WINO_SPLIT=1)")
         x0 = x0.detach()
         # the training form of the head's launch plan (modeling._trunk_plan): B images per level, every layer's output kept
-        st = {"x0": x0, "levels": list(levels), "dropout": False, "grouped": True, "images": int(B), "channels": max(int(x0.shape[1]), 64)}
+        st = modeling.HeadPlan(x0=x0, levels=list(levels), dropout=False, grouped=True, images=int(B), channels=max(int(x0.shape[1]), 64))
         last = [buf for buf, _ in head._trunks([(0, B), (1, B)], st)]
-        saved = st["saved"]                             # saved[sid][l] = (input, output) of trunk layer l
+        saved = st.saved                                # saved[sid][l] = (input, output) of trunk layer l
         preds = [(head.cls_score, 0), (head.bbox_pred, 1)] + ([(head.cls_var, 0)] if head.cls_var is not None else []) + \
                 ([(head.bbox_cov, 1)] if head.bbox_cov is not None else [])
         planes = head._predict([(conv, last[sid], B, 0, B, B) for conv, sid in preds], st, flat=True)
@@ -145,6 +141,7 @@ def forward_train(head, features: Sequence[torch.Tensor], anchors: Optional[List
         raise hip.PodError("head.forward_train runs on the GPU in fp32 only (got {} on {}): there is no CPU path".format(f0.dtype, f0.device))
     B, C = int(f0.shape[0]), int(f0.shape[1])
     convs = head_convs(head)
+    # C % 16: the split kernel, forward and (as the GEMM's Cin) backward; one of its four widths: a layer's output, unpadded, is the next one's input
     if C != head.cls_subnet[0].in_channels or C % 16 or C not in (64, 128, 256, 512) or any(c.bias is None for c in convs):
         raise hip.PodError("head.forward_train: {} input channels (conv {} -> {}) have no pod_wino_conv3x3_split form for both directions "
                            "(64, 128, 256 or 512 channels, biased convs)".format(C, head.cls_subnet[0].in_channels, head.cls_subnet[0].out_channels))

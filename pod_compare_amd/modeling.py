@@ -2,7 +2,8 @@
 
 The reference model (probabilistic_modeling/probabilistic_retinanet.py) subclasses detectron2's
 RetinaNet, which is not installed; this is a from-scratch statement of the same architecture in
-plain torch (convolutions run in MIOpen -- they are not part of the hand-written hot path):
+plain torch.  On the GPU its convolutions run on the hand-written HIP kernels (pod_stem7x7_split, pod_conv1x1_split, pod_wino_conv3x3[_split]:
+the switches below); MIOpen and the NCHW paths remain for CPU tensors and as the tests' references:
 
   backbone  detectron2 `build_retinanet_resnet_fpn_backbone`: ResNet-50 (FrozenBN, stride in the
             1x1 conv of each bottleneck), FPN on res3..res5 (256 ch) + LastLevelP6P7 from res5
@@ -23,13 +24,18 @@ MI355X-first differences from the reference's forward (PR:95-108, PR:486-537), n
   * dropout is enabled by a flag instead of `model.train()` (PI:53-56).
 """
 import math
+import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import amax, conv1x1, hip, sparse, wino          # (modules, called through: bench.py and the tests replace wino.grouped_launch, wino.block_table, ... on them)
 from . import anchors as _anchors
+from . import losses as _losses
+from .conv_forms import c1_of, s2_of, stem_of, wino_of   # (wino_of: tests and tools reach it as modeling.wino_of)
 from .synthetic import HeadOutputs
 
 PIXEL_MEAN_BGR = (103.530, 116.280, 123.675)   # detectron2 defaults used by the BDD configs
@@ -128,7 +134,6 @@ def conv_bias_act(m, x: torch.Tensor, relu: bool = False, residual: Optional[tor
         if relu:
             y = F.relu_(y)
         return F.dropout(y, dropout_p, training=True) if dropout_p > 0.0 else y
-    from . import hip
     lib = hip.load()
     nhwc = x.dim() == 4 and x.shape[1] > 1 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
     y = F.conv2d(x, _weight_for(conv, nhwc), None, conv.stride, conv.padding, conv.dilation, conv.groups)
@@ -177,55 +182,31 @@ def _weight_for(conv: nn.Conv2d, channels_last: bool) -> torch.Tensor:
 
 
 WINO_HEAD = True              # GPU only: the head subnets' 3x3 convs on pod_wino_conv3x3 (all levels, all runs per launch)
-WINO_BACKBONE = __import__("os").environ.get("POD_WINO_BACKBONE", "1") != "0"   # GPU only: the bottlenecks' and the FPN's 3x3 / stride-1 convs on pod_wino_conv3x3 too (batch 1: few
+WINO_BACKBONE = os.environ.get("POD_WINO_BACKBONE", "1") != "0"   # GPU only: the bottlenecks' and the FPN's 3x3 / stride-1 convs on pod_wino_conv3x3 too (batch 1: few
                               # workgroups per launch, but a third of MIOpen's CU-time per FLOP -- the other streams' images fill the idle CUs)
 NHWC_TRUNK_MIN_CELLS = 8192   # head trunks of maps at least this large run channels-last (p3 of a 768x1344 input: 16128)
 
 
-def _derived(conv: nn.Conv2d, attr: str, make, *extra_key):
-    """make(conv) -- a kernel's form of the conv's parameters -- cached on the conv as `attr`, rebuilt when the parameters (or extra_key) change."""
-    w, b = conv.weight, conv.bias
-    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version)) + extra_key
-    cached = getattr(conv, attr, None)
-    if cached is None or cached[0] != key:
-        cached = (key, make(conv))
-        torch.cuda.current_stream(w.device).synchronize()      # made once, then read from any stream
-        setattr(conv, attr, cached)
-    return cached[1]
-
-
-def wino_of(conv: nn.Conv2d):
-    """The conv's Winograd-transformed filter (pod_wino_filter_transform), refreshed when the parameters change."""
-    from . import wino
-    return _derived(conv, "_pod_wino", lambda c: wino.WinoConv(c.weight, c.bias), wino.SPLIT_BF16)
-
-
-def _wino_limits() -> int:
-    from .wino import MAX_CANVAS_BYTES
-    return MAX_CANVAS_BYTES
-
-
 def wino_eligible(conv: Optional[nn.Conv2d], x: torch.Tensor) -> bool:
     """pod_wino_conv3x3 can stand in for `conv` on x: 3x3 / stride 1 / pad 1, fp32 on the GPU, one image, channel counts it tiles."""
-    return (WINO_BACKBONE and FUSE_CONV_TAIL and conv is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] == 1
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1) and conv.groups == 1
-            and tuple(conv.dilation) == (1, 1) and conv.in_channels % 8 == 0 and conv.out_channels in (64, 128, 256, 512)
+    return (WINO_BACKBONE and FUSE_CONV_TAIL and wino.WinoConv.eligible(conv) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.shape[0] == 1
+            and conv.in_channels % 8 == 0                       # either kernel may serve an NCHW map: the fp32-MFMA kernel's channel step
+            and conv.out_channels in (64, 128, 256, 512)        # the backbone's and the FPN's own widths, none padded
             and x.shape[2] < 4096 and x.shape[3] < 4096
-            and x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 4 <= _wino_limits())      # 32-bit offsets inside a canvas
+            and x.shape[2] * x.shape[3] * max(conv.in_channels, conv.out_channels) * 4 <= wino.MAX_CANVAS_BYTES)      # 32-bit offsets inside a canvas
 
 
 def wino_conv_nchw(conv: nn.Conv2d, x: torch.Tensor, relu: bool, pre_bias: Optional[torch.Tensor] = None, pre_relu: bool = False) -> torch.Tensor:
     """act(conv(pre_act(x + pre_bias))) for an NCHW x (1, C, H, W): the element-wise tail of the PRODUCER of x (bias + ReLU of the conv
     before) rides on the pass that lays x out channels-last (pod_bias_act_to_nhwc), the 3x3 conv runs on pod_wino_conv3x3 with its own
     bias + ReLU in the store, and the result comes back as NCHW planes."""
-    from . import hip
-    from .wino import block_table
     _, C, H, W = x.shape
     a = torch.empty((H * W, C), dtype=x.dtype, device=x.device)
     hip.check(hip.load().pod_bias_act_to_nhwc(x.contiguous().data_ptr(), a.data_ptr(), hip.ptr(pre_bias), 1, C, H * W, 1 if pre_relu else 0,
                                               hip.current_stream()), "pod_bias_act_to_nhwc")
     out = torch.empty((1, conv.out_channels, H, W), dtype=x.dtype, device=x.device)
-    wino_of(conv).planes_of_one_image(a, out.view(-1), block_table([(H, W)], 1, x.device), relu=relu)     # (small maps: split over C)
+    wino_of(conv).planes_of_one_image(a, out.view(-1), wino.block_table([(H, W)], 1, x.device), relu=relu)     # (small maps: split over C)
     return out
 
 
@@ -234,51 +215,30 @@ def wino_conv_nchw(conv: nn.Conv2d, x: torch.Tensor, relu: bool, pre_bias: Optio
 # NCHW: MIOpen GEMM + one element-wise pass each for bias / residual / ReLU, plus a layout pass in front of every 3x3.  On
 # pod_conv1x1_split (csrc/k13_conv1x1_split.hip: channels-last GEMM, bias + residual + ReLU in the store, same exact-split products as
 # the 3x3 kernel) a bottleneck is three launches on (pixels, C) buffers and the whole trunk stays channels-last from the max-pool on.
-GROUPED_HEAD = __import__("os").environ.get("POD_GROUPED_HEAD", "1") != "0"         # layer l of the cls and the bbox subnet, and the four predictors, in one launch each
-CL_BACKBONE = __import__("os").environ.get("POD_CL_BACKBONE", "1") != "0"
-HIP_P6P7 = __import__("os").environ.get("POD_HIP_P6P7", "1") != "0"         # FPN's p6 / p7 (3x3 / stride 2) as pod_im2col3x3s2_cl + pod_conv1x1_split instead of MIOpen
-HIP_STEM = __import__("os").environ.get("POD_HIP_STEM", "1") != "0"         # the 7x7 stem + max-pool of the channels-last trunk on pod_stem7x7_split / pod_maxpool3x3s2_cl
+GROUPED_HEAD = os.environ.get("POD_GROUPED_HEAD", "1") != "0"         # layer l of the cls and the bbox subnet, and the four predictors, in one launch each
+CL_BACKBONE = os.environ.get("POD_CL_BACKBONE", "1") != "0"
+HIP_P6P7 = os.environ.get("POD_HIP_P6P7", "1") != "0"         # FPN's p6 / p7 (3x3 / stride 2) as pod_im2col3x3s2_cl + pod_conv1x1_split instead of MIOpen
+HIP_STEM = os.environ.get("POD_HIP_STEM", "1") != "0"         # the 7x7 stem + max-pool of the channels-last trunk on pod_stem7x7_split / pod_maxpool3x3s2_cl
 
 
 def kernel_selection() -> tuple:
     """Every switch that selects the kernels of a forward (part of the HIP-graph key: a graph captured under one selection must not answer for another)."""
-    from . import wino
     return (WINO_HEAD, WINO_BACKBONE, GROUPED_HEAD, CL_BACKBONE, HIP_STEM, HIP_P6P7, FUSE_CONV_TAIL, NHWC_TRUNK_MIN_CELLS, bool(wino.SPLIT_BF16))
 
 
-def c1_of(conv: nn.Conv2d):
-    """The conv's pod_conv1x1_split form (weight split once), refreshed when the parameters change."""
-    from .conv1x1 import Conv1x1
-    return _derived(conv, "_pod_c1", lambda c: Conv1x1(c.weight, c.bias, c.stride[0]))
-
-
-def stem_of(conv: nn.Conv2d):
-    """The stem conv's pod_stem7x7_split form (weight split once), refreshed when the parameters change."""
-    from .conv1x1 import Stem7x7
-    return _derived(conv, "_pod_stem", lambda c: Stem7x7(c.weight, c.bias))
-
-
-def s2_of(conv: nn.Conv2d):
-    """The conv's im2col + pod_conv1x1_split form (3x3 / stride 2: FPN's p6 / p7; weight re-laid and split once), refreshed when the parameters change."""
-    from .conv1x1 import Conv3x3S2
-    return _derived(conv, "_pod_s2", lambda c: Conv3x3S2(c.weight, c.bias))
-
-
 def _c1_ok(conv: Optional[nn.Conv2d]) -> bool:
-    from .conv1x1 import Conv1x1
-    return conv is not None and conv.bias is not None and Conv1x1.eligible(conv)
+    return conv is not None and conv.bias is not None and conv1x1.Conv1x1.eligible(conv)
 
 
 def _w3_ok(conv: Optional[nn.Conv2d]) -> bool:
-    return (conv is not None and conv.bias is not None and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-            and tuple(conv.padding) == (1, 1) and conv.groups == 1 and tuple(conv.dilation) == (1, 1) and conv.in_channels % 16 == 0
-            and conv.out_channels in (64, 128, 256, 512))
+    return (wino.WinoConv.eligible(conv) and conv.bias is not None
+            and conv.in_channels % 16 == 0                      # the split kernel: the one the channels-last trunk chains with pod_conv1x1_split
+            and conv.out_channels in (64, 128, 256, 512))       # channels-last output has no padded channels (K == Kpad)
 
 
 def wino_cl(conv: nn.Conv2d, x: torch.Tensor, h: int, w: int, relu: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(conv3x3(x) + bias) of one channels-last image (h * w, C) -> (h * w, K)."""
-    from .wino import block_table
-    return wino_of(conv).channels_last_of_one_image(x, block_table([(h, w)], 1, x.device, channels=max(conv.in_channels, conv.out_channels)), relu=relu, out=out)
+    return wino_of(conv).channels_last_of_one_image(x, wino.block_table([(h, w)], 1, x.device, channels=max(conv.in_channels, conv.out_channels)), relu=relu, out=out)
 
 
 def levels_channels_last(features: List[torch.Tensor]) -> torch.Tensor:
@@ -383,22 +343,20 @@ class ResNet50(_TracksStorage):
         return all(b.cl_eligible() for stage in (self.res2, self.res3, self.res4, self.res5) for b in stage)
 
     def hip_stem_ok(self) -> bool:
-        from .conv1x1 import Stem7x7
         stem = _plain_conv(self.stem)
-        return HIP_STEM and stem is not None and stem.bias is not None and Stem7x7.eligible(stem)
+        return HIP_STEM and stem is not None and stem.bias is not None and conv1x1.Stem7x7.eligible(stem)
 
     def forward_cl(self, x, frame=None):
         """Channels-last from the stem on: returns [(c3, h, w), (c4, h, w), (c5, h, w)] with c* (h * w, C) buffers.  frame = (image (3, h, w)
         uint8 / fp32 on the device, pixel mean, pixel std, padded (h, w)) instead of x: the stem kernel normalises and pads on load."""
         stem = _plain_conv(self.stem)
-        from .conv1x1 import maxpool3x3s2_cl
         if frame is not None:
             img, mean, std, padded = frame
             t, h, w = stem_of(stem)(img, relu=True, mean=mean, std=std, padded_hw=padded)
-            t, h, w = maxpool3x3s2_cl(t, h, w)
+            t, h, w = conv1x1.maxpool3x3s2_cl(t, h, w)
         elif self.hip_stem_ok() and x.shape[0] == 1 and x.is_contiguous():
             t, h, w = stem_of(stem)(x, relu=True)                        # 7x7 / stride 2 on pod_stem7x7_split: channels-last out
-            t, h, w = maxpool3x3s2_cl(t, h, w)
+            t, h, w = conv1x1.maxpool3x3s2_cl(t, h, w)
         else:
             x = conv_bias_act(self.stem, x, relu=True)                   # MIOpen, NCHW
             x = F.max_pool2d(x, kernel_size=3, stride=2, padding=1)
@@ -453,37 +411,57 @@ class FPN(_TracksStorage):
         l3 = lateral(self.lateral[0], c3, h3, w3, l4, h4, w4)
         if keep is not None:
             keep.update(l3=l3, l4=l4, l5=l5, hip_p6p7=False)
-        from . import amax
-        from .conv1x1 import Conv3x3S2
-        if HIP_P6P7 and Conv3x3S2.eligible(self.p6) and Conv3x3S2.eligible(self.p7) and self.output[0].out_channels == self.p6.out_channels == self.p7.out_channels:
+        S2 = conv1x1.Conv3x3S2
+        one_buffer = HIP_P6P7 and S2.eligible(self.p6) and S2.eligible(self.p7) and self.output[0].out_channels == self.p6.out_channels == self.p7.out_channels
+        hw, parts = [(h3, w3), (h4, w4), (h5, w5)], [None] * 3
+        if one_buffer:
             # the five levels go straight into ONE buffer, level after level -- the layout the head's grouped launches read (no concatenation
             # in front of the head) -- and max their abs-max into one record (the head's `in_amax`)
-            (h6, w6) = Conv3x3S2.out_hw(h5, w5)
-            (h7, w7) = Conv3x3S2.out_hw(h6, w6)
-            hw = [(h3, w3), (h4, w4), (h5, w5), (h6, w6), (h7, w7)]
+            hw.append(S2.out_hw(h5, w5))
+            hw.append(S2.out_hw(*hw[3]))
             buf = torch.empty((sum(h * w for h, w in hw), self.p6.out_channels), dtype=torch.float32, device=c5.device)
             rec, parts, at = amax.word(buf.device), [], 0
             for h, w in hw:
                 parts.append(buf[at:at + h * w])
                 parts[-1]._pod_amax_shared = rec             # (amax.produced: the launch that writes this slice max'es into the shared record)
                 at += h * w
-            wino_cl(self.output[0], l3, h3, w3, relu=False, out=parts[0])
-            wino_cl(self.output[1], l4, h4, w4, relu=False, out=parts[1])
-            wino_cl(self.output[2], l5, h5, w5, relu=False, out=parts[2])
-            s2_of(self.p6)(c5, h5, w5, out=parts[3])
-            s2_of(self.p7)(parts[3], h6, w6, relu_input=True, out=parts[4])
-            amax.attach(buf, rec)
-            outs = [cl_as_nchw(t, h, w) for t, (h, w) in zip(parts, hw)]
-            outs[0]._pod_cl_levels, outs[0]._pod_cl_version = buf, buf._version
-            if keep is not None:
-                keep["hip_p6p7"] = True
-            return outs
-        p3 = cl_as_nchw(wino_cl(self.output[0], l3, h3, w3, relu=False), h3, w3)
-        p4 = cl_as_nchw(wino_cl(self.output[1], l4, h4, w4, relu=False), h4, w4)
-        p5 = cl_as_nchw(wino_cl(self.output[2], l5, h5, w5, relu=False), h5, w5)
-        p6 = self.p6(cl_as_nchw(c5, h5, w5))
-        p7 = self.p7(F.relu(p6))
-        return [p3, p4, p5, p6, p7]
+        p345 = [wino_cl(conv, l, h, w, relu=False, out=out) for conv, l, (h, w), out in zip(self.output, (l3, l4, l5), hw, parts)]
+        if not one_buffer:
+            p6 = self.p6(cl_as_nchw(c5, h5, w5))
+            return [cl_as_nchw(t, h, w) for t, (h, w) in zip(p345, hw)] + [p6, self.p7(F.relu(p6))]
+        s2_of(self.p6)(c5, h5, w5, out=parts[3])
+        s2_of(self.p7)(parts[3], *hw[3], relu_input=True, out=parts[4])
+        amax.attach(buf, rec)
+        outs = [cl_as_nchw(t, h, w) for t, (h, w) in zip(parts, hw)]
+        outs[0]._pod_cl_levels, outs[0]._pod_cl_version = buf, buf._version
+        if keep is not None:
+            keep["hip_p6p7"] = True
+        return outs
+
+
+@dataclass(eq=False)
+class HeadPlan:
+    """What one evaluation of the head carries from `_plan` to its launches and on to the model: every field, who sets it, its default.
+    Inference form: `ProbabilisticRetinaNetHead._plan` (images = 0).  Training form: head_train.py builds HeadPlan(x0, levels, dropout =
+    False, grouped = True, images = B, channels) and leaves the run fields at their defaults."""
+    n: int = 1                      # _plan: MC runs
+    m: int = 1                      # _plan: the runs whose cls / cls_var / reg_var are needed, n - skip
+    skip: int = 0                   # _plan: 1 when the last run's unused evaluations are left out
+    dropout: bool = False           # _plan: MC dropout is active (mc_dropout and p > 0)
+    cls_copies: int = 1             # _plan: evaluations of the cls trunk
+    box_copies: int = 1             # _plan: evaluations of the bbox trunk
+    wino: bool = False              # _plan: every conv of the head takes pod_wino_conv3x3[_split]; the four below are set only then
+    grouped: bool = False           # _plan (`_grouped_ok`) / head_train: one grid per layer of both subnets, one for the predictors
+    levels: Optional[list] = None   # _plan / head_train: (h, w) per FPN level
+    x0: Optional[torch.Tensor] = None    # _plan / head_train: the features as (pixels of all levels, C) channels-last, level after level
+    images: int = 0                 # head_train: B images per level, every layer's output kept; 0 = the inference form
+    channels: int = 512             # head_train: the channel count that bounds the block tables' canvases
+    saved: Optional[list] = None    # _trunks, when `images` is set: saved[subnet][layer] = (input, output)
+    logits: Optional[list] = None        # forward_cls: cls_score's planes per level
+    logit_vars: Optional[list] = None    # forward_cls: cls_var's, or None
+    padded: Optional[tuple] = None       # ProbabilisticRetinaNet._cls_eager: the padded frame's (h, w)
+    image_hw: Optional[tuple] = None     # ProbabilisticRetinaNet._cls_eager: the frame's (h, w)
+    shapes: Optional[list] = None        # ProbabilisticRetinaNet._cls_eager: (h, w) per FPN level
 
 
 class ProbabilisticRetinaNetHead(_TracksStorage):
@@ -551,7 +529,6 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                 x = self._replayed(conv_bias_act(conv, x, relu=True) if fused else F.relu(conv(x)), sid, j, level)
             return x.contiguous()
         if fused and x.numel() % 4 == 0:
-            from . import hip
             src = x if (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)) else x.contiguous()
             x = torch.empty((copies,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device,
                             memory_format=torch.channels_last if (nhwc and not src.is_contiguous()) else torch.contiguous_format)
@@ -577,21 +554,20 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         return (GROUPED_HEAD and all(1 <= c <= 127 for c in copies)
                 and all(self._wino(c).split for c in list(self.cls_subnet) + list(self.bbox_subnet)))
 
-    def _trunk_plan(self, subnets, st: dict, bufs=None) -> dict:
+    def _trunk_plan(self, subnets, st: HeadPlan, bufs=None) -> dict:
         """The bookkeeping of the trunks' launches, subnets: [(0 = cls / 1 = bbox, copies)]; touches the device for buffers and
-        `block_table`s only.  st: `_plan`'s, x0 = the features as (pixels of all levels, C) channels-last, level after level, in two forms.
-        Inference: ONE image per level.  With st["dropout"] (MC dropout) a subnet is evaluated `copies` times -- its first activation,
+        `block_table`s only.  st: the HeadPlan, x0 = the features as (pixels of all levels, C) channels-last, level after level, in two forms.
+        Inference: ONE image per level.  With st.dropout (MC dropout) a subnet is evaluated `copies` times -- its first activation,
         identical for every copy, is computed once and stored `copies` times under the copies' masks (`firsts` tables, "replicas") -- and
         a subnet's layers ping-pong between two buffers (bufs: `new(key, shape)`, the sparse tower's re-used ones); without, one evaluation
-        and no mask arguments.  Training (st["images"] = B, head_train.py): B images per level, evaluated once by every subnet, every layer
-        writes a buffer of its own (the backward reads them), and masks are keyed at p = 0 too.  st["channels"] bounds the tables' canvases.
+        and no mask arguments.  Training (st.images = B, head_train.py): B images per level, evaluated once by every subnet, every layer
+        writes a buffer of its own (the backward reads them), and masks are keyed at p = 0 too.  st.channels bounds the tables' canvases.
         Masked, subnet i's layer l draws the Philox offset base + i L + l + 1, ONE for the whole buffer: an element's mask is keyed by its
         index in it.  -> layers: per layer the `sets` of wino.grouped_launch ("conv" still the nn.Conv2d, `_launch` looks its WinoConv up);
         kw: their common arguments; copies: images per level in each subnet's buffers; replay: recorded masks stand in for Philox's."""
-        from . import wino
-        x0, levels, B = st["x0"], st["levels"], st.get("images")
-        L, C, dev, ch = len(self.cls_subnet), x0.shape[1], x0.device, st.get("channels", 512)
-        replicas, masked = st["dropout"] and not B, bool(st["dropout"] or B)
+        x0, levels, B = st.x0, st.levels, st.images
+        L, C, dev, ch = len(self.cls_subnet), x0.shape[1], x0.device, st.channels
+        replicas, masked = st.dropout and not B, bool(st.dropout or B)
         copies = [B or (c if replicas else 1) for _, c in subnets]
         new = bufs or (lambda key, shape: torch.empty(shape, dtype=x0.dtype, device=dev))
         dsts = [[new("t%d_%d" % (i, j), (wino.level_pixel_offsets(levels, c)[-1], C)) for j in range(L if B else 2)] for i, c in enumerate(copies)]
@@ -609,14 +585,13 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                    for i, ((sid, _), d) in enumerate(zip(subnets, dsts))] for l in range(L)]
         return {"layers": layers, "kw": kw, "copies": copies, "replay": replay}
 
-    def _launch(self, sets, st: dict, live=None, **kw) -> None:
+    def _launch(self, sets, st: HeadPlan, live=None, **kw) -> None:
         """Launches `sets` (a layer of the trunks, or the predictors): ONE grid (pod_wino_conv3x3_split, n_sets > 1) when the head's launches
         are grouped and the convs share a padded width -- the kernel runs one workgroup per CU, so a launch costs whole rounds of 256
         workgroups: two launches of 1.5 rounds cost 4, one of 3.0 costs 3 -- and one one-set launch each otherwise: the same buffers, tables,
         Philox offsets and therefore the same bits.  live: a callable (table) -> its live records (the sparse tower), or None."""
-        from . import hip, wino
         sets = [dict(s, conv=self._wino(s["conv"])) for s in sets]
-        if st["grouped"] and len({s["conv"].Kpad for s in sets}) == 1 and all(s["conv"].split for s in sets):
+        if st.grouped and len({s["conv"].Kpad for s in sets}) == 1 and all(s["conv"].split for s in sets):
             return wino.grouped_launch(sets, live=live, **kw)
         for s in sets:
             conv, r = s["conv"], s.get("replicas", 0)
@@ -626,7 +601,7 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                 conv(s["src"], s["dst"], s["table"], offset=s.get("offset", 0), planes=s.get("planes", False),
                      **({} if live is None else {"live": live(s["table"])}), **kw)
             else:                                              # ... its copies stored by a pass of their own per level (the same masks)
-                levels, x0 = st["levels"], s["src"]
+                levels, x0 = st.levels, s["src"]
                 y = conv(x0, torch.empty_like(x0), wino.block_table(levels, 1, x0.device), relu=True)
                 off1, offr = wino.level_pixel_offsets(levels, 1), wino.level_pixel_offsets(levels, r)
                 for lv, (h, w) in enumerate(levels):
@@ -634,86 +609,83 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
                                                             kw["dropout_p"], kw["seed"], s["offset"] + offr[lv] * conv.C // 8,
                                                             kw["epoch"].data_ptr(), hip.current_stream()), "pod_expand_dropout")
 
-    def _trunks(self, subnets, st: dict, live=None, bufs=None):
+    def _trunks(self, subnets, st: HeadPlan, live=None, bufs=None):
         """Subnet evaluations on ALL levels: `_trunk_plan`'s launches, one per conv layer (fp32 Winograd on the matrix cores, bias + ReLU +
         dropout in its store) instead of one MIOpen call + one element-wise pass per level and layer.  Returns per subnet (buffer, images
         per level): the last activation as (pixels of all levels x images, C) channels-last, level after level; in the training form
-        st["saved"][i][l] = (input, output) of layer l besides.
+        st.saved[i][l] = (input, output) of layer l besides.
         live (sparse bbox tower, pod_compare_amd/sparse.py): a LiveBlocks -- layer j is launched over the blocks of reach L - j only; bufs:
         the tower's buffers (only live blocks are written; what dead blocks hold is never read)."""
-        from .sparse import DENSE_INPUT, reach_of_subnet_layer
-        from .wino import level_pixel_offsets
-        assert live is None or st["grouped"], "the sparse tower needs the split kernel's grouped launches"
+        assert live is None or st.grouped, "the sparse tower needs the split kernel's grouped launches"
         plan = self._trunk_plan(subnets, st, bufs)
-        levels, L = st["levels"], len(plan["layers"])
+        levels, L = st.levels, len(plan["layers"])
         for l, sets in enumerate(plan["layers"]):
-            self._launch(sets, st, live=None if live is None else (lambda t: live(t, reach_of_subnet_layer(l, L), DENSE_INPUT if l == 0 else -1)),
+            self._launch(sets, st, live=None if live is None else (lambda t: live(t, sparse.reach_of_subnet_layer(l, L), sparse.DENSE_INPUT if l == 0 else -1)),
                          **plan["kw"])
             if plan["replay"]:      # parity mode: the recorded masks on the channels-last images of the layer's output (the in-place
                 for s, (sid, _), c in zip(sets, subnets, plan["copies"]):         # copy bumps its version: the launch's abs-max record lapses)
-                    offs = level_pixel_offsets(levels, c)
+                    offs = wino.level_pixel_offsets(levels, c)
                     for lv, (h, w) in enumerate(levels):
                         v = s["dst"][offs[lv]:offs[lv + 1]].view(c, h, w, -1)
                         v.copy_(self._replayed(v.permute(0, 3, 1, 2), sid, l, lv).permute(0, 2, 3, 1))
-        if st.get("images"):
-            st["saved"] = [[(sets[i]["src"], sets[i]["dst"]) for sets in plan["layers"]] for i in range(len(subnets))]
+        if st.images:
+            st.saved = [[(sets[i]["src"], sets[i]["dst"]) for sets in plan["layers"]] for i in range(len(subnets))]
         return [(plan["layers"][-1][i]["dst"], c) for i, c in enumerate(plan["copies"])]
 
-    def _jobs(self, side: int, trunk, st: dict):
+    def _jobs(self, side: int, trunk, st: HeadPlan):
         """The predictor jobs (`_predict`) of one side -- 0: cls_score (+ cls_var), 1: bbox_pred (+ bbox_cov) -- on its trunk (buffer, images
         per level).  With dropout the mean branch reads the trunk's first images and the variance branch the m after them (an independent
         dropout draw, Q2): cls [0, m) and [m, 2m), bbox [0, n) and [n, n + m).  Without, both read the one evaluation."""
         buf, copies = trunk
         mean, var = (self.cls_score, self.cls_var) if side == 0 else (self.bbox_pred, self.bbox_cov)
-        if not st["dropout"]:
+        if not st.dropout:
             return [(conv, buf, 1, 0, 1, 1) for conv in (mean, var) if conv is not None]
-        n, m = st["n"], st["m"]
+        n, m = st.n, st.m
         first = m if side == 0 else n
         return [(mean, buf, copies, 0, first, n)] + ([(var, buf, copies, first, m, n)] if var is not None else [])
 
-    def _predict(self, jobs, st: dict, live=None, bufs=None, flat: bool = False):
+    def _predict(self, jobs, st: HeadPlan, live=None, bufs=None, flat: bool = False):
         """The predictor convs (cls_score / bbox_pred / cls_var / bbox_cov, PR:430-484), one `_launch`.  jobs: (conv, trunk buffer, images in
         it per level, first image, image count, output images) -- inference: `_jobs`'; training: all B images of a trunk, (conv, buf, B, 0,
         B, B).  Returns per job and level an (out_copies, K, H, W) NCHW tensor -- the planes K1 streams -- whose images past `count` are zero
         (never uninitialised memory: a consumer without the quirk merge would read them); flat: per job the one buffer those are views of.
         live / bufs: the sparse tower (`_trunks`)."""
-        from .sparse import REACH_PREDICTOR
-        from .wino import block_table, level_pixel_offsets
-        levels = st["levels"]
+        levels = st.levels
         sets, outs = [], []
         for ji, (conv, buf, buf_copies, first, count, out_copies) in enumerate(jobs):
             K = conv.out_channels
-            offs = level_pixel_offsets(levels, out_copies)
+            offs = wino.level_pixel_offsets(levels, out_copies)
             if bufs is not None:
                 out = bufs("p%d" % ji, (offs[-1] * K,))
             else:
                 out = (torch.zeros if out_copies > count else torch.empty)(offs[-1] * K, dtype=buf.dtype, device=buf.device)
             sets.append({"conv": conv, "src": buf, "dst": out, "planes": True,
-                         "table": block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies,
-                                              channels=st.get("channels", 512))})
+                         "table": wino.block_table(levels, count, buf.device, in_copies=buf_copies, in_first=first, out_copies=out_copies,
+                                                   channels=st.channels)})
             outs.append(out if flat else [out[offs[i] * K:offs[i + 1] * K].view(out_copies, K, h, w) for i, (h, w) in enumerate(levels)])
-        self._launch(sets, st, live=None if live is None else (lambda table: live(table, REACH_PREDICTOR)))
+        self._launch(sets, st, live=None if live is None else (lambda table: live(table, sparse.REACH_PREDICTOR)))
         return outs
 
     @staticmethod
-    def _expanded(res, st: dict):
+    def _expanded(res, st: HeadPlan):
         """Eval mode: the one evaluation of each predictor as the n runs' images (every run would give the same)."""
-        if st["dropout"] or st["n"] == 1:
+        if st.dropout or st.n == 1:
             return res
-        return [[t.expand(st["n"], -1, -1, -1).contiguous() for t in ts] for ts in res]
+        return [[t.expand(st.n, -1, -1, -1).contiguous() for t in ts] for ts in res]
 
     def takes_wino_path(self) -> bool:
         """Every conv of the head runs on pod_wino_conv3x3[_split] (GPU, fp32, one image): then all its dropout masks take the `_epoch` word."""
-        return (WINO_HEAD and self.fused_relu_dropout and FUSE_CONV_TAIL and self.cls_subnet[0].in_channels % 8 == 0
-                and self.cls_subnet[0].out_channels in (64, 128, 256, 512)
-                and max(c.out_channels for c in (self.cls_score, self.bbox_pred, self.cls_var, self.bbox_cov) if c is not None) <= 512)
+        predictors = [c for c in (self.cls_score, self.bbox_pred, self.cls_var, self.bbox_cov) if c is not None]
+        return (WINO_HEAD and self.fused_relu_dropout and FUSE_CONV_TAIL
+                and self.cls_subnet[0].in_channels % 8 == 0                       # either kernel: the fp32-MFMA kernel's channel step
+                and self.cls_subnet[0].out_channels in (64, 128, 256, 512)        # a trunk layer's channels-last output is the next one's input: no padded channels
+                and max(c.out_channels for c in predictors) <= 512)               # the predictors store their real K planes: only the padded width is bound
 
     def _relu_dropout(self, x: torch.Tensor) -> torch.Tensor:
         """ReLU + Dropout(p) after a subnet conv (PR:403-424).  On the GPU one fused in-place HIP pass
         (pod_relu_dropout) instead of torch's clamp + fused_dropout kernels."""
         if not (self.fused_relu_dropout and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
             return F.dropout(F.relu(x), self.dropout_rate, training=True)
-        from . import hip
         lib = hip.load()
         self._drop_calls += 1
         hip.check(lib.pod_relu_dropout(x.data_ptr(), x.numel(), float(self.dropout_rate), self.dropout_seed,
@@ -734,40 +706,40 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
             return t
         return new
 
-    def _plan(self, features: List[torch.Tensor], num_runs: int, mc_dropout: bool, skip_unused_last_run: bool) -> dict:
+    def _plan(self, features: List[torch.Tensor], num_runs: int, mc_dropout: bool, skip_unused_last_run: bool) -> HeadPlan:
         """The run bookkeeping of a head evaluation: n runs, of which m = n - skip need cls / cls_var / reg_var, the copies each trunk
-        evaluates, and whether every conv takes pod_wino_conv3x3 ("wino"; then "grouped" (`_grouped_ok`), "levels" and "x0", the features
+        evaluates, and whether every conv takes pod_wino_conv3x3 (`wino`; then `grouped` (`_grouped_ok`), `levels` and `x0`, the features
         as one channels-last buffer, level after level)."""
         dropout = mc_dropout and self.dropout_rate > 0.0
         n = num_runs
         skip = 1 if (skip_unused_last_run and dropout and n > 1) else 0
         m = n - skip                                               # runs whose cls / cls_var / reg_var are needed
-        st = {"n": n, "m": m, "skip": skip, "dropout": dropout,
-              "cls_copies": m * (2 if self.compute_cls_var else 1), "box_copies": n + (m if self.compute_bbox_cov else 0)}
+        st = HeadPlan(n=n, m=m, skip=skip, dropout=dropout, cls_copies=m * (2 if self.compute_cls_var else 1),
+                      box_copies=n + (m if self.compute_bbox_cov else 0))
         f = features[0]
-        st["wino"] = (self.takes_wino_path() and f.is_cuda and f.dtype == torch.float32 and f.shape[0] == 1
-                      and f.shape[1] == self.cls_subnet[0].in_channels)
-        if st["wino"]:
-            st.update(grouped=self._grouped_ok(st["cls_copies"], st["box_copies"]), levels=[(int(f.shape[2]), int(f.shape[3])) for f in features],
-                      x0=levels_channels_last(features))
+        st.wino = (self.takes_wino_path() and f.is_cuda and f.dtype == torch.float32 and f.shape[0] == 1
+                   and f.shape[1] == self.cls_subnet[0].in_channels)
+        if st.wino:
+            st.grouped, st.levels = self._grouped_ok(st.cls_copies, st.box_copies), [(int(f.shape[2]), int(f.shape[3])) for f in features]
+            st.x0 = levels_channels_last(features)
         return st
 
-    def forward_cls(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False) -> dict:
+    def forward_cls(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False) -> HeadPlan:
         """First half of the sparse evaluation (ProbabilisticRetinaNet.cls_part): the cls subnet + cls_score (+ cls_var) of all levels and
-        runs.  Returns the state `forward_bbox` continues from (the level features as one channels-last buffer among it)."""
+        runs.  Returns the plan `forward_bbox` continues from, `logits` and `logit_vars` set."""
         st = self._plan(features, num_runs, mc_dropout, skip_unused_last_run)
-        if not (st["wino"] and st["grouped"]):
+        if not (st.wino and st.grouped):
             raise RuntimeError("the sparse bbox tower needs the split kernels on the GPU (POD_WINO_SPLIT=1, one fp32 image, grouped head)")
-        (tc,) = self._trunks([(0, st["cls_copies"])], st)
+        (tc,) = self._trunks([(0, st.cls_copies)], st)
         res = self._expanded(self._predict(self._jobs(0, tc, st), st), st)
-        st.update(logits=res[0], logit_vars=res[1] if self.compute_cls_var else None)
+        st.logits, st.logit_vars = res[0], (res[1] if self.compute_cls_var else None)
         return st
 
-    def forward_bbox(self, st: dict, live):
+    def forward_bbox(self, st: HeadPlan, live):
         """Second half: bbox_subnet + bbox_pred (+ bbox_cov) over the blocks `live` (sparse.LiveBlocks) lists; None = all of them."""
-        bufs = None if live is None else self.sparse_buffers((torch.cuda.current_stream(st["x0"].device).cuda_stream, tuple(st["levels"]), st["n"],
-                                                              st["dropout"], st["skip"]))
-        (tb,) = self._trunks([(1, st["box_copies"])], st, live=live, bufs=bufs)
+        bufs = None if live is None else self.sparse_buffers((torch.cuda.current_stream(st.x0.device).cuda_stream, tuple(st.levels), st.n,
+                                                              st.dropout, st.skip))
+        (tb,) = self._trunks([(1, st.box_copies)], st, live=live, bufs=bufs)
         res = self._expanded(self._predict(self._jobs(1, tb, st), st, live=live, bufs=bufs), st)
         return res[0], (res[1] if self.compute_bbox_cov else None)
 
@@ -775,7 +747,7 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         """The training forward (PR:403-537 with dropout after every trunk conv, one evaluation per image): features per level
         (B, C, H, W), B images of one padded size -> HeadOutputs whose leading dimension is the image and whose tensors carry a grad_fn
         (pod_compare_amd/head_train.py: the HIP backward of the head's convolutions).  GPU only."""
-        from .head_train import forward_train
+        from .head_train import forward_train      # local, the one cycle: head_train imports modeling (HeadPlan) at its top
         return forward_train(self, features, anchors, image_size)
 
     def forward(self, features: List[torch.Tensor], num_runs: int = 1, mc_dropout: bool = False, skip_unused_last_run: bool = False):
@@ -787,13 +759,13 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
         tensors is zero): 3 of the 4N subnet evaluations, 7.5 % of the head at N = 10.  Only valid
         together with `merge_quirk=True` in the hot path."""
         st = self._plan(features, num_runs, mc_dropout, skip_unused_last_run)
-        if st["wino"]:
+        if st.wino:
             # every conv of the head on pod_wino_conv3x3: one launch per layer over all levels and all runs, both trunks, then the predictors
-            tc, tb = self._trunks([(0, st["cls_copies"]), (1, st["box_copies"])], st)
+            tc, tb = self._trunks([(0, st.cls_copies), (1, st.box_copies)], st)
             cj, bj = self._jobs(0, tc, st), self._jobs(1, tb, st)
             res = self._expanded(self._predict(cj[:1] + bj[:1] + cj[1:] + bj[1:], st), st)       # cls_score, bbox_pred (, cls_var) (, bbox_cov)
             return res[0], res[1], (res[2] if self.compute_cls_var else None), (res[-1] if self.compute_bbox_cov else None)
-        n, m, dropout = st["n"], st["m"], st["dropout"]
+        n, m, dropout = st.n, st.m, st.dropout
 
         def padded(t):                                            # (m, C, H, W) -> (n, C, H, W) NCHW planes (what K1 streams),
             if m == n:                                            # last slab untouched; a channels-last trunk output is
@@ -805,8 +777,8 @@ class ProbabilisticRetinaNetHead(_TracksStorage):
 
         logits, deltas, logit_vars, delta_covs = [], [], [], []
         for level, f in enumerate(features):
-            tc = self._trunk(self.cls_subnet, f, st["cls_copies"], dropout, level)
-            tb = self._trunk(self.bbox_subnet, f, st["box_copies"], dropout, level)
+            tc = self._trunk(self.cls_subnet, f, st.cls_copies, dropout, level)
+            tb = self._trunk(self.bbox_subnet, f, st.box_copies, dropout, level)
             if dropout:
                 # (a channels-last trunk hands its last activation over as NCHW planes: the A*K / A*4-channel predictor convs
                 #  are faster as NCHW Winograd calls than as NHWC implicit GEMMs)
@@ -890,7 +862,6 @@ class ProbabilisticRetinaNet(_TracksStorage):
         gt_classes are per-image lists of (G_i, 4) XYXY boxes in network-input pixels and (G_i,) contiguous class ids.  Returns
         {"loss_cls", "loss_box_reg"} as device scalars.  The state the reference keeps on the model (loss_normalizer, current_step) lives in
         `self.loss_state` (losses.ProbabilisticLosses); eps / normalizer as in its __call__."""
-        from . import losses as _losses
         if getattr(self, "loss_state", None) is None:
             self.loss_state = _losses.ProbabilisticLosses(num_classes=self.num_classes, cls_var_num_samples=self.cls_var_num_samples)
         labels, matched, _ = _losses.label_anchors(outputs.anchors, gt_boxes, gt_classes, self.num_classes)
@@ -929,31 +900,39 @@ class ProbabilisticRetinaNet(_TracksStorage):
             ts = self._fingerprint_tensors = (gen, [t for t in list(self.parameters()) + list(self.buffers()) if t is not self.head._epoch])
         return gen, len(ts[1]), sum(t._version for t in ts[1])
 
-    def _cls_eager(self, image: torch.Tensor, n: int, dropout: bool, skip: bool) -> dict:
+    def _cls_eager(self, image: torch.Tensor, n: int, dropout: bool, skip: bool) -> HeadPlan:
         feats, padded = self._trunk_eager(image)
         st = self.head.forward_cls(feats, n, mc_dropout=dropout, skip_unused_last_run=skip)
-        st.update(padded=padded, image_hw=tuple(image.shape[-2:]), shapes=[tuple(f.shape[-2:]) for f in feats])
+        st.padded, st.image_hw, st.shapes = padded, tuple(image.shape[-2:]), [tuple(f.shape[-2:]) for f in feats]
         return st
 
-    @torch.no_grad()
-    def cls_part(self, image: torch.Tensor, num_mc_dropout_runs: int = -1, skip_unused_last_run: bool = False, mc_dropout: Optional[bool] = None) -> dict:
-        """First part of a forward with the sparse bbox tower: trunk + the cls side of the head (captured into a HIP graph like a whole forward
-        when graphs are enabled).  Returns the state `bbox_part` continues from; state["partial"] is the HeadOutputs with cls / cls_var set."""
+    def _run_args(self, num_mc_dropout_runs: int, mc_dropout: Optional[bool]) -> Tuple[int, bool]:
+        """(n runs, dropout active) of a forward's arguments: dropout defaults to "several runs are requested", and needs a model that has it."""
         n = num_mc_dropout_runs if num_mc_dropout_runs > 1 else 1
         if mc_dropout is None:
             mc_dropout = n > 1
-        dropout = bool(mc_dropout) and self.use_dropout
-        graphs = (self.use_graphs and image.is_cuda and self.device.type == "cuda" and self.head.dropout_replay is None
-                  and (not dropout or self.head.takes_wino_path()))
-        st = self._forward_graphed(image, n, dropout, skip_unused_last_run, part="cls") if graphs else self._cls_eager(image, n, dropout, skip_unused_last_run)
-        return st
+        return n, bool(mc_dropout) and self.use_dropout
 
-    def partial_outputs(self, st: dict, delta=None, reg_var=None) -> HeadOutputs:
-        return HeadOutputs(st["logits"], delta, st["logit_vars"], reg_var, self.anchors_for(st["padded"]), st["shapes"], self.num_anchors,
-                           self.num_classes, st["image_hw"], last_run_valid=not bool(st["skip"]))
+    def _graphable(self, image: torch.Tensor, dropout: bool) -> bool:
+        """This forward may be captured and replayed (see "HIP graphs" above for what may not)."""
+        return (self.use_graphs and image.is_cuda and self.device.type == "cuda" and self.head.dropout_replay is None
+                and (not dropout or self.head.takes_wino_path()))
 
     @torch.no_grad()
-    def bbox_part(self, st: dict, live) -> HeadOutputs:
+    def cls_part(self, image: torch.Tensor, num_mc_dropout_runs: int = -1, skip_unused_last_run: bool = False, mc_dropout: Optional[bool] = None) -> HeadPlan:
+        """First part of a forward with the sparse bbox tower: trunk + the cls side of the head (captured into a HIP graph like a whole forward
+        when graphs are enabled).  Returns the plan `bbox_part` continues from; `partial_outputs` of it is the HeadOutputs with cls / cls_var set."""
+        n, dropout = self._run_args(num_mc_dropout_runs, mc_dropout)
+        if self._graphable(image, dropout):
+            return self._forward_graphed(image, n, dropout, skip_unused_last_run, part="cls")
+        return self._cls_eager(image, n, dropout, skip_unused_last_run)
+
+    def partial_outputs(self, st: HeadPlan, delta=None, reg_var=None) -> HeadOutputs:
+        return HeadOutputs(st.logits, delta, st.logit_vars, reg_var, self.anchors_for(st.padded), st.shapes, self.num_anchors,
+                           self.num_classes, st.image_hw, last_run_valid=not bool(st.skip))
+
+    @torch.no_grad()
+    def bbox_part(self, st: HeadPlan, live) -> HeadOutputs:
         """Second part: the bbox side over the blocks `live` (sparse.LiveBlocks, made from the candidates the caller selected) lists."""
         delta, reg_var = self.head.forward_bbox(st, live)
         return self.partial_outputs(st, delta, reg_var)
@@ -986,7 +965,6 @@ class ProbabilisticRetinaNet(_TracksStorage):
             self._graph_serial += 1
             epoch = torch.full_like(shared_epoch, self._graph_serial << 32)
             self.head._epoch = epoch
-            from . import amax
             try:
                 for _ in range(2):                       # eager: MIOpen's solver search, filter transforms, block tables, anchors
                     run(static_in, n, dropout, skip)
@@ -1042,43 +1020,42 @@ class ProbabilisticRetinaNet(_TracksStorage):
         only -- runs over the blocks that can reach a candidate.  Its outputs are defined at the candidates' cells and stale elsewhere; same
         Philox offsets, so the same dropout masks as the dense evaluation.  The trunk + cls half is replayed as a HIP graph (`cls_part`), the
         bbox half is enqueued eagerly (its live lists are made per image)."""
-        n = num_mc_dropout_runs if num_mc_dropout_runs > 1 else 1
-        if mc_dropout is None:
-            mc_dropout = n > 1
-        dropout = bool(mc_dropout) and self.use_dropout
+        n, dropout = self._run_args(num_mc_dropout_runs, mc_dropout)
         if sparse_bbox is not None:
             st = self.cls_part(image, num_mc_dropout_runs, skip_unused_last_run, mc_dropout)
             return self.bbox_part(st, sparse_bbox(self.partial_outputs(st)))
-        if (self.use_graphs and image.is_cuda and self.device.type == "cuda" and self.head.dropout_replay is None
-                and (not dropout or self.head.takes_wino_path())):
+        if self._graphable(image, dropout):
             return self._forward_graphed(image, n, dropout, skip_unused_last_run)
         return self._forward_eager(image, n, dropout, skip_unused_last_run)
 
     def _cl_backbone(self, x: torch.Tensor) -> bool:
         """The trunk runs channels-last on pod_conv1x1_split + pod_wino_conv3x3_split: GPU, fp32, FrozenBN folded, the split kernels
         selected (POD_WINO_SPLIT=0 -- the fp32-MFMA reference leg -- keeps the 1x1 convolutions on MIOpen as in round 3)."""
-        from . import wino
         if not (CL_BACKBONE and FUSE_CONV_TAIL and WINO_BACKBONE and wino.SPLIT_BF16 and x.is_cuda and x.dtype == torch.float32):
             return False
         if not getattr(self, "_cl_ok", False):
             self._cl_ok = self.bottom_up.cl_eligible() and self.fpn.cl_eligible()       # (cached once true: folding is one-way)
         return self._cl_ok
 
-    def _trunk_eager(self, image: torch.Tensor):
-        """Frame -> (the five FPN maps, padded (h, w)): everything ahead of the head."""
+    def _backbone_cl(self, image: torch.Tensor):
+        """Frame -> ([(c3, h, w), (c4, h, w), (c5, h, w)] channels-last, padded (h, w)) when the channels-last HIP backbone takes it, else None."""
         if (image.is_cuda and image.device == self.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
                 and image.dtype in (torch.uint8, torch.float32) and self._cl_backbone(self.pixel_mean) and self.bottom_up.hip_stem_ok()):
             # the frame as the loader hands it over: pod_stem7x7_split normalises ((x - mean) / std, PR:96) and pads on load
             padded = _anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
-            feats = self.fpn.forward_cl(self.bottom_up.forward_cl(None, frame=(image, self.pixel_mean.reshape(3), self.pixel_std.reshape(3), padded)))
-        else:
-            x = self.preprocess_image(image)
-            if self._cl_backbone(x):
-                feats = self.fpn.forward_cl(self.bottom_up.forward_cl(x))      # channels-last trunk on pod_conv1x1_split + pod_wino_conv3x3[_split]
-            else:
-                feats = self.fpn(self.bottom_up(x))
-            padded = tuple(x.shape[-2:])
-        return feats, padded
+            return self.bottom_up.forward_cl(None, frame=(image, self.pixel_mean.reshape(3), self.pixel_std.reshape(3), padded)), padded
+        x = self.preprocess_image(image)
+        if self._cl_backbone(x):
+            return self.bottom_up.forward_cl(x), tuple(x.shape[-2:])      # channels-last trunk on pod_conv1x1_split + pod_wino_conv3x3[_split]
+        return None
+
+    def _trunk_eager(self, image: torch.Tensor):
+        """Frame -> (the five FPN maps, padded (h, w)): everything ahead of the head."""
+        cl = self._backbone_cl(image)
+        if cl is not None:
+            return self.fpn.forward_cl(cl[0]), cl[1]
+        x = self.preprocess_image(image)                                 # the NCHW path (CPU tensors, the tests' reference; normalised a second time here)
+        return self.fpn(self.bottom_up(x)), tuple(x.shape[-2:])
 
     def _head_eager(self, feats, padded, image_hw, n: int, mc_dropout: bool, skip_unused_last_run: bool) -> HeadOutputs:
         shapes = [tuple(f.shape[-2:]) for f in feats]

@@ -28,8 +28,12 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import checkpoint, losses
+from .apply_net import CocoImages, Prefetched, add_dataset_arguments, evaluation_category_map
+from .compute_losses import image_ground_truth
+from .config import setup_config
 from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import head_convs
+from .probabilistic_inference import build_model
 
 
 def warmup_multistep_lr(iteration: int, base_lr: float, steps: Sequence[int], gamma: float, warmup_iters: int, warmup_factor: float) -> float:
@@ -117,10 +121,6 @@ def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, trai
 
 
 def main(argv=None):
-    from .apply_net import CocoImages, Prefetched, add_dataset_arguments, evaluation_category_map
-    from .compute_losses import image_ground_truth
-    from .config import setup_config
-    from .probabilistic_inference import build_model
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
                                  epilog="A step takes SOLVER.IMS_PER_BATCH frames of ONE resized shape: the sampler batches frames of equal shape "
                                         "together, in data-set order; frames of a shape wait until a batch of them is complete.  Only the head "

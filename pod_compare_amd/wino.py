@@ -168,7 +168,7 @@ class WinoConv:
         assert weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)
         self.K, self.C = int(weight.shape[0]), int(weight.shape[1])
         self.Kpad = (self.K + 63) // 64 * 64
-        if self.C % 8 or self.Kpad not in (64, 128, 256, 512):
+        if self.C % 8 or self.Kpad not in (64, 128, 256, 512):     # the fp32-MFMA kernel's channel step (the split kernel's, C % 16: `split` below); K only as padded
             raise ValueError("pod_wino_conv3x3: C %% 8 == 0 and K <= 512 in steps of 64 required, got C=%d K=%d" % (self.C, self.K))
         lib = hip.load()
         self.split = (SPLIT_BF16 if split is None else bool(split)) and self.C % 16 == 0
@@ -185,6 +185,12 @@ class WinoConv:
             self.bias = torch.zeros(self.Kpad, dtype=torch.float32, device=weight.device)
             self.bias[:self.K].copy_(bias.detach())
         self.version = (weight._version, None if bias is None else bias._version, weight.data_ptr())
+
+    @staticmethod
+    def eligible(conv: Optional[torch.nn.Conv2d]) -> bool:
+        """The shape these kernels compute.  The channel rules differ by kernel and by output layout: each caller states its own."""
+        return (conv is not None and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+                and conv.groups == 1 and tuple(conv.dilation) == (1, 1))
 
     def __call__(self, src: torch.Tensor, dst: torch.Tensor, table: torch.Tensor, relu: bool = False, dropout_p: float = 0.0,
                  seed: int = 0, offset: int = 0, planes: bool = False, epoch: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None) -> torch.Tensor:

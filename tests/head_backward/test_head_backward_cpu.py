@@ -164,7 +164,7 @@ def plan_of(monkeypatch, p, subnets, **st):
         return real(levels, copies, device, **kw)
     monkeypatch.setattr(wino, "block_table", block_table)
     x0 = torch.zeros(PLAN_PIXELS * st.get("images", 1), PLAN_C)
-    plan = head._trunk_plan(subnets, dict(st, x0=x0, levels=PLAN_LEVELS, grouped=True))
+    plan = head._trunk_plan(subnets, modeling.HeadPlan(x0=x0, levels=PLAN_LEVELS, grouped=True, **st))
     assert len(plan["layers"]) == 4 and all(len(sets) == len(subnets) for sets in plan["layers"])
     assert all(s["conv"] is (head.cls_subnet, head.bbox_subnet)[sid][l] for l, sets in enumerate(plan["layers"]) for s, (sid, _) in zip(sets, subnets))
     return head, plan, x0, tables
@@ -210,5 +210,6 @@ def test_training_plan(monkeypatch, p):
     if p > 0.0:                                                    # replay: the launches draw no masks, the recorded ones are applied after them
         head._drop_calls = 7
         head.dropout_replay = lambda sid, layer, level, copy_: None
-        again = head._trunk_plan([(0, 2), (1, 2)], {"x0": x0, "levels": PLAN_LEVELS, "grouped": True, "dropout": False, "images": 2, "channels": 64})
+        from pod_compare_amd.modeling import HeadPlan
+        again = head._trunk_plan([(0, 2), (1, 2)], HeadPlan(x0=x0, levels=PLAN_LEVELS, grouped=True, dropout=False, images=2, channels=64))
         assert again["replay"] and again["kw"]["dropout_p"] == 0.0 and again["layers"][3][1]["offset"] == 15 << 34

@@ -3,6 +3,7 @@ build's model is validated against the reference's constructor constants and lay
 naive restatements of its own forward)."""
 import math
 
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -95,3 +96,20 @@ def test_preprocess_pads_to_fpn_divisibility_and_normalises():
     assert float(x[0, :, 60, 90].abs().max()) == 0.0                                   # zero padding
     r = modeling.resize_test_image(torch.zeros(3, 720, 1280))
     assert r.shape == (3, 750, 1333)
+
+
+@pytest.mark.parametrize("mc_dropout, want", [(True, dict(n=10, m=9, skip=1, cls_copies=18, box_copies=19)),
+                                              (False, dict(n=10, m=10, skip=0))])      # skipping the last run needs dropout
+def test_head_plan_run_arithmetic(mc_dropout, want):
+    """`_plan` of 10 runs with skip_unused_last_run: m = n - skip runs need cls / cls_var / reg_var; the cls trunk evaluates m for the mean
+    and m for the variance, the bbox trunk n for the mean and m for the covariance.  CPU features never take the Winograd path."""
+    torch.manual_seed(0)
+    head = modeling.ProbabilisticRetinaNetHead(compute_cls_var=True, compute_bbox_cov=True, dropout_rate=0.1)
+    st = head._plan([torch.zeros(1, 256, 4, 6), torch.zeros(1, 256, 2, 3)], 10, mc_dropout, True)
+    assert isinstance(st, modeling.HeadPlan) and st.wino is False
+    assert {k: getattr(st, k) for k in want} == want
+
+
+def test_head_plan_rejects_a_misspelt_field():
+    with pytest.raises(TypeError):
+        modeling.HeadPlan(levls=[(4, 6)])

@@ -275,7 +275,7 @@ def test_eval_mode_evaluates_each_trunk_once_on_the_gpu():
     real_all = model.head._trunks
 
     def counting_all(subnets, st, **kw):                          # (all levels, one launch per layer)
-        calls["n"] += len(subnets) * len(st["levels"])
+        calls["n"] += len(subnets) * len(st.levels)
         return real_all(subnets, st, **kw)
 
     model.head._trunk = counting
