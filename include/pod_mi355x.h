@@ -776,6 +776,32 @@ int pod_col2im3x3s2_cl(const float* dcols, const float* gate, const float* add, 
                        pod_stream_t stream);
 int pod_upsample2_sum_cl(const float* d_child, int32_t h, int32_t w, const float* add, float* d_top, int32_t C, float* d_top_amax, pod_stream_t stream);
 
+/* ---- K24  backward of the ResNet bottlenecks (csrc/k24_resnet_backward.hip) -------------------------------------------------
+ * Serves: the backward pass of detectron2's BottleneckBlock (1x1 with STRIDE_IN_1X1, 3x3, 1x1, shortcut; FrozenBN) in res3 - res5 under
+ * train_net.py:18-81 (`Trainer(DefaultTrainer)`, `trainer.train()`: every parameter above MODEL.BACKBONE.FREEZE_AT = 2 moves), behind
+ * `self.backbone(images.tensor)` (probabilistic_retinanet.py:96-100); the reference gets it from autograd.  The 1x1 input gradients run on
+ * pod_conv1x1_split with the transposed filter, the 3x3 ones on K22 and the patch-matrix GEMM, the gates on pod_relu_dropout_backward.
+ * What is new: the 1x1 weight gradient at the backbone's widths and strides, and the input gradient of the stride's pixel selection.  Three
+ * new symbols under POD_ABI_VERSION 18, as for K20 - K23: no entry or structure that existed changed, so the number stands.
+ *
+ * pod_conv1x1_wgrad_strided: x dev (images * H_in * W_in, C), dy dev (images * Ho * Wo, K), channels-last fp32, Ho = (H_in - 1) / stride + 1,
+ *   Wo = (W_in - 1) / stride + 1.  dW dev fp32 (K, C):
+ *   dW[k][c] = sum over (b, oy, ox) of dy[(b, oy, ox)][k] x[b H_in W_in + stride oy W_in + stride ox][c]; db dev fp32 (K) or NULL: the column
+ *   sums of dy.  stride 1 or 2, C % 16 == 0, C <= 18432, K % 64 == 0, K <= 2048, images * H_in * W_in < 2^30.  Arithmetic, slices (of the
+ *   images * Ho * Wo OUTPUT pixels), `partials` (pod_conv1x1_wgrad_strided_partials(...) floats, 16-byte aligned; 0 = invalid geometry) and
+ *   the fixed-order fp64 second launch as pod_conv1x1_wgrad: on the same pixels the two give the same bits.  The rows a stride selects are
+ *   gathered in the kernel's loads, never materialised.  dW, db and partials may alias neither each other nor an operand.
+ * pod_subsample2_scatter_cl: the input gradient of the stride-2 pixel selection for one image, with the gate and the sum the full map needs
+ *   in the same pass.  d_small dev (Ho * Wo, C), Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; gate, add, dx dev (H * W, C):
+ *   dx[(y, x)][c] = (gate == NULL or gate[(y, x)][c] > 0) ? ((y and x even ? d_small[(y / 2) Wo + x / 2][c] : 0) + (add == NULL ? 0 :
+ *   add[(y, x)][c])) : 0 -- `add` sits INSIDE the gate, unlike pod_col2im3x3s2_cl: the gate is the ReLU that closes the block whose output the
+ *   map is.  add may be dx; dx may be neither d_small nor gate.  C % 4 == 0.  dx_amax: NULL or the zeroed record that receives max |dx|. */
+int64_t pod_conv1x1_wgrad_strided_partials(int32_t images, int32_t H_in, int32_t W_in, int32_t stride, int32_t C, int32_t K);
+int pod_conv1x1_wgrad_strided(const float* x, const float* dy, int32_t images, int32_t H_in, int32_t W_in, int32_t stride, int32_t C, int32_t K,
+                              const float* x_amax, const float* dy_amax, float* dW, float* db, float* partials, pod_stream_t stream);
+int pod_subsample2_scatter_cl(const float* d_small, const float* gate, const float* add, float* dx, int32_t H, int32_t W, int32_t C, float* dx_amax,
+                              pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -13,6 +13,8 @@
 // half-wave read 32 consecutive channels of one pixel, conflict-free whatever the row stride).  The next step's rows are asked for ahead of
 // the current step's products.  A pixel tail and a channel-tile edge are zero-filled in the staging, never read.
 //
+// (The kernel itself, k_conv1x1_wgrad, is in pod_wgrad.h: K24 launches it too, on the rows a stride selects.)
+//
 // Parallelism and determinism: the pixels are cut into SLICES of c1w_slice_pixels(pixels, C, K) consecutive pixels -- the geometry alone:
 // 1024, halved down to 128 while the launch has fewer than 512 workgroups; grid = slices x k tiles x c tiles.  A slice writes its
 // partial sums [slice][k][c], and pod_wgrad.h's second launch adds them in slice order, in fp64 (db: fp64 column sums over chunks of
@@ -24,114 +26,6 @@
 #include "pod_wgrad.h"
 
 namespace pod {
-
-constexpr int C1W_STEP = 32;            // pixels of one step
-constexpr int C1W_KT = 64, C1W_CT = 128;
-constexpr int C1W_DS = C1W_KT + 4;      // LDS row strides, floats (16-byte rows; any stride serves the column reads)
-constexpr int C1W_XS = C1W_CT + 4;
-constexpr int C1W_MAX_C = 18432;        // p6's patch matrix: 9 x 2048
-
-// Host and device agree on the slices through this function of the geometry alone.
-static inline int c1w_slice_pixels(int64_t pixels, int C, int K) {
-    const int64_t tiles = (int64_t)(K / C1W_KT) * ((C + C1W_CT - 1) / C1W_CT);
-    int s = 1024;
-    while (s > 128 && ((pixels + s - 1) / s) * tiles < 512) s >>= 1;
-    return s;
-}
-
-__global__ void __launch_bounds__(256, 2) k_conv1x1_wgrad(const float* __restrict__ X, const float* __restrict__ dY, const int64_t pixels, const int C, const int K,
-                                                       const int slice_px, const float* __restrict__ x_amax, const float* __restrict__ dy_amax,
-                                                       float* __restrict__ partials) {
-    __shared__ __attribute__((aligned(16))) float ds[C1W_STEP * C1W_DS];
-    __shared__ __attribute__((aligned(16))) float xs[C1W_STEP * C1W_XS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int i32 = lane & 31, h = lane >> 5, kb = wave & 1, cw = wave >> 1;
-    const int slice = blockIdx.x, k0 = blockIdx.y * C1W_KT, c0 = blockIdx.z * C1W_CT;
-    const float sx = sg_activation_scale(x_amax), sd = sg_activation_scale(dy_amax);
-    const int64_t p_begin = (int64_t)slice * slice_px;
-    const int64_t p_end = p_begin + slice_px < pixels ? p_begin + slice_px : pixels;
-    // staging: dY 32 pixels x 16 channel quads = 2 quads a thread, X 32 pixels x 32 quads = 4 quads a thread
-    const int dq = t & 15, dp = t >> 4;          // dY: quad, pixel (+ 16 for the second)
-    const int xq = t & 31, xp = t >> 5;          // X: quad, pixel (+ 8 j)
-    const bool x_in = c0 + 4 * xq < C;           // (C % 16 == 0: a quad is inside or outside as a whole)
-
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 dreg[2], xreg[4];
-    auto load = [&](int64_t p0) {                // the step's rows -> registers, zeros past the slice's last pixel and past C
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int64_t p = p0 + dp + 16 * j;
-            dreg[j] = p < p_end ? *reinterpret_cast<const f32x4*>(dY + p * K + k0 + 4 * dq) : zero4;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t p = p0 + xp + 8 * j;
-            xreg[j] = (p < p_end && x_in) ? *reinterpret_cast<const f32x4*>(X + p * C + c0 + 4 * xq) : zero4;
-        }
-    };
-
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 acc[2] = {zero16, zero16};
-
-    load(p_begin);
-    for (int64_t p0 = p_begin; p0 < p_end; p0 += C1W_STEP) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(ds + (dp + 16 * j) * C1W_DS + 4 * dq) = dreg[j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(xs + (xp + 8 * j) * C1W_XS + 4 * xq) = xreg[j];
-        __syncthreads();
-        if (p0 + C1W_STEP < p_end) load(p0 + C1W_STEP);      // (uniform) in flight behind the products below
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            if (p0 + 16 * s >= p_end) break;                 // (uniform) a half step of zeros
-            // the lane's 8 pixels 16 s + 8 h .. + 7 of channel 32 kb + i32 of dY, split
-            sg_u32x4 dyf[2];
-            {
-                const float* p = ds + (16 * s + 8 * h) * C1W_DS + 32 * kb + i32;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    uint32_t w[2];
-                    wino_f16_split2(p[(2 * m) * C1W_DS], p[(2 * m + 1) * C1W_DS], sd, w);
-                    dyf[0][m] = w[0];
-                    dyf[1][m] = w[1];
-                }
-            }
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                sg_u32x4 xf[2];
-                const float* p = xs + (16 * s + 8 * h) * C1W_XS + 64 * cw + 32 * cb + i32;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    uint32_t w[2];
-                    wino_f16_split2(p[(2 * m) * C1W_XS], p[(2 * m + 1) * C1W_XS], sx, w);
-                    xf[0][m] = w[0];
-                    xf[1][m] = w[1];
-                }
-                // small products first (as k12 / k13 / k22)
-                f32x16 a = acc[cb];
-                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[1]), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[1]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
-                acc[cb] = a;
-            }
-        }
-        __syncthreads();
-    }
-
-    // partial sums [slice][k < K][c < C]: accumulator register j of a lane is row (j & 3) + 8 (j >> 2) + 4 h, column i32
-    const float inv = wino_pow2_inverse(sx) * wino_pow2_inverse(sd);
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-        const int c = c0 + 64 * cw + 32 * cb + i32;
-        if (c < C) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int k = k0 + 32 * kb + (j & 3) + 8 * (j >> 2) + 4 * h;
-                partials[((int64_t)slice * K + k) * C + c] = acc[cb][j] * inv;
-            }
-        }
-    }
-}
 
 // dx[(y, x)][c] = gate(sum of the entries of dcols that read pixel (y, x)) + add: tap (ty, tx) of output pixel (oy, ox) read input pixel
 // (2 oy + ty - 1, 2 ox + tx - 1), so pixel (y, x) is met by oy = (y + 1 - ty) / 2 where that is integral and in range -- ty, tx ascending.
@@ -220,8 +114,8 @@ extern "C" int pod_conv1x1_wgrad(const float* x, const float* dy, int64_t pixels
         hipLaunchKernelGGL(pod::k_wgrad_db<pod::WG_DB_CHUNK>, dim3((unsigned)n_chunks, (unsigned)(K / 64)), dim3(256), 0, s, dy, pixels, K, dbp);
         POD_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(pod::k_conv1x1_wgrad, dim3((unsigned)n_slices, (unsigned)(K / pod::C1W_KT), (unsigned)((C + pod::C1W_CT - 1) / pod::C1W_CT)), dim3(256), 0, s, x, dy,
-                       pixels, C, K, sp, x_amax, dy_amax, wp);
+    hipLaunchKernelGGL(pod::k_conv1x1_wgrad<false>, dim3((unsigned)n_slices, (unsigned)(K / pod::C1W_KT), (unsigned)((C + pod::C1W_CT - 1) / pod::C1W_CT)), dim3(256), 0, s, x, dy,
+                       pixels, C, K, sp, x_amax, dy_amax, wp, pod::C1wGather{});
     POD_CHECK_LAUNCH();
     const int64_t n_out = (int64_t)K * C + (db ? K : 0);
     hipLaunchKernelGGL(pod::k_wgrad_reduce<1>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, K, dW, db);

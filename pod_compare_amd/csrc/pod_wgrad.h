@@ -1,5 +1,6 @@
 // What the weight-gradient kernels share (k22_conv3x3_wgrad.hip, k23_fpn_backward.hip): the bias gradient's fp64 column sums and the
-// second launch that adds the slices' partial sums in slice order.  Templates, so that each file that launches them carries its own copy.
+// second launch that adds the slices' partial sums in slice order -- and the 1x1 weight gradient's kernel, which K23 launches on consecutive
+// rows and K24 (k24_resnet_backward.hip) on the rows a stride selects.  Templates, so that each file that launches them carries its own copy.
 #pragma once
 #include "pod_split_gemm.h"
 
@@ -45,6 +46,132 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce(const float* __restrict__ 
         double a = 0.0;
         for (int ch = 0; ch < n_chunks; ++ch) a += dbp[(int64_t)ch * Kpad + k];
         db[k] = (float)a;
+    }
+}
+
+constexpr int C1W_STEP = 32;            // pixels of one step
+constexpr int C1W_KT = 64, C1W_CT = 128;
+constexpr int C1W_DS = C1W_KT + 4;      // LDS row strides, floats (16-byte rows; any stride serves the column reads)
+constexpr int C1W_XS = C1W_CT + 4;
+constexpr int C1W_MAX_C = 18432;        // p6's patch matrix: 9 x 2048
+
+// Host and device agree on the slices through this function of the geometry alone.
+static inline int c1w_slice_pixels(int64_t pixels, int C, int K) {
+    const int64_t tiles = (int64_t)(K / C1W_KT) * ((C + C1W_CT - 1) / C1W_CT);
+    int s = 1024;
+    while (s > 128 && ((pixels + s - 1) / s) * tiles < 512) s >>= 1;
+    return s;
+}
+
+// The rows of X that the output pixels pair with, for a 1x1 convolution of stride 1 or 2 (k24_resnet_backward.hip): output pixel
+// p = (b, oy, ox) of a (Ho, Wo) map reads input row pin(p) = b H_in W_in + stride (oy W_in + ox).  Counts fit 30 bits (the host checks).
+struct C1wGather {
+    int Wo, HoWo, W_in, HWin, stride;
+};
+
+// GATHER = false: X's rows are the pixels as they lie there (K23; `g` is not read).  GATHER = true: row p of X is X + pin(p) C, taken in the
+// staging loads and never materialised.
+template <bool GATHER>
+__global__ void __launch_bounds__(256, 2) k_conv1x1_wgrad(const float* __restrict__ X, const float* __restrict__ dY, const int64_t pixels, const int C, const int K,
+                                                       const int slice_px, const float* __restrict__ x_amax, const float* __restrict__ dy_amax,
+                                                       float* __restrict__ partials, const C1wGather g) {
+    __shared__ __attribute__((aligned(16))) float ds[C1W_STEP * C1W_DS];
+    __shared__ __attribute__((aligned(16))) float xs[C1W_STEP * C1W_XS];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i32 = lane & 31, h = lane >> 5, kb = wave & 1, cw = wave >> 1;
+    const int slice = blockIdx.x, k0 = blockIdx.y * C1W_KT, c0 = blockIdx.z * C1W_CT;
+    const float sx = sg_activation_scale(x_amax), sd = sg_activation_scale(dy_amax);
+    const int64_t p_begin = (int64_t)slice * slice_px;
+    const int64_t p_end = p_begin + slice_px < pixels ? p_begin + slice_px : pixels;
+    // staging: dY 32 pixels x 16 channel quads = 2 quads a thread, X 32 pixels x 32 quads = 4 quads a thread
+    const int dq = t & 15, dp = t >> 4;          // dY: quad, pixel (+ 16 for the second)
+    const int xq = t & 31, xp = t >> 5;          // X: quad, pixel (+ 8 j)
+    const bool x_in = c0 + 4 * xq < C;           // (C % 16 == 0: a quad is inside or outside as a whole)
+
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dreg[2], xreg[4];
+    auto load = [&](int64_t p0) {                // the step's rows -> registers, zeros past the slice's last pixel and past C
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int64_t p = p0 + dp + 16 * j;
+            dreg[j] = p < p_end ? *reinterpret_cast<const f32x4*>(dY + p * K + k0 + 4 * dq) : zero4;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t p = p0 + xp + 8 * j;
+            if constexpr (GATHER) {
+                xreg[j] = zero4;
+                if (p < p_end && x_in) {
+                    const uint32_t up = (uint32_t)p, b = up / (uint32_t)g.HoWo, r = up - b * (uint32_t)g.HoWo, oy = r / (uint32_t)g.Wo, ox = r - oy * (uint32_t)g.Wo;
+                    const int64_t pin = (int64_t)(b * (uint32_t)g.HWin + (uint32_t)g.stride * (oy * (uint32_t)g.W_in + ox));
+                    xreg[j] = *reinterpret_cast<const f32x4*>(X + pin * C + c0 + 4 * xq);
+                }
+            } else {
+                xreg[j] = (p < p_end && x_in) ? *reinterpret_cast<const f32x4*>(X + p * C + c0 + 4 * xq) : zero4;
+            }
+        }
+    };
+
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 acc[2] = {zero16, zero16};
+
+    load(p_begin);
+    for (int64_t p0 = p_begin; p0 < p_end; p0 += C1W_STEP) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *reinterpret_cast<f32x4*>(ds + (dp + 16 * j) * C1W_DS + 4 * dq) = dreg[j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(xs + (xp + 8 * j) * C1W_XS + 4 * xq) = xreg[j];
+        __syncthreads();
+        if (p0 + C1W_STEP < p_end) load(p0 + C1W_STEP);      // (uniform) in flight behind the products below
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (p0 + 16 * s >= p_end) break;                 // (uniform) a half step of zeros
+            // the lane's 8 pixels 16 s + 8 h .. + 7 of channel 32 kb + i32 of dY, split
+            sg_u32x4 dyf[2];
+            {
+                const float* p = ds + (16 * s + 8 * h) * C1W_DS + 32 * kb + i32;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    uint32_t w[2];
+                    wino_f16_split2(p[(2 * m) * C1W_DS], p[(2 * m + 1) * C1W_DS], sd, w);
+                    dyf[0][m] = w[0];
+                    dyf[1][m] = w[1];
+                }
+            }
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                sg_u32x4 xf[2];
+                const float* p = xs + (16 * s + 8 * h) * C1W_XS + 64 * cw + 32 * cb + i32;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    uint32_t w[2];
+                    wino_f16_split2(p[(2 * m) * C1W_XS], p[(2 * m + 1) * C1W_XS], sx, w);
+                    xf[0][m] = w[0];
+                    xf[1][m] = w[1];
+                }
+                // small products first (as k12 / k13 / k22)
+                f32x16 a = acc[cb];
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[1]), a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[1]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wino_f16x8, dyf[0]), __builtin_bit_cast(wino_f16x8, xf[0]), a, 0, 0, 0);
+                acc[cb] = a;
+            }
+        }
+        __syncthreads();
+    }
+
+    // partial sums [slice][k < K][c < C]: accumulator register j of a lane is row (j & 3) + 8 (j >> 2) + 4 h, column i32
+    const float inv = wino_pow2_inverse(sx) * wino_pow2_inverse(sd);
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        const int c = c0 + 64 * cw + 32 * cb + i32;
+        if (c < C) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = k0 + 32 * kb + (j & 3) + 8 * (j >> 2) + 4 * h;
+                partials[((int64_t)slice * K + k) * C + c] = acc[cb][j] * inv;
+            }
+        }
     }
 }
 

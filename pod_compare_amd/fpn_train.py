@@ -10,7 +10,10 @@ they are of):
     output convs     dW, db = pod_conv3x3_wgrad(l_i, dP_i) (K22); dL_i = the GEMM of dP_i's patch matrix with the flipped, transposed filter
                      (head_train.input_grad_gemm)
     top-down         dL4 += up2_sum(dL3), dL5 += up2_sum(dL4) (pod_upsample2_sum_cl), l3 first
-    laterals         dW, db = pod_conv1x1_wgrad(c_i, dL_i); nothing reaches below them
+    laterals         dW, db = pod_conv1x1_wgrad(c_i, dL_i)
+    below            only when the maps c3 - c5 require it (the ResNet trains: resnet_train.py): dC_i = dL_i W_lateral_i, the GEMM with the
+                     transposed filter on pod_conv1x1_split, and for c5 also pod_col2im3x3s2_cl(dP6 W9(p6)), ungated -- the gate of a map is its
+                     producer's and is applied there.  Otherwise nothing reaches below the laterals and p6, and nothing more is launched.
 GPU only -- anything this path cannot take raises (hip.PodError): there is no fallback."""
 from typing import List, Sequence, Tuple
 
@@ -48,6 +51,20 @@ def _dcols_gemm(conv):
     return conv_forms.derived(conv, "_pod_dcols_gemm", make)
 
 
+def transposed_gemm(conv, negated: bool = False):
+    """dX = dY W for a 1x1 conv's (K, C) filter: the GEMM with the transposed filter on pod_conv1x1_split, split once and cached by the
+    weight's version (conv_forms.derived).  Called as gemm(dY (pixels, K), pixels, 1[, residual=...]) -> (pixels, C).  negated: the same
+    with -W (every f16 term and every product the exact negative: what differs from -(dY W) is the accumulation's error alone)."""
+    def make(c):
+        K, C = c.out_channels, c.in_channels
+        wt = c.weight.detach().reshape(K, C).t().reshape(C, K, 1, 1).contiguous()
+        try:
+            return conv1x1.Conv1x1(-wt if negated else wt, None, 1)
+        except ValueError as e:
+            raise hip.PodError("backward: the input gradient of a 1x1 {} -> {} conv has no pod_conv1x1_split form ({})".format(C, K, e))
+    return conv_forms.derived(conv, "_pod_dx_t_neg" if negated else "_pod_dx_t", make)
+
+
 def _cols(x: torch.Tensor, h: int, w: int, relu: bool, out: torch.Tensor) -> None:
     hip.check(hip.load().pod_im2col3x3s2_cl(x.data_ptr(), out.data_ptr(), int(h), int(w), int(x.shape[1]), 1 if relu else 0, hip.current_stream()),
               "pod_im2col3x3s2_cl")
@@ -77,7 +94,9 @@ def _grad_cl(g, B: int, K: int, h: int, w: int, device) -> torch.Tensor:
 
 class _FpnTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fpn, feats, *params):
+    def forward(ctx, fpn, feats, n_maps, *tensors):
+        # tensors: the n_maps maps of `feats`, image-major (so that autograd sees them: they may carry the ResNet's grad_fn), then the parameters
+        params = tensors[n_maps:]
         saved, per_image = [], []
         for f in feats:
             keep = {}
@@ -130,17 +149,34 @@ class _FpnTrain(torch.autograd.Function):
         for i in range(3):
             dW, db = wgrad.conv1x1_wgrad(_stacked([s["c"][i] for s in saved]), dL[i])
             grads[fpn.lateral[i]] = (dW.view(K, -1, 1, 1), db)
+        # below the FPN, where the maps ask for it: every lateral's input gradient, and p6's on c5
+        d_maps = [None] * (3 * B)
+        if any(ctx.needs_input_grad[3:3 + 3 * B]):
+            for i in range(3):
+                (h, w), n = hw[i], hw[i][0] * hw[i][1]
+                dC = transposed_gemm(fpn.lateral[i])(dL[i], B * n, 1)
+                if i == 2:
+                    dcols, rec = _dcols_gemm(fpn.p6)(dP[3], B * n6, 1), amax.word(dev)
+                    for b in range(B):
+                        wgrad.col2im3x3s2_cl(dcols[b * n6:(b + 1) * n6], h, w, add=dC[b * n:(b + 1) * n], out=dC[b * n:(b + 1) * n], record=rec)
+                    amax.attach(dC, rec)
+                for b in range(B):
+                    d_maps[3 * b + i] = dC[b * n:(b + 1) * n]
+        tap = getattr(fpn, "train_tap", None)               # tests: a dict that receives what this pass hands below the FPN
+        if tap is not None:
+            tap["d_maps"] = list(d_maps)
         flat = []
         for conv in fpn_convs(fpn):
             flat += list(grads[conv])
         assert len(flat) == ctx.n_params
         ctx.state = None
-        return (None, None) + tuple(flat)
+        return (None, None, None) + tuple(d_maps) + tuple(flat)
 
 
 def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int]]]) -> List[torch.Tensor]:
     """feats: per image the [(c3, h, w), (c4, h, w), (c5, h, w)] of ResNet50.forward_cl, B images of one padded size.  Returns the per-level
-    (B, K, H, W) features; they carry a grad_fn that reaches every parameter of the FPN (and nothing below it)."""
+    (B, K, H, W) features; they carry a grad_fn that reaches every parameter of the FPN and, where the maps require grad (resnet_train's),
+    the maps; otherwise nothing below it."""
     feats = [list(f) for f in feats]
     if not feats or any(len(f) != 3 for f in feats):
         raise hip.PodError("fpn_forward_train: per image the three maps (c3, h, w), (c4, h, w), (c5, h, w)")
@@ -161,7 +197,8 @@ def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int
     for c in fpn_convs(fpn):
         params += [c.weight, c.bias]
     with torch.cuda.device(dev):
-        return list(_FpnTrain.apply(fpn, feats, *params))
+        maps = [t for f in feats for t, _, _ in f]
+        return list(_FpnTrain.apply(fpn, feats, len(maps), *maps, *params))
 
 
 def backbone_maps(model, image: torch.Tensor):

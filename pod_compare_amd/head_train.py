@@ -33,17 +33,20 @@ def transposed_weight(weight: torch.Tensor) -> torch.Tensor:
     return wt
 
 
-def input_grad_gemm(conv):
+def input_grad_gemm(conv, negated: bool = False):
     """The conv's input gradient as a GEMM: W' laid out (C, ty, tx, Kpad) and split once for pod_conv1x1_split (conv1x1.Conv3x3S2's form,
-    stride 1), cached by the weight's version as conv_forms.wino_of caches the forward filter."""
+    stride 1), cached by the weight's version as conv_forms.wino_of caches the forward filter.  negated: the same with -W' (every f16 term
+    and product the exact negative; resnet_train.centred uses the pair)."""
     def make(c):
         wt = transposed_weight(c.weight)
+        if negated:
+            wt = -wt
         try:
             return conv1x1.Conv1x1(wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1).contiguous(), None, 1)
         except ValueError as e:
             raise hip.PodError("head backward: the input gradient of a {} -> {} conv has no pod_conv1x1_split form ({})".format(
                 c.in_channels, c.out_channels, e))
-    return conv_forms.derived(conv, "_pod_dx_gemm", make)
+    return conv_forms.derived(conv, "_pod_dx_gemm_neg" if negated else "_pod_dx_gemm", make)
 
 
 def patch_matrix(dz: torch.Tensor, levels, B: int) -> torch.Tensor:

@@ -303,15 +303,19 @@ class Bottleneck(_TracksStorage):
         sc = None if self.shortcut is None else _plain_conv(self.shortcut)
         return _c1_ok(convs[0]) and _w3_ok(convs[1]) and _c1_ok(convs[2]) and (self.shortcut is None or _c1_ok(sc))
 
-    def forward_cl(self, x: torch.Tensor, h: int, w: int):
+    def forward_cl(self, x: torch.Tensor, h: int, w: int, keep: Optional[dict] = None):
         """The block on a channels-last buffer x (h * w, Cin): conv1 (1x1, stride) -> conv2 (3x3) -> conv3 (1x1) + shortcut + ReLU, three
-        (four) launches, every bias / ReLU / residual in the producing kernel's store.  Returns (y, h_out, w_out)."""
+        (four) launches, every bias / ReLU / residual in the producing kernel's store.  Returns (y, h_out, w_out).  keep: a dict that receives
+        what a backward pass needs of this forward (resnet_train.py): the input x, conv1's and conv2's outputs a and b, the output y."""
         c1, c2, c3 = c1_of(_plain_conv(self.conv1)), _plain_conv(self.conv2), c1_of(_plain_conv(self.conv3))
         h1, w1 = c1.out_hw(h, w)
         a = c1(x, h, w, relu=True)
         b = wino_cl(c2, a, h1, w1, relu=True)
         r = x if self.shortcut is None else c1_of(_plain_conv(self.shortcut))(x, h, w, relu=False)
-        return c3(b, h1, w1, relu=True, residual=r), h1, w1
+        y = c3(b, h1, w1, relu=True, residual=r)
+        if keep is not None:
+            keep.update(x=x, a=a, b=b, y=y, hw_in=(h, w), hw=(h1, w1))
+        return y, h1, w1
 
 
 class ResNet50(_TracksStorage):
@@ -346,9 +350,19 @@ class ResNet50(_TracksStorage):
         stem = _plain_conv(self.stem)
         return HIP_STEM and stem is not None and stem.bias is not None and conv1x1.Stem7x7.eligible(stem)
 
-    def forward_cl(self, x, frame=None):
+    def forward_cl(self, x, frame=None, stop_after_res2: bool = False, res2=None):
         """Channels-last from the stem on: returns [(c3, h, w), (c4, h, w), (c5, h, w)] with c* (h * w, C) buffers.  frame = (image (3, h, w)
-        uint8 / fp32 on the device, pixel mean, pixel std, padded (h, w)) instead of x: the stem kernel normalises and pads on load."""
+        uint8 / fp32 on the device, pixel mean, pixel std, padded (h, w)) instead of x: the stem kernel normalises and pads on load.
+        The two halves a trainer of res3 - res5 runs apart (resnet_train.py): stop_after_res2 returns res2's (t, h, w) -- the part
+        detectron2 freezes; res2 = that triple runs res3 - res5 on it instead of a frame."""
+        if res2 is not None:
+            t, h, w = res2
+            outs = []
+            for stage in (self.res3, self.res4, self.res5):
+                for block in stage:
+                    t, h, w = block.forward_cl(t, h, w)
+                outs.append((t, h, w))
+            return outs
         stem = _plain_conv(self.stem)
         if frame is not None:
             img, mean, std, padded = frame
@@ -367,6 +381,8 @@ class ResNet50(_TracksStorage):
             for block in stage:
                 t, h, w = block.forward_cl(t, h, w)
             outs.append((t, h, w))
+            if stop_after_res2:
+                return outs[0]
         return outs[1:]
 
 

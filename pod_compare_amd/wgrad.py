@@ -1,7 +1,8 @@
 """Host side of K22 (csrc/k22_conv3x3_wgrad.hip): the weight / bias gradients of a 3x3 / stride-1 / pad-1 convolution and the
 ReLU + dropout gate of the head's backward pass (probabilistic_retinanet.py:403-484 under train_net.py's loop) -- and of K23
-(csrc/k23_fpn_backward.hip): the weight gradient without taps and the two gathers of the FPN's backward pass.  GPU only: there is no
-CPU path."""
+(csrc/k23_fpn_backward.hip): the weight gradient without taps and the two gathers of the FPN's backward pass -- and of K24
+(csrc/k24_resnet_backward.hip): the 1x1 weight gradient at the backbone's widths and strides and the scatter that undoes a stride-2 pixel
+selection.  GPU only: there is no CPU path."""
 import ctypes
 from typing import Optional, Sequence, Tuple
 
@@ -125,3 +126,51 @@ def upsample2_sum_cl(d_child: torch.Tensor, h: int, w: int, add: torch.Tensor, o
         hip.check(hip.load().pod_upsample2_sum_cl(d_child.data_ptr(), int(h), int(w), add.data_ptr(), d_top.data_ptr(), C,
                                                   _record_of(d_top, record).data_ptr(), hip.current_stream()), "pod_upsample2_sum_cl")
     return d_top
+
+
+def conv1x1_wgrad_strided(x: torch.Tensor, dy: torch.Tensor, images: int, h: int, w: int, stride: int = 1, bias: bool = False):
+    """x (images * h * w, C), dy (images * ho * wo, K), channels-last, ho = (h - 1) // stride + 1: (dW (K, C), db (K,) or None) in fp32,
+    dW[k][c] = sum over (b, oy, ox) of dy[(b, oy, ox)][k] x[b h w + stride oy w + stride ox][c] -- the weight gradient of a 1x1 convolution of
+    stride 1 or 2 with up to 2048 output channels (the bottlenecks' conv1 / conv3 / shortcut).  The rows the stride selects are gathered in
+    the kernel.  The operands' abs-max records are their producers' (pod_compare_amd.amax), else computed now."""
+    _cl("pod_conv1x1_wgrad_strided", "x", x)
+    _cl("pod_conv1x1_wgrad_strided", "dy", dy)
+    images, h, w, stride = int(images), int(h), int(w), int(stride)
+    C, K = int(x.shape[1]), int(dy.shape[1])
+    lib = hip.load()
+    n = int(lib.pod_conv1x1_wgrad_strided_partials(images, h, w, stride, C, K))
+    if n <= 0:
+        raise hip.PodError("pod_conv1x1_wgrad_strided: images >= 1, stride 1 or 2, C % 16 == 0, C <= 18432, K % 64 == 0 and K <= 2048 required, got "
+                           "images={} {} x {} stride={} C={} K={}".format(images, h, w, stride, C, K))
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if int(x.shape[0]) != images * h * w or int(dy.shape[0]) != images * ho * wo or dy.device != x.device:
+        raise hip.PodError("pod_conv1x1_wgrad_strided: {} images of {} x {} at stride {} pair {} rows of x with {} of dy, got {} on {} and {} on {}".format(
+            images, h, w, stride, images * h * w, images * ho * wo, x.shape[0], x.device, dy.shape[0], dy.device))
+    partials = torch.empty(n, dtype=torch.float32, device=x.device)
+    dW = torch.empty((K, C), dtype=torch.float32, device=x.device)
+    db = torch.empty((K,), dtype=torch.float32, device=x.device) if bias else None
+    with torch.cuda.device(x.device):
+        hip.check(lib.pod_conv1x1_wgrad_strided(x.data_ptr(), dy.data_ptr(), images, h, w, stride, C, K, amax.of(x).data_ptr(), amax.of(dy).data_ptr(),
+                                                dW.data_ptr(), hip.ptr(db), partials.data_ptr(), hip.current_stream()), "pod_conv1x1_wgrad_strided")
+    return dW, db
+
+
+def subsample2_scatter_cl(d_small: torch.Tensor, h: int, w: int, gate: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The input gradient of a stride-2 pixel selection for one (h, w) image: d_small (ho * wo, C) -> dx (h * w, C) = (gate > 0) * (d_small on
+    the pixels with even coordinates, zero elsewhere, + add).  out may be `add`."""
+    _cl("pod_subsample2_scatter_cl", "d_small", d_small)
+    h, w = int(h), int(w)
+    ho, wo, C = (h - 1) // 2 + 1, (w - 1) // 2 + 1, int(d_small.shape[1])
+    if h < 1 or w < 1 or C % 4 or int(d_small.shape[0]) != ho * wo:
+        raise hip.PodError("pod_subsample2_scatter_cl: a {} x {} map has ({}, C) selected rows with C % 4 == 0, got {}".format(h, w, ho * wo, tuple(d_small.shape)))
+    dx = torch.empty((h * w, C), dtype=torch.float32, device=d_small.device) if out is None else out
+    for what, t in (("gate", gate), ("add", add), ("dx", dx)):
+        if t is not None:
+            _cl("pod_subsample2_scatter_cl", what, t)
+            if tuple(t.shape) != (h * w, C) or t.device != d_small.device:
+                raise hip.PodError("pod_subsample2_scatter_cl: {} must be ({}, {}) on {}, got {} on {}".format(what, h * w, C, d_small.device, tuple(t.shape), t.device))
+    with torch.cuda.device(d_small.device):
+        hip.check(hip.load().pod_subsample2_scatter_cl(d_small.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), h, w, C,
+                                                       _record_of(dx, record).data_ptr(), hip.current_stream()), "pod_subsample2_scatter_cl")
+    return dx
