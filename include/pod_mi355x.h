@@ -802,6 +802,37 @@ int pod_conv1x1_wgrad_strided(const float* x, const float* dy, int32_t images, i
 int pod_subsample2_scatter_cl(const float* d_small, const float* gate, const float* add, float* dx, int32_t H, int32_t W, int32_t C, float* dx_amax,
                               pod_stream_t stream);
 
+/* ---- K25  the optimiser's step, every trained tensor in one launch (csrc/k25_sgd_step.hip) ------------------------------------
+ * Serves: detectron2's build_optimizer / torch.optim.SGD (momentum, weight decay, one parameter group) under train_net.py's loop, together
+ * with the two passes a FrozenBN-folded filter needs around it (W.grad = s dW' before, W' = W s after).  Two new symbols and one new
+ * structure under POD_ABI_VERSION 18, as for K20 - K24: no entry or structure that existed changed, so the number stands.
+ *
+ * For every element i of every tensor of the table, in fp32, each operation rounded on its own:
+ *     a  = scale ? scale[i / per_channel] * grad[i] : grad[i]
+ *     g' = a + weight_decay * w[i];   m' = momentum * m[i] + g';   w' = w[i] - lr * m'
+ *     m[i] = m';  w[i] = w';  if (folded) folded[i] = w' * scale[i / per_channel]
+ * (zeroed momentum before the first step gives torch's first step, buf = g').  A tensor whose grad is NULL is skipped entirely -- no weight
+ * decay, no momentum decay -- as torch skips a parameter without .grad.  w, grad, momentum, folded: dev fp32, n elements, 16-byte aligned,
+ * no two overlapping; scale: dev fp32, n / per_channel floats (FrozenBN's s per OUTPUT channel), 16-byte aligned.
+ * pod_sgd_chunk_map: the work list of a table -- per tensor ceil(n / POD_SGD_CHUNK) pairs (tensor, chunk of that tensor), int32, in table
+ *   order -- written to HOST `map` if it is not NULL and holds `capacity` >= the result's pairs.  Returns the number of pairs, -1 for a
+ *   table pod_sgd_step would refuse.  It depends on the n alone: built once per parameter set and kept on the device.
+ * pod_sgd_step: `tensors` HOST (n_tensors descriptors; pinned memory makes the copy asynchronous), `tensors_dev` dev room for as many,
+ *   `chunk_map` dev (n_chunks, 2) from pod_sgd_chunk_map of the same n.  Enqueues ONE host-to-device copy of the table and ONE launch on
+ *   `stream`; no synchronisation, no read-back.  The caller leaves `tensors` unchanged until the copy has run (an event recorded after
+ *   the call).  POD_E_INVALID before anything is enqueued: tensors NULL with n_tensors > 0, n_tensors < 0, a descriptor with w or momentum
+ *   NULL, n < 0, a misaligned pointer, scale without per_channel > 0 or with n % per_channel != 0, folded without scale, folded == w,
+ *   w == momentum, n_chunks other than the table's, lr / momentum / weight_decay not finite, momentum outside [0, 1), weight_decay < 0,
+ *   tensors_dev or chunk_map NULL with n_chunks > 0.  n_tensors == 0, or every n == 0: POD_OK, nothing enqueued. */
+#define POD_SGD_CHUNK 4096
+typedef struct PodSgdTensor {
+    float* w;  const float* grad;  float* momentum;  float* folded;  const float* scale;
+    int64_t n;  int64_t per_channel;
+} PodSgdTensor;
+int64_t pod_sgd_chunk_map(const PodSgdTensor* tensors, int32_t n_tensors, int32_t* map, int64_t capacity);
+int pod_sgd_step(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks,
+                 float lr, float momentum, float weight_decay, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

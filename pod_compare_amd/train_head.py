@@ -2,6 +2,7 @@
 
     python -m pod_compare_amd.train_head --coco-json <gt.json> --image-root <dir> --data-dir <checkpoints root> \
         --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn | --train-backbone]
+        [--fused-step] [--random-flip] [--resume]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
 shape together; a shape's frames wait until a batch of them is complete), the frozen backbone + FPN per image under no_grad through the
@@ -23,14 +24,26 @@ laterals and p6.  The device model computes with FrozenBN folded, W' = W s; the 
 momentum and weight decay act on what the reference's act on, and conv.weight is refolded from W after every step.  A checkpoint carries
 W.  Only FREEZE_AT = 2 is supported.
 
-Still NOT the reference's full trainer: no random flip (the frames are the loader's, resized only), no optimiser state in checkpoints
-(a resumed run restarts momentum), one GPU.  The loss line is the only host read-back, on log steps only.
+--fused-step: the optimiser's step is ONE launch of this project's own (K25, pod_compare_amd/sgd_step.py) in place of collect_grads + torch's
+SGD + refold: the trainer owns the momentum buffers, the kernel scales a folded filter's gradient by s, steps the master and rewrites the
+folded filter, and the written tensors' versions are bumped so that the derived filters are rebuilt.  Without the flag torch.optim.SGD steps.
+
+--random-flip: detectron2's RandomFlip(horizontal), probability 0.5.  The draw is made in the main loop in data order from a generator
+seeded with --random-seed; the frame is flipped on the device and its boxes follow HFlipTransform (`hflip_boxes`).
+
+Every checkpoint also carries the trainer's state (`pod_trainer`: iteration, the loss state's step / draw count / normaliser, the momentum
+buffers under detectron2's names, the sampler's position, the frames waiting in the shape buckets, the flip generator).  --resume
+(detectron2's flag): OUTPUT_DIR/last_checkpoint's weights AND that state are restored, and the run continues where it stopped -- schedule,
+annealing, momentum and data order.  A checkpoint without the state, or from a run that trained other parts, is refused.  Without --resume
+the weights of last_checkpoint load as before and the run starts at iteration 0.
+
+Still NOT the reference's full trainer: one GPU.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies).
 """
 import argparse
 import bisect
 import json
 import os
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -43,6 +56,7 @@ from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import head_convs
 from .resnet_train import FoldedMasters, res2_maps, resnet_forward_train, trainable_convs, unfolded_pairs
 from .probabilistic_inference import build_model
+from .sgd_step import FusedSGD, SgdEntry
 
 
 def warmup_multistep_lr(iteration: int, base_lr: float, steps: Sequence[int], gamma: float, warmup_iters: int, warmup_factor: float) -> float:
@@ -55,14 +69,24 @@ def warmup_multistep_lr(iteration: int, base_lr: float, steps: Sequence[int], ga
     return base_lr * w * gamma ** bisect.bisect_right(list(steps), iteration)
 
 
+def hflip_boxes(boxes: torch.Tensor, width) -> torch.Tensor:
+    """detectron2's HFlipTransform.apply_box on (N, 4) XYXY boxes of an image `width` pixels wide (the RESIZED width, the boxes' own
+    scale): x1' = W - x2, x2' = W - x1, y unchanged -- x1' < x2' wherever x1 < x2."""
+    out = boxes.clone()
+    out[:, 0] = width - boxes[:, 2]
+    out[:, 2] = width - boxes[:, 0]
+    return out
+
+
 class HeadTrainer:
     """The step function of train_head: optimiser, schedule and the iteration count around model.head.forward_train + model.losses."""
 
     def __init__(self, model, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, steps: Sequence[int] = (60000, 80000),
                  gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0, train_fpn: bool = False,
-                 train_backbone: bool = False, shadow=None):
+                 train_backbone: bool = False, shadow=None, fused_step: bool = False):
         """train_backbone: res3 - res5 train too (and the FPN: it lies between them and the head); `shadow`, the same model unfolded, gives
-        the master weights and FrozenBN scales (resnet_train.FoldedMasters)."""
+        the master weights and FrozenBN scales (resnet_train.FoldedMasters).  fused_step: the optimiser's step is pod_sgd_step (K25) on
+        momentum buffers the trainer owns (`self.fused`), not torch's SGD; `self.opt` is the torch.optim.SGD either way (unused when fused)."""
         self.model, self.train_backbone = model, bool(train_backbone)
         self.train_fpn = bool(train_fpn) or self.train_backbone
         self.params = [p for c in head_convs(model.head) for p in (c.weight, c.bias)]
@@ -82,6 +106,57 @@ class HeadTrainer:
                              warmup_factor=float(warmup_factor))
         self.opt = torch.optim.SGD(self.params, lr=float(base_lr), momentum=float(momentum), weight_decay=float(weight_decay))
         self.iteration = int(iteration)
+        self.momentum_mu = float(momentum)
+        self.fused = None
+        if fused_step:
+            n_plain = len(self.params) - (len(self.masters.params) if self.masters is not None else 0)
+            entries = [SgdEntry(p) for p in self.params[:n_plain]]
+            if self.masters is not None:
+                entries += [SgdEntry(p, grad_of=c.weight, scale=s, folded=c.weight) for c, p, s in zip(self.masters.convs, self.masters.params, self.masters.scales)]
+            self.fused = FusedSGD(entries, momentum=float(momentum), weight_decay=float(weight_decay))
+        self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
+
+    @property
+    def lr(self) -> float:
+        """The learning rate of the last step taken (before the first: the one the first will take), whichever optimiser steps."""
+        return self._lr
+
+    def trained(self) -> List[str]:
+        return ["head"] + (["fpn"] if self.train_fpn else []) + (["backbone"] if self.train_backbone else [])
+
+    def param_names(self) -> List[str]:
+        """detectron2's name of the weight each of self.params is (a master weight: of the conv it is the unfolded filter of)."""
+        local = {id(p): k for k, p in self.model.named_parameters()}
+        to_d2 = {v: k for k, v in checkpoint.detectron2_to_local_keys(self.model, 3 if self.model.use_dropout else 2).items()}
+        owners = list(self.params)
+        if self.masters is not None:
+            owners[len(owners) - len(self.masters.params):] = [c.weight for c in self.masters.convs]
+        return [to_d2[local[id(p)]] for p in owners]
+
+    def momentum_state(self) -> Dict[str, torch.Tensor]:
+        """The momentum buffers on the CPU under param_names(), from whichever optimiser steps; zeros where torch's has not stepped yet
+        (its first step, buf = g', is what a zero buffer gives)."""
+        out = {}
+        for i, (name, p) in enumerate(zip(self.param_names(), self.params)):
+            buf = self.fused.buffers[i] if self.fused is not None else self.opt.state.get(p, {}).get("momentum_buffer")
+            out[name] = torch.zeros(p.shape, dtype=p.dtype) if buf is None else buf.detach().cpu().clone()
+        return out
+
+    def load_momentum_state(self, state: Dict[str, torch.Tensor]) -> None:
+        """Raises ValueError unless `state` holds exactly param_names(), each of its parameter's shape."""
+        names = self.param_names()
+        if sorted(names) != sorted(state):
+            odd = sorted(set(names) ^ set(state))
+            raise ValueError("the momentum buffers' names do not match the trained parameters (e.g. {})".format(odd[:3]))
+        for i, (name, p) in enumerate(zip(names, self.params)):
+            if tuple(state[name].shape) != tuple(p.shape):
+                raise ValueError("momentum of {}: shape {} in the file, {} in the model".format(name, tuple(state[name].shape), tuple(p.shape)))
+        with torch.no_grad():
+            for i, (name, p) in enumerate(zip(names, self.params)):
+                if self.fused is not None:
+                    self.fused.buffers[i].copy_(state[name])
+                else:
+                    self.opt.state[p]["momentum_buffer"] = state[name].to(device=p.device, dtype=p.dtype).clone()
 
     def features(self, images: Sequence[torch.Tensor]):
         """The frozen backbone + FPN per image -> (per-level (B, 256, H, W) features, padded (h, w)).  train_fpn: only the backbone is
@@ -112,27 +187,39 @@ class HeadTrainer:
 
     def step(self, feats, padded, image_hw, gt_boxes, gt_classes, eps=None, normalizer=None) -> Dict[str, torch.Tensor]:
         """One iteration on the stacked features of a batch; returns the losses (device scalars)."""
-        lr = warmup_multistep_lr(self.iteration, **self.schedule)
+        lr = self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
         for g in self.opt.param_groups:
             g["lr"] = lr
         out = self.model.head.forward_train(feats, self.model.anchors_for(tuple(padded)), image_hw)
         res = self.model.losses(out, gt_boxes, gt_classes, eps=eps, normalizer=normalizer)
         self.opt.zero_grad(set_to_none=True)
         (res["loss_cls"] + res["loss_box_reg"]).backward()
+        self.optimizer_step(lr)
+        self.model.loss_state.current_step += 1   # PR:146
+        self.iteration += 1
+        return res
+
+    def optimizer_step(self, lr: float) -> None:
+        """From the gradients backward() left to the stepped weights and refolded filters."""
+        if self.fused is not None:
+            self.fused.step(lr)                   # K25: s dW', the step on W and W' = W s in one launch; bumps the written tensors' versions
+            if self.masters is not None:
+                for c in self.masters.convs:
+                    c.weight.grad = None          # (as collect_grads leaves them)
+            return
         if self.masters is not None:
             self.masters.collect_grads()          # W.grad = s dW': the optimiser steps the unfolded weights
         self.opt.step()                           # bumps the weights' versions: the filters and HIP graphs derived from them are rebuilt
         if self.masters is not None:
             self.masters.refold()                 # conv.weight = W s, in place
-        self.model.loss_state.current_step += 1   # PR:146
-        self.iteration += 1
-        return res
 
 
-def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, train_fpn: bool = False, train_backbone: bool = False, masters=None) -> str:
+def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, train_fpn: bool = False, train_backbone: bool = False, masters=None,
+                    trainer=None, sampler=None, random_seed: int = 0) -> str:
     """`shadow`: the same model unfolded (conv + FrozenBN pairs) on the CPU -- the form detectron2's names describe; it receives the
     trained head (train_fpn: and the trained FPN, which has no norm to unfold; train_backbone: and the master weights of res3 - res5,
-    `masters` = the trainer's FoldedMasters) and is written as <out_dir>/<name>.pth, named in <out_dir>/last_checkpoint."""
+    `masters` = the trainer's FoldedMasters) and is written as <out_dir>/<name>.pth, named in <out_dir>/last_checkpoint.  trainer: the
+    file also carries `pod_trainer`, the state --resume continues from (trainer_state; `sampler`: the FrameSampler of the run)."""
     os.makedirs(out_dir, exist_ok=True)
     pairs = list(zip(head_convs(shadow.head), head_convs(model.head)))
     if train_fpn or train_backbone:
@@ -146,10 +233,88 @@ def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, trai
             dst.weight.copy_(src.weight.detach().cpu())
             dst.bias.copy_(src.bias.detach().cpu())
     path = os.path.join(out_dir, name + ".pth")
-    torch.save({"model": checkpoint.to_detectron2_state_dict(shadow, with_dropout_entries=model.use_dropout), "iteration": int(iteration)}, path)
+    data = {"model": checkpoint.to_detectron2_state_dict(shadow, with_dropout_entries=model.use_dropout), "iteration": int(iteration)}
+    if trainer is not None:
+        data[TRAINER_KEY] = trainer_state(trainer, sampler, random_seed)
+    torch.save(data, path)
     with open(os.path.join(out_dir, "last_checkpoint"), "w") as f:
         f.write(name + ".pth")
     return path
+
+
+TRAINER_KEY = "pod_trainer"
+
+
+class FrameSampler:
+    """The data order of train_head as state: the position within the pass over the data set, the frames waiting in the shape buckets, and
+    the generator of the flip draws (one draw per frame, in data order, only with random_flip)."""
+
+    def __init__(self, batch: int, random_flip: bool = False, seed: int = 0):
+        self.batch, self.random_flip = max(1, int(batch)), bool(random_flip)
+        self.generator = torch.Generator().manual_seed(int(seed))
+        self.buckets: Dict[tuple, list] = {}
+        self.next_index, self.arrivals = 0, 0
+
+    def draw_flip(self) -> bool:
+        return bool(torch.rand((), generator=self.generator) < 0.5) if self.random_flip else False
+
+    def add(self, index: int, flipped: bool, image, boxes, classes):
+        """Files a frame under its shape; returns the (images, boxes, classes) of a batch once `batch` frames of that shape wait, else None."""
+        bucket = self.buckets.setdefault(tuple(image.shape), [])
+        bucket.append((self.arrivals, int(index), bool(flipped), image, boxes, classes))
+        self.arrivals += 1
+        if len(bucket) < self.batch:
+            return None
+        _, _, _, images, gb, gc = zip(*bucket)
+        bucket.clear()
+        return images, list(gb), list(gc)
+
+    def state(self) -> dict:
+        pending = sorted(e[:3] for b in self.buckets.values() for e in b)
+        return {"next_index": int(self.next_index), "pending": [[int(i), int(f)] for _, i, f in pending], "flip_generator": self.generator.get_state().clone()}
+
+    def load_state(self, state: dict) -> List[list]:
+        """Restores position and generator; returns the pending (index, flipped) pairs, which the caller re-reads and files in order."""
+        self.next_index = int(state["next_index"])
+        self.generator.set_state(state["flip_generator"])
+        return [[int(i), int(f)] for i, f in state["pending"]]
+
+
+def trainer_state(trainer: HeadTrainer, sampler: Optional[FrameSampler] = None, random_seed: int = 0) -> dict:
+    """What a run needs beside the weights to continue where it stopped -- tensors, numbers, strings, lists and dicts only (the restricted
+    unpickler reads it)."""
+    ls = trainer.model.loss_state
+    norm = ls.loss_normalizer
+    return {"iteration": int(trainer.iteration),
+            "loss_state": {"current_step": int(ls.current_step), "draws": int(ls.draws),
+                           "loss_normalizer": (norm.detach() if torch.is_tensor(norm) else torch.tensor(float(norm))).to("cpu", torch.float64).reshape(())},
+            "momentum": trainer.momentum_state(), "momentum_mu": float(trainer.momentum_mu), "trained": trainer.trained(),
+            "sampler": (sampler if sampler is not None else FrameSampler(1, seed=random_seed)).state(), "random_seed": int(random_seed)}
+
+
+def read_trainer_state(path: str) -> dict:
+    """The `pod_trainer` entry of a checkpoint file; SystemExit naming the file if it has none."""
+    data = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(data, dict) or not isinstance(data.get(TRAINER_KEY), dict):
+        raise SystemExit("--resume: {} holds no `{}` entry (weights only: written without the trainer's state, or not by train_head); "
+                         "run without --resume to fine-tune from its weights at iteration 0".format(path, TRAINER_KEY))
+    return data[TRAINER_KEY]
+
+
+def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
+    """Iteration, loss state and momentum from a checkpoint's `pod_trainer`; SystemExit naming the file where it does not fit this run."""
+    if list(state.get("trained", [])) != trainer.trained():
+        raise SystemExit("--resume: {} comes from a run that trained {}, this one trains {}: give the same --train-fpn / --train-backbone".format(
+            path, " + ".join(state.get("trained", [])) or "nothing", " + ".join(trainer.trained())))
+    try:
+        trainer.load_momentum_state(state["momentum"])
+    except ValueError as e:
+        raise SystemExit("--resume: {}: {}".format(path, e))
+    trainer.iteration = int(state["iteration"])
+    trainer._lr = warmup_multistep_lr(trainer.iteration, **trainer.schedule)
+    ls = trainer.model.loss_state
+    ls.current_step, ls.draws = int(state["loss_state"]["current_step"]), int(state["loss_state"]["draws"])
+    ls.loss_normalizer = float(state["loss_state"]["loss_normalizer"])
 
 
 def main(argv=None):
@@ -175,6 +340,12 @@ def main(argv=None):
     ap.add_argument("--train-fpn", action="store_true", help="train the FPN's eight convolutions together with the head (the ResNet stays frozen)")
     ap.add_argument("--train-backbone", action="store_true", help="train res3 - res5 of the ResNet too, as detectron2 does at MODEL.BACKBONE.FREEZE_AT = 2 "
                                                                   "(implies --train-fpn; the stem and res2 stay frozen)")
+    ap.add_argument("--fused-step", action="store_true", help="the optimiser's step as one launch of the project's own kernel (K25) in place of "
+                                                              "torch.optim.SGD and the refold passes around it")
+    ap.add_argument("--random-flip", action="store_true", help="detectron2's RandomFlip: every frame is mirrored with probability 0.5 (drawn in "
+                                                               "data order from --random-seed), its boxes with it")
+    ap.add_argument("--resume", action="store_true", help="continue the run OUTPUT_DIR/last_checkpoint stopped in: its weights and its trainer state "
+                                                          "(iteration, loss state, momentum, data position); refused if the file carries none")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     cfg = setup_config(args.config_file, "", args.random_seed, data_dir=args.data_dir)
@@ -192,6 +363,13 @@ def main(argv=None):
         raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: the stem and res2 are frozen and res3 - res5 train (detectron2's "
                          "default, FREEZE_AT = 2), or with neither --train-backbone nor --train-fpn only the head does".format(freeze_at))
     train_fpn = args.train_fpn or args.train_backbone
+    # --resume: the file last_checkpoint names, if there is one (none: the run starts as without the flag, as detectron2's resume_or_load)
+    resume_from = checkpoint.resolve_checkpoint(cfg.OUTPUT_DIR, "") if args.resume else ""
+    resume_state = read_trainer_state(resume_from) if resume_from else None
+    trains = ["head"] + (["fpn"] if train_fpn else []) + (["backbone"] if args.train_backbone else [])
+    if resume_state is not None and list(resume_state.get("trained", [])) != trains:          # (before a model is built; restore_trainer checks the rest)
+        raise SystemExit("--resume: {} comes from a run that trained {}, this one trains {}: give the same --train-fpn / --train-backbone".format(
+            resume_from, " + ".join(resume_state.get("trained", [])) or "nothing", " + ".join(trains)))
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     with open(args.coco_json, "r") as f:
@@ -204,7 +382,7 @@ def main(argv=None):
     cat_map = evaluation_category_map(args.train_dataset, args.test_dataset)
     dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     # the model twice from one seed: on the device with FrozenBN folded (what runs), and unfolded on the CPU (what a checkpoint describes)
-    load = not args.random_init
+    load = not args.random_init or bool(resume_from)       # (a resumed run's weights are the checkpoint's, whatever the first run started from)
     torch.manual_seed(args.random_seed)
     model = build_model(cfg, load_weights=load)
     cpu_cfg = cfg.clone()
@@ -219,37 +397,55 @@ def main(argv=None):
                                                   seed=args.random_seed)
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
                           warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=train_fpn, train_backbone=args.train_backbone,
-                          shadow=shadow if args.train_backbone else None)
-    saved = dict(train_fpn=train_fpn, train_backbone=args.train_backbone, masters=trainer.masters)
+                          shadow=shadow if args.train_backbone else None, fused_step=args.fused_step)
     max_iter = args.max_iter if args.max_iter >= 0 else int(s.MAX_ITER)
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
-    buckets: Dict[tuple, list] = {}
+    sampler = FrameSampler(batch, random_flip=args.random_flip, seed=args.random_seed)
+    saved = dict(train_fpn=train_fpn, train_backbone=args.train_backbone, masters=trainer.masters, trainer=trainer, sampler=sampler,
+                 random_seed=args.random_seed)
+
+    def frame(d: dict, flipped: bool):
+        """One loader entry on the device with its ground truth in network-input pixels, mirrored if the draw said so."""
+        image = d["image"].to(dev, non_blocking=True)
+        sy, sx = image.shape[1] / float(d["height"]), image.shape[2] / float(d["width"])
+        boxes, classes = image_ground_truth(by_image.get(d["image_id"], []), cat_map, sx, sy)
+        if flipped:
+            image, boxes = image.flip(-1), hflip_boxes(boxes, float(image.shape[2]))
+        return image, boxes, classes
+
+    if resume_state is not None:
+        restore_trainer(trainer, resume_state, resume_from)
+        for index, flipped in sampler.load_state(resume_state["sampler"]):       # the frames that waited in the buckets, in arrival order
+            if not 0 <= index < len(dataset) or sampler.add(index, bool(flipped), *frame(dataset[index], bool(flipped))) is not None:
+                raise SystemExit("--resume: {}: its waiting frames do not fit this data set and SOLVER.IMS_PER_BATCH".format(resume_from))
+        if not 0 <= sampler.next_index < max(1, len(dataset)):
+            raise SystemExit("--resume: {}: stopped at frame {} of a data set of {}".format(resume_from, sampler.next_index, len(dataset)))
+        print("resumed %s at iteration %d" % (resume_from, trainer.iteration), flush=True)
     written, last_line, stalled = [], None, 0
     while trainer.iteration < max_iter:
         progressed = False
-        for _, d in Prefetched(dataset, range(len(dataset)), workers=workers):
-            image = d["image"].to(dev, non_blocking=True)
-            sy, sx = image.shape[1] / float(d["height"]), image.shape[2] / float(d["width"])
-            boxes, classes = image_ground_truth(by_image.get(d["image_id"], []), cat_map, sx, sy)
-            bucket = buckets.setdefault(tuple(image.shape), [])
-            bucket.append((image, boxes, classes))
-            if len(bucket) < batch:
+        for index, d in Prefetched(dataset, range(sampler.next_index, len(dataset)), workers=workers):
+            flipped = sampler.draw_flip()
+            ready = sampler.add(index, flipped, *frame(d, flipped))
+            sampler.next_index = (index + 1) % len(dataset)
+            if ready is None:
                 continue
-            images, gb, gc = zip(*bucket)
-            bucket.clear()
+            images, gb, gc = ready
             feats, padded = trainer.features(images)
-            res = trainer.step(feats, padded, tuple(images[0].shape[-2:]), list(gb), list(gc))
+            res = trainer.step(feats, padded, tuple(images[0].shape[-2:]), gb, gc)
             progressed = True
             it = trainer.iteration
             if args.log_period > 0 and (it % args.log_period == 0 or it == max_iter):
                 last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(res["loss_cls"]), float(res["loss_box_reg"]),
-                                                                                  trainer.opt.param_groups[0]["lr"])
+                                                                                  trainer.lr)
                 print(last_line, flush=True)
             if period > 0 and it % period == 0 and it < max_iter:
                 written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_%07d" % (it - 1), it, **saved))
             if it >= max_iter:
                 break
+        else:
+            sampler.next_index = 0
         stalled = 0 if progressed else stalled + 1      # (an incomplete batch carries over into the next pass over the data set)
         if stalled >= batch:
             raise SystemExit("no batch of {} frames of one resized shape can be formed from {} frames".format(batch, len(dataset)))
