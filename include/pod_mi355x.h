@@ -833,6 +833,27 @@ int64_t pod_sgd_chunk_map(const PodSgdTensor* tensors, int32_t n_tensors, int32_
 int pod_sgd_step(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks,
                  float lr, float momentum, float weight_decay, pod_stream_t stream);
 
+/* ---- K26  the gradient bucket of data-parallel training, every gradient packed in one launch (csrc/k26_grad_bucket.hip) ----------
+ * Serves: the gradient averaging of detectron2's launch + DistributedDataParallel under train_net.py -- one flat fp32 buffer that ONE
+ * all-reduce averages and pod_sgd_step then steps from.  Two new symbols under POD_ABI_VERSION 18, no new structure: the table is K25's
+ * PodSgdTensor (the pack reads `grad` and `n` alone; the rest only has to make a table pod_sgd_chunk_map accepts), cut by K25's chunk map.
+ * pod_grad_bucket_layout: tensor t starts at the sum of the previous tensors' n, each rounded up to a multiple of 4 floats (every start is
+ *   16-byte aligned), written to HOST `offsets` (n_tensors) if it is not NULL.  Returns the total number of floats, a multiple of 4; -1 for
+ *   a table pod_sgd_chunk_map would refuse.  It depends on the n alone.
+ * pod_grad_pack: bucket[offsets[t] + i] = scale * grad_t[i], fp32, one rounding.  `tensors` HOST (pinned memory makes the copy
+ *   asynchronous), `tensors_dev` dev room for as many, `chunk_map` dev (n_chunks, 2) from pod_sgd_chunk_map and `offsets_dev` dev int64
+ *   from pod_grad_bucket_layout of the same n, `bucket` dev, bucket_floats floats, 16-byte aligned.  Enqueues ONE host-to-device copy of
+ *   the table and ONE launch on `stream`; no synchronisation, no read-back, no atomics: two launches give the same bits.  The caller leaves
+ *   `tensors` unchanged until the copy has run, as for pod_sgd_step.  The padding floats between tensors are never written (the owner zeroes
+ *   the bucket once).  POD_E_INVALID before anything is enqueued: a table pod_sgd_chunk_map refuses (a misaligned pointer among them), a
+ *   tensor with n > 0 whose grad is NULL (every trained tensor has a gradient on every rank: not K25's skip), bucket overlapping a
+ *   gradient, bucket_floats other than the layout's total, n_chunks other than the table's, scale not finite or <= 0, and with
+ *   n_chunks > 0: bucket, tensors_dev, chunk_map or offsets_dev NULL, bucket misaligned.  n_tensors == 0, or every n == 0: POD_OK,
+ *   nothing enqueued. */
+int64_t pod_grad_bucket_layout(const PodSgdTensor* tensors, int32_t n_tensors, int64_t* offsets);
+int pod_grad_pack(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks,
+                  const int64_t* offsets_dev, float* bucket, int64_t bucket_floats, float scale, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -45,11 +45,12 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_conv3x3_wgrad_partials", "pod_conv3x3_wgrad", "pod_relu_dropout_backward",
            "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad", "pod_col2im3x3s2_cl", "pod_upsample2_sum_cl",
            "pod_conv1x1_wgrad_strided_partials", "pod_conv1x1_wgrad_strided", "pod_subsample2_scatter_cl",
-           "pod_sgd_chunk_map", "pod_sgd_step")
+           "pod_sgd_chunk_map", "pod_sgd_step", "pod_grad_bucket_layout", "pod_grad_pack")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
-                 "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map")
+                 "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
+                 "pod_grad_bucket_layout")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws and of the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -249,6 +250,9 @@ def load() -> ctypes.CDLL:
     lib.pod_sgd_chunk_map.argtypes = [POINTER(PodSgdTensor), c_int32, P, c_int64]
     lib.pod_sgd_chunk_map.restype = c_int64
     lib.pod_sgd_step.argtypes = [POINTER(PodSgdTensor), P, c_int32, P, c_int64, c_float, c_float, c_float, P]
+    lib.pod_grad_bucket_layout.argtypes = [POINTER(PodSgdTensor), c_int32, P]
+    lib.pod_grad_bucket_layout.restype = c_int64
+    lib.pod_grad_pack.argtypes = [POINTER(PodSgdTensor), P, c_int32, P, c_int64, P, P, c_int64, c_float, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -9,6 +9,8 @@ from the stepped master on the way out.  `FusedSGD` owns the momentum buffers an
     * the chunk map (pod_sgd_chunk_map) depends on the sizes alone: built once, kept on the device.
     * the kernel writes through raw pointers, so every tensor it may have written gets its version counter bumped
       (torch._C._increment_version, no launch): the derived filters, abs-max records and graph fingerprints key on Tensor._version.
+    * grads_from (data-parallel training, data_parallel.GradBucket): the gradients are read from the bucket's slices, where the all-reduce
+      left the rank mean; those pointers never change, so the table is filled once and the refresh is the pack's.
 GPU only: pod_sgd_step refusing the table raises hip.PodError; there is no fallback to torch's optimiser."""
 import ctypes
 from typing import List, Optional, Sequence
@@ -32,8 +34,13 @@ def bump_versions(tensors: Sequence[torch.Tensor]) -> None:
 
 
 class FusedSGD:
-    def __init__(self, entries: Sequence[SgdEntry], momentum: float, weight_decay: float):
-        self.entries = list(entries)
+    def __init__(self, entries: Sequence[SgdEntry], momentum: float, weight_decay: float, grads_from=None):
+        """grads_from: a data_parallel.GradBucket over the same entries.  The step then reads every gradient from its slice of the bucket
+        (the averaged gradient the collective left there): the table's grad pointers are set once, here, and the per-step refresh and the
+        checks of .grad are the pack's."""
+        self.entries, self.grads_from = list(entries), grads_from
+        if grads_from is not None and [e.w.numel() for e in grads_from.entries] != [e.w.numel() for e in self.entries]:
+            raise hip.PodError("FusedSGD: the gradient bucket was laid out for other tensors than the ones this optimiser steps")
         self.mu, self.weight_decay = float(momentum), float(weight_decay)
         n = len(self.entries)
         dev = self.entries[0].w.device if n else torch.device("cpu")
@@ -57,8 +64,8 @@ class FusedSGD:
         for _ in range(2):
             host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
             table = (hip.PodSgdTensor * n).from_address(host.data_ptr())
-            for d, e, m in zip(table, self.entries, self.buffers):
-                d.w, d.grad, d.momentum, d.n = e.w.data_ptr(), None, m.data_ptr(), e.w.numel()
+            for i, (d, e, m) in enumerate(zip(table, self.entries, self.buffers)):
+                d.w, d.grad, d.momentum, d.n = e.w.data_ptr(), None if grads_from is None else grads_from.slice_ptr(i), m.data_ptr(), e.w.numel()
                 d.folded = None if e.folded is None else e.folded.data_ptr()
                 d.scale = None if e.scale is None else e.scale.data_ptr()
                 d.per_channel = e.w.numel() // e.w.shape[0] if e.scale is not None and e.w.shape[0] else 0
@@ -74,14 +81,15 @@ class FusedSGD:
         self._table_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
 
     def step(self, lr: float) -> None:
-        """One launch over every entry whose gradient exists; the entries' .grad stay (the caller clears them)."""
+        """One launch over every entry whose gradient exists (with a bucket: over every entry, from the bucket); the entries' .grad stay (the
+        caller clears them)."""
         if not self.entries:
             return
         k = self._turn
         self._turn ^= 1
         if self._events[k] is not None:
             self._events[k].synchronize()              # the copy enqueued from this table two steps ago has long run
-        for d, e in zip(self._tables[k], self.entries):
+        for d, e in zip(self._tables[k], self.entries if self.grads_from is None else ()):
             g = e.grad_of.grad
             if g is not None and not (g.is_contiguous() and g.dtype == torch.float32 and g.device == self.device and tuple(g.shape) == tuple(e.w.shape)):
                 raise hip.PodError("FusedSGD: a gradient that is not a contiguous fp32 tensor of its weight's shape on its GPU")

@@ -2,7 +2,7 @@
 
     python -m pod_compare_amd.train_head --coco-json <gt.json> --image-root <dir> --data-dir <checkpoints root> \
         --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn | --train-backbone]
-        [--fused-step] [--random-flip] [--resume]
+        [--fused-step] [--random-flip] [--resume] [--data-parallel [--backend nccl|gloo] [--share-gpu]]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
 shape together; a shape's frames wait until a batch of them is complete), the frozen backbone + FPN per image under no_grad through the
@@ -37,7 +37,18 @@ buffers under detectron2's names, the sampler's position, the frames waiting in 
 annealing, momentum and data order.  A checkpoint without the state, or from a run that trained other parts, is refused.  Without --resume
 the weights of last_checkpoint load as before and the run starts at iteration 0.
 
-Still NOT the reference's full trainer: one GPU.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies).
+--data-parallel [--backend nccl|gloo] [--share-gpu] (implies --fused-step): this process is one rank of a data-parallel run, as detectron2's
+launch starts them (RANK / WORLD_SIZE / LOCAL_RANK of torch.distributed.run; a process group that is already initialised is used as it
+is).  Every rank walks the same index stream, flip draws and shape buckets, so the global batches are the one-rank run's; rank r takes
+frames [r B / W, (r + 1) B / W) of each and decodes only those (the bucket key comes from the json's height / width).  Per step ONE
+launch packs every gradient times 1 / W into a flat bucket (K26, pod_compare_amd/data_parallel.py), the two losses behind them, ONE
+all-reduce sums it over the ranks and K25 steps from the bucket.  Each rank keeps its own loss state (its normaliser, its draws; seeds
+--random-seed + rank); rank 0's trained tensors and momentum are broadcast once at the start; only rank 0 prints (the rank means of the
+losses) and writes checkpoints, whose `pod_trainer` then carries `world` and `ranks`, every rank's loss state -- --resume continues at
+the same world size only.  SOLVER.IMS_PER_BATCH must be a multiple of W.
+
+Still NOT the reference's full trainer: the all-reduce does not overlap the backward pass, and a data-parallel rank reads its frames
+without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies).
 """
 import argparse
 import bisect
@@ -50,8 +61,9 @@ import torch
 from . import checkpoint, losses
 from .apply_net import CocoImages, Prefetched, add_dataset_arguments, evaluation_category_map
 from .compute_losses import image_ground_truth
-from .anchors import padded_size as _padded_size
+from .anchors import padded_size as _padded_size, resize_shortest_edge
 from .config import setup_config
+from .data_parallel import GradBucket, broadcast_tensors, gather_objects, rank_slice
 from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import head_convs
 from .resnet_train import FoldedMasters, res2_maps, resnet_forward_train, trainable_convs, unfolded_pairs
@@ -83,10 +95,15 @@ class HeadTrainer:
 
     def __init__(self, model, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, steps: Sequence[int] = (60000, 80000),
                  gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0, train_fpn: bool = False,
-                 train_backbone: bool = False, shadow=None, fused_step: bool = False):
+                 train_backbone: bool = False, shadow=None, fused_step: bool = False, data_parallel=None):
         """train_backbone: res3 - res5 train too (and the FPN: it lies between them and the head); `shadow`, the same model unfolded, gives
         the master weights and FrozenBN scales (resnet_train.FoldedMasters).  fused_step: the optimiser's step is pod_sgd_step (K25) on
-        momentum buffers the trainer owns (`self.fused`), not torch's SGD; `self.opt` is the torch.optim.SGD either way (unused when fused)."""
+        momentum buffers the trainer owns (`self.fused`), not torch's SGD; `self.opt` is the torch.optim.SGD either way (unused when fused).
+        data_parallel: (rank, world, process group or None = the default one) -- this trainer is one rank of `world`: its gradients go
+        through a bucket (`self.bucket`, data_parallel.GradBucket: K26, one all-reduce) and the fused step reads the rank mean from it.
+        Needs fused_step.  The loss state stays the rank's own, as under DistributedDataParallel."""
+        if data_parallel is not None and not fused_step:
+            raise ValueError("data_parallel needs fused_step: the averaged gradients are stepped from the bucket by pod_sgd_step")
         self.model, self.train_backbone = model, bool(train_backbone)
         self.train_fpn = bool(train_fpn) or self.train_backbone
         self.params = [p for c in head_convs(model.head) for p in (c.weight, c.bias)]
@@ -107,14 +124,20 @@ class HeadTrainer:
         self.opt = torch.optim.SGD(self.params, lr=float(base_lr), momentum=float(momentum), weight_decay=float(weight_decay))
         self.iteration = int(iteration)
         self.momentum_mu = float(momentum)
-        self.fused = None
+        self.fused, self.bucket, self.rank, self.world = None, None, 0, 1
         if fused_step:
             n_plain = len(self.params) - (len(self.masters.params) if self.masters is not None else 0)
             entries = [SgdEntry(p) for p in self.params[:n_plain]]
             if self.masters is not None:
                 entries += [SgdEntry(p, grad_of=c.weight, scale=s, folded=c.weight) for c, p, s in zip(self.masters.convs, self.masters.params, self.masters.scales)]
-            self.fused = FusedSGD(entries, momentum=float(momentum), weight_decay=float(weight_decay))
+            if data_parallel is not None:
+                self.rank, self.world, group = int(data_parallel[0]), int(data_parallel[1]), data_parallel[2]
+                if not 0 <= self.rank < self.world:
+                    raise ValueError("data_parallel: rank {} of world {}".format(self.rank, self.world))
+                self.bucket = GradBucket(entries, self.world, group)
+            self.fused = FusedSGD(entries, momentum=float(momentum), weight_decay=float(weight_decay), grads_from=self.bucket)
         self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
+        self._losses = None
 
     @property
     def lr(self) -> float:
@@ -186,7 +209,18 @@ class HeadTrainer:
         return stacked, padded
 
     def step(self, feats, padded, image_hw, gt_boxes, gt_classes, eps=None, normalizer=None) -> Dict[str, torch.Tensor]:
-        """One iteration on the stacked features of a batch; returns the losses (device scalars)."""
+        """One iteration on the stacked features of a batch; returns the losses (device scalars; under data_parallel this rank's own --
+        `mean_losses()` holds the rank means)."""
+        res = self.forward_backward(feats, padded, image_hw, gt_boxes, gt_classes, eps=eps, normalizer=normalizer)
+        if self.bucket is not None:
+            self.reduce_gradients()
+        self.optimizer_step(self._lr)
+        self.advance()
+        return res
+
+    def forward_backward(self, feats, padded, image_hw, gt_boxes, gt_classes, eps=None, normalizer=None) -> Dict[str, torch.Tensor]:
+        """The first part of a step: this iteration's learning rate, the head's forward, the losses and backward().  Leaves the gradients
+        in .grad and returns the losses (device scalars)."""
         lr = self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
         for g in self.opt.param_groups:
             g["lr"] = lr
@@ -194,13 +228,31 @@ class HeadTrainer:
         res = self.model.losses(out, gt_boxes, gt_classes, eps=eps, normalizer=normalizer)
         self.opt.zero_grad(set_to_none=True)
         (res["loss_cls"] + res["loss_box_reg"]).backward()
-        self.optimizer_step(lr)
-        self.model.loss_state.current_step += 1   # PR:146
-        self.iteration += 1
+        self._losses = {k: v.detach() for k, v in res.items()}        # (what reduce_gradients puts into the bucket's tail)
         return res
 
+    def reduce_gradients(self) -> None:
+        """data_parallel only, between forward_backward and optimizer_step: the gradients times 1 / world into the bucket (K26, one
+        launch), this rank's two losses behind them, and the one all-reduce -- after it the bucket holds the rank means."""
+        if self.bucket is None:
+            raise ValueError("reduce_gradients: this trainer was built without data_parallel")
+        self.bucket.pack()
+        self.bucket.set_tail(self._losses["loss_cls"], self._losses["loss_box_reg"])
+        self.bucket.all_reduce()
+
+    def mean_losses(self) -> Dict[str, torch.Tensor]:
+        """data_parallel: the rank means of the last step's losses (device scalars, views of the bucket's tail), as detectron2's
+        reduce_dict logs them."""
+        return {"loss_cls": self.bucket.tail[0], "loss_box_reg": self.bucket.tail[1]}
+
+    def advance(self) -> None:
+        """The end of a step: the loss state's step (PR:146) and the iteration count."""
+        self.model.loss_state.current_step += 1
+        self.iteration += 1
+
     def optimizer_step(self, lr: float) -> None:
-        """From the gradients backward() left to the stepped weights and refolded filters."""
+        """From the gradients backward() left (data_parallel: from the averaged ones in the bucket) to the stepped weights and refolded
+        filters."""
         if self.fused is not None:
             self.fused.step(lr)                   # K25: s dW', the step on W and W' = W s in one launch; bumps the written tensors' versions
             if self.masters is not None:
@@ -215,11 +267,12 @@ class HeadTrainer:
 
 
 def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, train_fpn: bool = False, train_backbone: bool = False, masters=None,
-                    trainer=None, sampler=None, random_seed: int = 0) -> str:
+                    trainer=None, sampler=None, random_seed: int = 0, ranks=None) -> str:
     """`shadow`: the same model unfolded (conv + FrozenBN pairs) on the CPU -- the form detectron2's names describe; it receives the
     trained head (train_fpn: and the trained FPN, which has no norm to unfold; train_backbone: and the master weights of res3 - res5,
     `masters` = the trainer's FoldedMasters) and is written as <out_dir>/<name>.pth, named in <out_dir>/last_checkpoint.  trainer: the
-    file also carries `pod_trainer`, the state --resume continues from (trainer_state; `sampler`: the FrameSampler of the run)."""
+    file also carries `pod_trainer`, the state --resume continues from (trainer_state; `sampler`: the FrameSampler of the run; `ranks`:
+    every rank's loss state, of a data-parallel run)."""
     os.makedirs(out_dir, exist_ok=True)
     pairs = list(zip(head_convs(shadow.head), head_convs(model.head)))
     if train_fpn or train_backbone:
@@ -235,7 +288,7 @@ def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, trai
     path = os.path.join(out_dir, name + ".pth")
     data = {"model": checkpoint.to_detectron2_state_dict(shadow, with_dropout_entries=model.use_dropout), "iteration": int(iteration)}
     if trainer is not None:
-        data[TRAINER_KEY] = trainer_state(trainer, sampler, random_seed)
+        data[TRAINER_KEY] = trainer_state(trainer, sampler, random_seed, ranks=ranks)
     torch.save(data, path)
     with open(os.path.join(out_dir, "last_checkpoint"), "w") as f:
         f.write(name + ".pth")
@@ -269,6 +322,18 @@ class FrameSampler:
         bucket.clear()
         return images, list(gb), list(gc)
 
+    def add_keyed(self, key, index: int, flipped: bool):
+        """`add` without the frame (data parallelism: a rank decodes only its own frames): files (index, flipped) under `key`, the shape the
+        frame will have; returns the batch's [(index, flipped)] in arrival order once `batch` entries of that key wait, else None."""
+        bucket = self.buckets.setdefault(tuple(key), [])
+        bucket.append((self.arrivals, int(index), bool(flipped), None, None, None))
+        self.arrivals += 1
+        if len(bucket) < self.batch:
+            return None
+        out = [(e[1], e[2]) for e in bucket]
+        bucket.clear()
+        return out
+
     def state(self) -> dict:
         pending = sorted(e[:3] for b in self.buckets.values() for e in b)
         return {"next_index": int(self.next_index), "pending": [[int(i), int(f)] for _, i, f in pending], "flip_generator": self.generator.get_state().clone()}
@@ -280,16 +345,32 @@ class FrameSampler:
         return [[int(i), int(f)] for i, f in state["pending"]]
 
 
-def trainer_state(trainer: HeadTrainer, sampler: Optional[FrameSampler] = None, random_seed: int = 0) -> dict:
-    """What a run needs beside the weights to continue where it stopped -- tensors, numbers, strings, lists and dicts only (the restricted
-    unpickler reads it)."""
+def loss_state_of(trainer: HeadTrainer) -> dict:
+    """The loss state of this trainer's model as a checkpoint holds it (a rank's own under data parallelism)."""
     ls = trainer.model.loss_state
     norm = ls.loss_normalizer
-    return {"iteration": int(trainer.iteration),
-            "loss_state": {"current_step": int(ls.current_step), "draws": int(ls.draws),
-                           "loss_normalizer": (norm.detach() if torch.is_tensor(norm) else torch.tensor(float(norm))).to("cpu", torch.float64).reshape(())},
-            "momentum": trainer.momentum_state(), "momentum_mu": float(trainer.momentum_mu), "trained": trainer.trained(),
-            "sampler": (sampler if sampler is not None else FrameSampler(1, seed=random_seed)).state(), "random_seed": int(random_seed)}
+    return {"current_step": int(ls.current_step), "draws": int(ls.draws),
+            "loss_normalizer": (norm.detach() if torch.is_tensor(norm) else torch.tensor(float(norm))).to("cpu", torch.float64).reshape(())}
+
+
+def trainer_state(trainer: HeadTrainer, sampler: Optional[FrameSampler] = None, random_seed: int = 0, ranks: Optional[List[dict]] = None) -> dict:
+    """What a run needs beside the weights to continue where it stopped -- tensors, numbers, strings, lists and dicts only (the restricted
+    unpickler reads it).  ranks: a data-parallel run of more than one rank adds `world` and `ranks`, every rank's loss_state_of in rank
+    order (`loss_state` is this rank's); a one-rank run writes the keys it always wrote."""
+    state = {"iteration": int(trainer.iteration), "loss_state": loss_state_of(trainer),
+             "momentum": trainer.momentum_state(), "momentum_mu": float(trainer.momentum_mu), "trained": trainer.trained(),
+             "sampler": (sampler if sampler is not None else FrameSampler(1, seed=random_seed)).state(), "random_seed": int(random_seed)}
+    if ranks is not None and len(ranks) > 1:
+        state["world"], state["ranks"] = len(ranks), [dict(r) for r in ranks]
+    return state
+
+
+def check_world(state: dict, world: int, path: str) -> None:
+    """SystemExit naming the file and both sizes unless `state` was written by a run of `world` ranks (a file without the field: by one)."""
+    wrote = int(state.get("world", 1))
+    if wrote != int(world) or (wrote > 1 and len(state.get("ranks", [])) != wrote):
+        raise SystemExit("--resume: {} was written by a run of {} rank{}, this one has {}: resume with the same world size".format(
+            path, wrote, "" if wrote == 1 else "s", int(world)))
 
 
 def read_trainer_state(path: str) -> dict:
@@ -302,7 +383,9 @@ def read_trainer_state(path: str) -> dict:
 
 
 def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
-    """Iteration, loss state and momentum from a checkpoint's `pod_trainer`; SystemExit naming the file where it does not fit this run."""
+    """Iteration, loss state and momentum from a checkpoint's `pod_trainer`; SystemExit naming the file where it does not fit this run
+    (its world size among the rest: a rank of a data-parallel run takes its own entry of `ranks`)."""
+    check_world(state, trainer.world, path)
     if list(state.get("trained", [])) != trainer.trained():
         raise SystemExit("--resume: {} comes from a run that trained {}, this one trains {}: give the same --train-fpn / --train-backbone".format(
             path, " + ".join(state.get("trained", [])) or "nothing", " + ".join(trainer.trained())))
@@ -312,9 +395,9 @@ def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
         raise SystemExit("--resume: {}: {}".format(path, e))
     trainer.iteration = int(state["iteration"])
     trainer._lr = warmup_multistep_lr(trainer.iteration, **trainer.schedule)
-    ls = trainer.model.loss_state
-    ls.current_step, ls.draws = int(state["loss_state"]["current_step"]), int(state["loss_state"]["draws"])
-    ls.loss_normalizer = float(state["loss_state"]["loss_normalizer"])
+    ls, own = trainer.model.loss_state, state["ranks"][trainer.rank] if trainer.world > 1 else state["loss_state"]
+    ls.current_step, ls.draws = int(own["current_step"]), int(own["draws"])
+    ls.loss_normalizer = float(own["loss_normalizer"])
 
 
 def main(argv=None):
@@ -346,8 +429,42 @@ def main(argv=None):
                                                                "data order from --random-seed), its boxes with it")
     ap.add_argument("--resume", action="store_true", help="continue the run OUTPUT_DIR/last_checkpoint stopped in: its weights and its trainer state "
                                                           "(iteration, loss state, momentum, data position); refused if the file carries none")
+    ap.add_argument("--data-parallel", action="store_true", help="one rank of a data-parallel run (RANK / WORLD_SIZE / LOCAL_RANK, as torch.distributed.run "
+                                                                 "sets them): the rank takes its share of every batch of SOLVER.IMS_PER_BATCH frames, the "
+                                                                 "gradients are averaged over the ranks through one bucket (K26) and one all-reduce; implies "
+                                                                 "--fused-step")
+    ap.add_argument("--backend", default="nccl", help="--data-parallel: torch.distributed backend: nccl = RCCL over xGMI (the real path); gloo for a "
+                                                      "functional run, e.g. several ranks on one GPU with --share-gpu")
+    ap.add_argument("--share-gpu", action="store_true", help="--data-parallel, functional check only: every rank uses cuda:0")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+    rank, world, group, own_group = 0, 1, None, False
+    if args.data_parallel:
+        import torch.distributed as dist
+        args.fused_step = True
+        if dist.is_initialized():                          # the caller's process group (and its --device) is used as it is
+            rank, world = dist.get_rank(), dist.get_world_size()
+        else:
+            rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+            local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
+            args.device = "cuda:%d" % local_rank
+            if world > 1:
+                if args.backend == "nccl":
+                    dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+                else:
+                    dist.init_process_group(args.backend)
+                own_group = True
+    try:
+        return _run(args, rank, world, group, bind=own_group)
+    finally:
+        if own_group:
+            dist.destroy_process_group()
+
+
+def _run(args, rank: int, world: int, group, bind: bool = False):
+    """main behind its arguments and process group: rank `rank` of `world` (1: the one-GPU run).  bind: this process was started as a rank
+    and is bound to its GPU's NUMA node, as apply_net binds its ranks (a caller that brought its own process group keeps its affinity)."""
+    say = print if rank == 0 else (lambda *a, **k: None)              # only rank 0 prints and writes
     cfg = setup_config(args.config_file, "", args.random_seed, data_dir=args.data_dir)
     if args.output_dir:
         cfg.OUTPUT_DIR = args.output_dir
@@ -370,8 +487,15 @@ def main(argv=None):
     if resume_state is not None and list(resume_state.get("trained", [])) != trains:          # (before a model is built; restore_trainer checks the rest)
         raise SystemExit("--resume: {} comes from a run that trained {}, this one trains {}: give the same --train-fpn / --train-backbone".format(
             resume_from, " + ".join(resume_state.get("trained", [])) or "nothing", " + ".join(trains)))
+    if resume_state is not None:
+        check_world(resume_state, world, resume_from)
+    first, last = rank_slice(max(1, int(cfg.SOLVER.IMS_PER_BATCH)), rank, world)           # this rank's frames of every global batch
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
+    if bind:                      # enqueue + loader threads of this rank on its GPU's NUMA node (hostbind.py; POD_BIND_NUMA=0: off)
+        from . import hostbind
+        b = hostbind.bind_rank_to_gpu_numa(dev.index or 0)
+        say("rank %d: %s pci %s numa node %s -> %s" % (rank, dev, b["pci"], b["numa_node"], b["cpus"] if b["bound"] else "not bound (%s)" % b.get("why_not", "off")))
     with open(args.coco_json, "r") as f:
         gt = json.load(f)
     if "annotations" not in gt:
@@ -394,10 +518,12 @@ def main(argv=None):
     model.loss_state = losses.ProbabilisticLosses(num_classes=K, cls_var_num_samples=cfg.MODEL.PROBABILISTIC_MODELING.CLS_VAR_LOSS.NUM_SAMPLES,
                                                   smooth_l1_beta=float(cfg.MODEL.RETINANET.get("SMOOTH_L1_LOSS_BETA", 0.0)),
                                                   box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=int(s.STEPS[1]),
-                                                  seed=args.random_seed)
+                                                  seed=args.random_seed + rank)
+    model.head.dropout_seed += rank                        # a rank's loss samples and dropout masks are its own, as detectron2 seeds its ranks
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
                           warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=train_fpn, train_backbone=args.train_backbone,
-                          shadow=shadow if args.train_backbone else None, fused_step=args.fused_step)
+                          shadow=shadow if args.train_backbone else None, fused_step=args.fused_step,
+                          data_parallel=(rank, world, group) if args.data_parallel else None)
     max_iter = args.max_iter if args.max_iter >= 0 else int(s.MAX_ITER)
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
@@ -414,20 +540,49 @@ def main(argv=None):
             image, boxes = image.flip(-1), hflip_boxes(boxes, float(image.shape[2]))
         return image, boxes, classes
 
+    def shape_key(index: int):
+        """--data-parallel: the shape frame `index` will have, from the json alone -- every rank files every frame, and decodes only its own."""
+        rec = dataset.images[index]
+        if "height" not in rec or "width" not in rec:
+            raise SystemExit("--data-parallel: image {} of {} has no `height` / `width`: the ranks agree on the batches from the json "
+                             "alone".format(rec.get("file_name", index), args.coco_json))
+        return (3,) + tuple(resize_shortest_edge(int(rec["height"]), int(rec["width"]), dataset.min_size, dataset.max_size))
+
+    def file_frame(index: int, flipped: bool, d=None):
+        """Files a frame with the sampler; a complete batch comes back as this rank's (images, boxes, classes) of it."""
+        if not args.data_parallel:
+            return sampler.add(index, flipped, *frame(dataset[index] if d is None else d, flipped))
+        ready = sampler.add_keyed(shape_key(index), index, flipped)
+        if ready is None:
+            return None
+        images, gb, gc = zip(*[frame(dataset[i], f) for i, f in ready[first:last]])
+        return images, list(gb), list(gc)
+
+    def write(name: str, it: int):
+        """A checkpoint: every rank hands in its loss state (the one collective of a checkpoint), rank 0 writes the file."""
+        ranks = gather_objects(loss_state_of(trainer), world, group) if world > 1 else None
+        if rank == 0:
+            written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, name, it, ranks=ranks, **saved))
+
     if resume_state is not None:
         restore_trainer(trainer, resume_state, resume_from)
         for index, flipped in sampler.load_state(resume_state["sampler"]):       # the frames that waited in the buckets, in arrival order
-            if not 0 <= index < len(dataset) or sampler.add(index, bool(flipped), *frame(dataset[index], bool(flipped))) is not None:
+            if not 0 <= index < len(dataset) or file_frame(index, bool(flipped)) is not None:
                 raise SystemExit("--resume: {}: its waiting frames do not fit this data set and SOLVER.IMS_PER_BATCH".format(resume_from))
         if not 0 <= sampler.next_index < max(1, len(dataset)):
             raise SystemExit("--resume: {}: stopped at frame {} of a data set of {}".format(resume_from, sampler.next_index, len(dataset)))
-        print("resumed %s at iteration %d" % (resume_from, trainer.iteration), flush=True)
+        say("resumed %s at iteration %d" % (resume_from, trainer.iteration), flush=True)
+    if world > 1:                 # once: every rank starts from rank 0's trained tensors (the masters and the filters folded from them) and momentum
+        folded = [c.weight for c in trainer.masters.convs] if trainer.masters is not None else []
+        broadcast_tensors(trainer.params + folded + trainer.fused.buffers, group)
     written, last_line, stalled = [], None, 0
     while trainer.iteration < max_iter:
         progressed = False
-        for index, d in Prefetched(dataset, range(sampler.next_index, len(dataset)), workers=workers):
+        indices = range(sampler.next_index, len(dataset))
+        # --data-parallel: the index stream alone; a rank reads a frame when the batch that holds it is complete
+        for index, d in (((i, None) for i in indices) if args.data_parallel else Prefetched(dataset, indices, workers=workers)):
             flipped = sampler.draw_flip()
-            ready = sampler.add(index, flipped, *frame(d, flipped))
+            ready = file_frame(index, flipped, d)
             sampler.next_index = (index + 1) % len(dataset)
             if ready is None:
                 continue
@@ -437,11 +592,12 @@ def main(argv=None):
             progressed = True
             it = trainer.iteration
             if args.log_period > 0 and (it % args.log_period == 0 or it == max_iter):
-                last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(res["loss_cls"]), float(res["loss_box_reg"]),
+                shown = trainer.mean_losses() if args.data_parallel else res          # (the rank means, from the bucket's tail)
+                last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(shown["loss_cls"]), float(shown["loss_box_reg"]),
                                                                                   trainer.lr)
-                print(last_line, flush=True)
+                say(last_line, flush=True)
             if period > 0 and it % period == 0 and it < max_iter:
-                written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_%07d" % (it - 1), it, **saved))
+                write("model_%07d" % (it - 1), it)
             if it >= max_iter:
                 break
         else:
@@ -449,10 +605,15 @@ def main(argv=None):
         stalled = 0 if progressed else stalled + 1      # (an incomplete batch carries over into the next pass over the data set)
         if stalled >= batch:
             raise SystemExit("no batch of {} frames of one resized shape can be formed from {} frames".format(batch, len(dataset)))
-    written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, "model_final", trainer.iteration, **saved))
+    write("model_final", trainer.iteration)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier(group)               # no rank leaves before the final checkpoint is on disk
     what = ", the FPN and res3 - res5" if args.train_backbone else " and the FPN" if train_fpn else ""
-    print("trained the head%s for %d iterations; wrote %s" % (what, trainer.iteration, written[-1]))
-    return {"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line}
+    if rank == 0:
+        print("trained the head%s for %d iterations; wrote %s" % (what, trainer.iteration, written[-1]))
+    return {"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line,
+            "trainer": trainer}
 
 
 if __name__ == "__main__":
