@@ -735,7 +735,9 @@ int pod_train_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelG
  *   products, fp32 accumulate.  The pixel reduction is cut into slices of 256 row segments of 16 pixels, enumerated by the geometry alone
  *   (level, image, column strip, row); each slice writes partial sums into `partials` (dev, 16-byte aligned,
  *   pod_conv3x3_wgrad_partials(...) floats; 0 = invalid geometry) and a second launch adds them in slice order in fp64 (db: fp64 column
- *   sums over chunks of 4096 pixels, added in chunk order): no atomics, two launches give the same bits.
+ *   sums over chunks of 4096 pixels, added in chunk order): no atomics, two launches give the same bits.  POD_E_INVALID before any
+ *   launch, as for every weight gradient (K22 - K24): a NULL pointer (db too, here); x, dy or partials off 16 bytes; a record, dW or db off
+ *   4 bytes; dW, db or partials aliasing each other or an operand; more slices or chunks than a grid's x holds.
  * pod_relu_dropout_backward: the gate of conv + bias + ReLU + dropout(p) as pod_wino_conv3x3_split's store pass computes it: the stored
  *   output is relu(z) keep / (1 - p) with exact zeros where ReLU or the mask killed the element, so d_z = d_out (out > 0) / (1 - p)
  *   (1.0f / (1.0f - p) in fp32, the forward's factor).  n % 4 == 0; d_z may be d_out; dz_amax: NULL or the zeroed record that receives
@@ -759,7 +761,8 @@ int pod_relu_dropout_backward(const float* out, const float* d_out, float* d_z, 
  *   into slices of 1024 pixels, halved down to 128 while slices x (K / 64) x ceil(C / 128) < 512 -- the geometry alone; each slice writes
  *   partial sums into `partials` (dev, 16-byte aligned, pod_conv1x1_wgrad_partials(...) floats; 0 = invalid geometry) and a second launch
  *   adds them in slice order in fp64 (db: fp64 column sums over chunks of 4096 pixels, added in chunk order): no atomics, two launches
- *   give the same bits.
+ *   give the same bits.  POD_E_INVALID before any launch as pod_conv3x3_wgrad's (db may be NULL): NULL or misaligned pointers (16 bytes:
+ *   x, dy, partials; 4 bytes: the records, dW, db), dW, db or partials aliasing each other or an operand.
  * pod_col2im3x3s2_cl: the input gradient of pod_im2col3x3s2_cl for one image.  dcols dev (Ho * Wo, 9 C), Ho = (H - 1) / 2 + 1,
  *   Wo = (W - 1) / 2 + 1, taps in (ty, tx) order; dx dev (H * W, C):
  *   dx[(y, x)][c] = (gate == NULL or gate[(y, x)][c] > 0 ? sum of dcols[(oy, ox)][(ty, tx, c)] over the taps with 2 oy + ty - 1 == y and
@@ -790,7 +793,7 @@ int pod_upsample2_sum_cl(const float* d_child, int32_t h, int32_t w, const float
  *   sums of dy.  stride 1 or 2, C % 16 == 0, C <= 18432, K % 64 == 0, K <= 2048, images * H_in * W_in < 2^30.  Arithmetic, slices (of the
  *   images * Ho * Wo OUTPUT pixels), `partials` (pod_conv1x1_wgrad_strided_partials(...) floats, 16-byte aligned; 0 = invalid geometry) and
  *   the fixed-order fp64 second launch as pod_conv1x1_wgrad: on the same pixels the two give the same bits.  The rows a stride selects are
- *   gathered in the kernel's loads, never materialised.  dW, db and partials may alias neither each other nor an operand.
+ *   gathered in the kernel's loads, never materialised.  Argument checks: pod_conv1x1_wgrad's.
  * pod_subsample2_scatter_cl: the input gradient of the stride-2 pixel selection for one image, with the gate and the sum the full map needs
  *   in the same pass.  d_small dev (Ho * Wo, C), Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; gate, add, dx dev (H * W, C):
  *   dx[(y, x)][c] = (gate == NULL or gate[(y, x)][c] > 0) ? ((y and x even ? d_small[(y / 2) Wo + x / 2][c] : 0) + (add == NULL ? 0 :

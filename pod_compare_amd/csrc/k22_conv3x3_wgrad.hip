@@ -17,10 +17,11 @@
 // Parallelism and determinism: the steps of a launch are enumerated by the geometry alone -- level, image, strip, row -- and cut into
 // SLICES of WG_STEPS consecutive steps; grid = slices x k tiles x c tiles.  A slice owns its X rows (all three taps of them), writes its
 // partial sums, and a second launch adds the slices' partials in slice order, in fp64.  No atomics: two launches give the same bits.
-// db: fp64 partial column sums over chunks of 4096 pixels (a launch of its own), added by the same second launch.
+// db: fp64 partial column sums over chunks of 4096 pixels (a launch of its own), added by the same second launch.  Both of them, the
+// partial buffer's layout, the argument checks and the launch sequence are pod_wgrad.h's (wgrad_launch), shared with K23 and K24.
 //
 // pod_relu_dropout_backward: the gate of a trunk layer.  The layer's stored output is relu(z) keep / (1 - p) (pod_wino.h's store pass:
-// scale = 1.0f / (1.0f - p), exact zeros where dropped), so it is its own mask: dZ = dOut (out > 0) / (1 - p).
+// scale = 1.0f / (1.0f - p), exact zeros where dropped), so it is its own mask: dZ = dOut (out > 0) / (1 - p) (pod_wgrad.h: quad_pass, gate4).
 #include "pod_wgrad.h"
 
 namespace pod {
@@ -184,22 +185,9 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wgrad(const float* __restric
     }
 }
 
-// (the db partials and the second launch that adds the slices in order: pod_wgrad.h, shared with k23_fpn_backward.hip)
-
 __global__ void __launch_bounds__(256) k_relu_dropout_backward(const float* __restrict__ out, const float* d_out, float* d_z, const int64_t n4, const float scale,
                                                                float* __restrict__ amax) {
-    float m = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const f32x4 o = reinterpret_cast<const f32x4*>(out)[i];
-        f32x4 g = reinterpret_cast<const f32x4*>(d_out)[i];
-        g.x = o.x > 0.f ? g.x * scale : 0.f;
-        g.y = o.y > 0.f ? g.y * scale : 0.f;
-        g.z = o.z > 0.f ? g.z * scale : 0.f;
-        g.w = o.w > 0.f ? g.w * scale : 0.f;
-        reinterpret_cast<f32x4*>(d_z)[i] = g;
-        m = wino_absmax4(m, g);
-    }
-    if (amax) wino_publish_amax_block(amax, m);      // (uniform: every thread of the workgroup calls it)
+    quad_pass(d_z, n4, amax, [&](const int64_t i) { return gate4(reinterpret_cast<const f32x4*>(d_out)[i], reinterpret_cast<const f32x4*>(out)[i], scale); });
 }
 
 // Host: the geometry of a launch.  false: outside what the kernel addresses.
@@ -227,39 +215,30 @@ static bool wgrad_geometry(const int32_t* level_hw, int32_t n_levels, int32_t co
     return true;
 }
 
+static WgradLayout wgrad3x3_layout(const WgradGeom& G, int64_t pixels, int32_t C, int32_t Kpad) {
+    return wgrad_layout(pixels, (G.total_steps + WG_STEPS - 1) / WG_STEPS, Kpad, 9, C);
+}
+
 }  // namespace pod
 
 extern "C" int64_t pod_conv3x3_wgrad_partials(const int32_t* level_hw, int32_t n_levels, int32_t copies, int32_t C, int32_t K, int32_t Kpad) {
     pod::WgradGeom G;
     int64_t pixels;
     if (!pod::wgrad_geometry(level_hw, n_levels, copies, C, K, Kpad, G, pixels)) return 0;
-    const int64_t n_slices = (G.first_step[n_levels] + pod::WG_STEPS - 1) / pod::WG_STEPS;
-    const int64_t n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
-    return 2 * n_chunks * Kpad + n_slices * 9 * Kpad * C;
+    return pod::wgrad3x3_layout(G, pixels, C, Kpad).floats;
 }
 
 extern "C" int pod_conv3x3_wgrad(const float* x, const float* dy, const int32_t* level_hw, int32_t n_levels, int32_t copies, int32_t C, int32_t K,
                                  int32_t Kpad, const float* x_amax, const float* dy_amax, float* dW, float* db, float* partials, pod_stream_t stream) {
     pod::WgradGeom G;
     int64_t pixels;
-    if (!x || !dy || !x_amax || !dy_amax || !dW || !db || !partials) return POD_E_INVALID;
-    if (!pod::wgrad_geometry(level_hw, n_levels, copies, C, K, Kpad, G, pixels)) return POD_E_INVALID;
-    if (!pod_aligned(16, x, dy, partials)) return POD_E_INVALID;
-    const int64_t n_slices = (G.first_step[n_levels] + pod::WG_STEPS - 1) / pod::WG_STEPS;
-    const int64_t n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
-    if (n_slices > 0x7FFFFFFF || n_chunks > 0x7FFFFFFF) return POD_E_INVALID;
-    double* dbp = reinterpret_cast<double*>(partials);
-    float* wp = partials + 2 * n_chunks * Kpad;
+    if (!db || !pod::wgrad_geometry(level_hw, n_levels, copies, C, K, Kpad, G, pixels)) return POD_E_INVALID;
+    const pod::WgradLayout L = pod::wgrad3x3_layout(G, pixels, C, Kpad);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pod::k_wgrad_db<pod::WG_DB_CHUNK>, dim3((unsigned)n_chunks, (unsigned)(Kpad / 64)), dim3(256), 0, s, dy, pixels, Kpad, dbp);
-    POD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pod::k_conv3x3_wgrad, dim3((unsigned)n_slices, (unsigned)(Kpad / 64), (unsigned)((C + 63) / 64)), dim3(256), 0, s, x, dy, G, C, K, Kpad,
-                       x_amax, dy_amax, wp);
-    POD_CHECK_LAUNCH();
-    const int64_t n_out = (int64_t)9 * K * C + K;
-    hipLaunchKernelGGL(pod::k_wgrad_reduce<9>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, Kpad, dW, db);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::wgrad_launch<9>(x, dy, pixels, C, K, Kpad, x_amax, dy_amax, L, partials, dW, db, s, [&](float* wp) {
+        hipLaunchKernelGGL(pod::k_conv3x3_wgrad, dim3((unsigned)L.n_slices, (unsigned)(Kpad / 64), (unsigned)((C + 63) / 64)), dim3(256), 0, s, x, dy, G, C, K, Kpad, x_amax,
+                           dy_amax, wp);
+    });
 }
 
 extern "C" int pod_relu_dropout_backward(const float* out, const float* d_out, float* d_z, int64_t n, float p, float* dz_amax, pod_stream_t stream) {

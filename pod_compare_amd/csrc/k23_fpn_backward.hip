@@ -13,7 +13,7 @@
 // half-wave read 32 consecutive channels of one pixel, conflict-free whatever the row stride).  The next step's rows are asked for ahead of
 // the current step's products.  A pixel tail and a channel-tile edge are zero-filled in the staging, never read.
 //
-// (The kernel itself, k_conv1x1_wgrad, is in pod_wgrad.h: K24 launches it too, on the rows a stride selects.)
+// (The kernel, k_conv1x1_wgrad, and its launcher, c1w_launch, are in pod_wgrad.h: K24 runs them too, on the rows a stride selects.)
 //
 // Parallelism and determinism: the pixels are cut into SLICES of c1w_slice_pixels(pixels, C, K) consecutive pixels -- the geometry alone:
 // 1024, halved down to 128 while the launch has fewer than 512 workgroups; grid = slices x k tiles x c tiles.  A slice writes its
@@ -22,7 +22,8 @@
 //
 // pod_col2im3x3s2_cl, pod_upsample2_sum_cl: the two gathers of the backward pass -- the input gradient of pod_im2col3x3s2_cl (with the
 // ReLU gate of p7's input and the gradient p6 already has), and the backward of the nearest top-down sum at factor two.  One thread per
-// 16 bytes of the result, a fixed order of at most four terms, the result's abs-max record published by the same pass.
+// 16 bytes of the result, a fixed order of at most four terms, the result's abs-max record published by the same pass: the loop, the
+// gate and the entries' shared check are pod_wgrad.h's (map_quad_pass, gate4, map_gather).
 #include "pod_wgrad.h"
 
 namespace pod {
@@ -31,12 +32,7 @@ namespace pod {
 // (2 oy + ty - 1, 2 ox + tx - 1), so pixel (y, x) is met by oy = (y + 1 - ty) / 2 where that is integral and in range -- ty, tx ascending.
 __global__ void __launch_bounds__(256) k_col2im3x3s2_cl(const float* __restrict__ dcols, const float* __restrict__ gate, const float* add, float* dx, const int H,
                                                         const int W, const int Ho, const int Wo, const int C4, float* __restrict__ amax) {
-    const int64_t n = (int64_t)H * W * C4, stride = (int64_t)gridDim.x * blockDim.x;
-    float m = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int c4 = (int)(i % C4);
-        const int64_t pix = i / C4;
-        const int x = (int)(pix % W), y = (int)(pix / W);
+    map_quad_pass(dx, H, W, C4, amax, [&](const int64_t i, const int c4, const int x, const int y) {
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ty = 0; ty < 3; ++ty) {
@@ -49,29 +45,16 @@ __global__ void __launch_bounds__(256) k_col2im3x3s2_cl(const float* __restrict_
                 v += *reinterpret_cast<const f32x4*>(dcols + ((((int64_t)oy * Wo + ox) * 9 + ty * 3 + tx) * C4 + c4) * 4);
             }
         }
-        if (gate) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gate + i * 4);
-            v.x = g.x > 0.f ? v.x : 0.f;
-            v.y = g.y > 0.f ? v.y : 0.f;
-            v.z = g.z > 0.f ? v.z : 0.f;
-            v.w = g.w > 0.f ? v.w : 0.f;
-        }
+        if (gate) v = gate4(v, *reinterpret_cast<const f32x4*>(gate + i * 4));
         if (add) v += *reinterpret_cast<const f32x4*>(add + i * 4);
-        *reinterpret_cast<f32x4*>(dx + i * 4) = v;
-        m = wino_absmax4(m, v);
-    }
-    if (amax) wino_publish_amax_block(amax, m);      // (uniform: every thread of the workgroup calls it)
+        return v;
+    });
 }
 
 // d_top[(Y, X)] = add[(Y, X)] + the children (2 Y + dy, 2 X + dx) of d_child that exist, dy then dx ascending
 __global__ void __launch_bounds__(256) k_upsample2_sum_cl(const float* __restrict__ d_child, const int h, const int w, const float* add, float* d_top, const int Ht,
                                                           const int Wt, const int C4, float* __restrict__ amax) {
-    const int64_t n = (int64_t)Ht * Wt * C4, stride = (int64_t)gridDim.x * blockDim.x;
-    float m = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int c4 = (int)(i % C4);
-        const int64_t pix = i / C4;
-        const int X = (int)(pix % Wt), Y = (int)(pix / Wt);
+    map_quad_pass(d_top, Ht, Wt, C4, amax, [&](const int64_t i, const int c4, const int X, const int Y) {
         f32x4 v = *reinterpret_cast<const f32x4*>(add + i * 4);
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
@@ -80,10 +63,8 @@ __global__ void __launch_bounds__(256) k_upsample2_sum_cl(const float* __restric
                 const int y = 2 * Y + dy, x = 2 * X + dx;
                 if (y < h && x < w) v += *reinterpret_cast<const f32x4*>(d_child + (((int64_t)y * w + x) * C4 + c4) * 4);
             }
-        *reinterpret_cast<f32x4*>(d_top + i * 4) = v;
-        m = wino_absmax4(m, v);
-    }
-    if (amax) wino_publish_amax_block(amax, m);      // (uniform)
+        return v;
+    });
 }
 
 // Host: false = outside what the kernel addresses.
@@ -94,52 +75,27 @@ static bool c1w_geometry(int64_t pixels, int32_t C, int32_t K) {
 }  // namespace pod
 
 extern "C" int64_t pod_conv1x1_wgrad_partials(int64_t pixels, int32_t C, int32_t K) {
-    if (!pod::c1w_geometry(pixels, C, K)) return 0;
-    const int sp = pod::c1w_slice_pixels(pixels, C, K);
-    const int64_t n_slices = (pixels + sp - 1) / sp, n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
-    return 2 * n_chunks * K + n_slices * K * C;
+    return pod::c1w_geometry(pixels, C, K) ? pod::c1w_layout(pixels, C, K).floats : 0;
 }
 
 extern "C" int pod_conv1x1_wgrad(const float* x, const float* dy, int64_t pixels, int32_t C, int32_t K, const float* x_amax, const float* dy_amax, float* dW,
                                  float* db, float* partials, pod_stream_t stream) {
-    if (!x || !dy || !x_amax || !dy_amax || !dW || !partials) return POD_E_INVALID;
     if (!pod::c1w_geometry(pixels, C, K)) return POD_E_INVALID;
-    if (!pod_aligned(16, x, dy, partials)) return POD_E_INVALID;
-    const int sp = pod::c1w_slice_pixels(pixels, C, K);
-    const int64_t n_slices = (pixels + sp - 1) / sp, n_chunks = (pixels + pod::WG_DB_CHUNK - 1) / pod::WG_DB_CHUNK;
-    double* dbp = reinterpret_cast<double*>(partials);
-    float* wp = partials + 2 * n_chunks * K;
-    hipStream_t s = (hipStream_t)stream;
-    if (db) {
-        hipLaunchKernelGGL(pod::k_wgrad_db<pod::WG_DB_CHUNK>, dim3((unsigned)n_chunks, (unsigned)(K / 64)), dim3(256), 0, s, dy, pixels, K, dbp);
-        POD_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(pod::k_conv1x1_wgrad<false>, dim3((unsigned)n_slices, (unsigned)(K / pod::C1W_KT), (unsigned)((C + pod::C1W_CT - 1) / pod::C1W_CT)), dim3(256), 0, s, x, dy,
-                       pixels, C, K, sp, x_amax, dy_amax, wp, pod::C1wGather{});
-    POD_CHECK_LAUNCH();
-    const int64_t n_out = (int64_t)K * C + (db ? K : 0);
-    hipLaunchKernelGGL(pod::k_wgrad_reduce<1>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)n_slices, dbp, (int)n_chunks, C, K, K, dW, db);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::c1w_launch<false>(x, dy, pixels, C, K, pod::C1wGather{}, x_amax, dy_amax, dW, db, partials, (hipStream_t)stream);
 }
 
 extern "C" int pod_col2im3x3s2_cl(const float* dcols, const float* gate, const float* add, float* dx, int32_t H, int32_t W, int32_t C, float* dx_amax,
                                   pod_stream_t stream) {
-    if (!dcols || !dx || dcols == dx || gate == dx || H < 1 || W < 1 || H > 16384 || W > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
-    if (!pod_aligned(16, dcols, gate, add, dx) || !pod_aligned(4, dx_amax)) return POD_E_INVALID;
-    const int32_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int64_t n4 = (int64_t)H * W * (C / 4);
-    hipLaunchKernelGGL(pod::k_col2im3x3s2_cl, dim3(pod_grid_stride_blocks(n4, 4096)), dim3(256), 0, (hipStream_t)stream, dcols, gate, add, dx, H, W, Ho, Wo, C / 4, dx_amax);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    const int32_t Ho = (int32_t)(((int64_t)H - 1) / 2 + 1), Wo = (int32_t)(((int64_t)W - 1) / 2 + 1);      // (H, W are checked below)
+    return pod::map_gather(dcols, gate, add, dx, H, W, C, dx_amax, (int64_t)H * W, [&](dim3 grid) {
+        hipLaunchKernelGGL(pod::k_col2im3x3s2_cl, grid, dim3(256), 0, (hipStream_t)stream, dcols, gate, add, dx, H, W, Ho, Wo, C / 4, dx_amax);
+    });
 }
 
 extern "C" int pod_upsample2_sum_cl(const float* d_child, int32_t h, int32_t w, const float* add, float* d_top, int32_t C, float* d_top_amax, pod_stream_t stream) {
-    if (!d_child || !add || !d_top || d_child == d_top || h < 1 || w < 1 || h > 16384 || w > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
-    if (!pod_aligned(16, d_child, add, d_top) || !pod_aligned(4, d_top_amax)) return POD_E_INVALID;
-    const int32_t Ht = (h + 1) / 2, Wt = (w + 1) / 2;
-    const int64_t n4 = (int64_t)Ht * Wt * (C / 4);
-    hipLaunchKernelGGL(pod::k_upsample2_sum_cl, dim3(pod_grid_stride_blocks(n4, 4096)), dim3(256), 0, (hipStream_t)stream, d_child, h, w, add, d_top, Ht, Wt, C / 4, d_top_amax);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    const int32_t Ht = (int32_t)(((int64_t)h + 1) / 2), Wt = (int32_t)(((int64_t)w + 1) / 2);      // (h, w are checked below)
+    if (!add) return POD_E_INVALID;
+    return pod::map_gather(d_child, nullptr, add, d_top, h, w, C, d_top_amax, (int64_t)Ht * Wt, [&](dim3 grid) {
+        hipLaunchKernelGGL(pod::k_upsample2_sum_cl, grid, dim3(256), 0, (hipStream_t)stream, d_child, h, w, add, d_top, Ht, Wt, C / 4, d_top_amax);
+    });
 }

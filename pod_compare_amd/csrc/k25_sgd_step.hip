@@ -5,19 +5,15 @@
 //     a = scale ? s[i / per_channel] * g[i] : g[i];  g' = a + wd * w[i];  m' = mu * m[i] + g';  w' = w[i] - lr * m'
 //     m[i] = m';  w[i] = w';  folded[i] = w' * s[i / per_channel]
 // Work is cut into chunks of POD_SGD_CHUNK elements of ONE tensor, listed in a chunk map (tensor, chunk of that tensor) that is built once
-// per parameter set (pod_sgd_chunk_map) and stays on the device: a 2.4 M-element filter is 576 chunks, a 36-float bias one, and the
-// workgroups walk the map with a grid stride.  A workgroup takes a chunk in 4 trips of 256 lanes x 16 bytes; the elements behind a tensor's
-// last whole float4 (n % 4, the 63-float bias of cls_score) go to the lane that would have held them, one float at a time.  A chunk whose
-// tensor has no gradient this step is left alone, weight decay and momentum decay included, as torch leaves a parameter whose .grad is None.
-// Plain vector loads and stores; nothing is shared between lanes, so two launches give the same bits.
+// per parameter set (pod_sgd_chunk_map) and stays on the device: a 2.4 M-element filter is 576 chunks, a 36-float bias one.  The walk over
+// the map, shared with K26, is pod_tensor_table.h's: whole float4s, then a tensor's last n % 4 floats (the 63-float bias of cls_score) one
+// at a time.  A chunk whose tensor has no gradient this step is left alone, weight decay and momentum decay included, as torch leaves a
+// parameter whose .grad is None.  Plain vector loads and stores; nothing is shared between lanes, so two launches give the same bits.
 #include <cmath>
 
-#include "pod_device.h"
+#include "pod_tensor_table.h"
 
 namespace pod {
-
-constexpr int SGD_THREADS = 256;
-constexpr int SGD_MAX_BLOCKS = 2048;            // 256 CUs x 8 workgroups: the memory-bound grid cap, the rest by grid stride
 
 struct SgdHyper {
     float lr, mu, wd;
@@ -29,28 +25,22 @@ __device__ __forceinline__ void sgd_one(float& w, float& m, const float a, const
     w = w - h.lr * m;
 }
 
-__global__ void __launch_bounds__(SGD_THREADS) k_sgd_step(const PodSgdTensor* __restrict__ table, const int32_t n_tensors, const int32_t* __restrict__ chunk_map,
-                                                          const int64_t n_chunks, const SgdHyper h) {
-    for (int64_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
-        const int32_t t = chunk_map[2 * ci], chunk = chunk_map[2 * ci + 1];
-        if (t < 0 || t >= n_tensors || chunk < 0) continue;                    // (a map that does not belong to the table touches nothing)
-        const PodSgdTensor d = table[t];
-        const int64_t first = (int64_t)chunk * POD_SGD_CHUNK;
-        if (d.grad == nullptr || first >= d.n) continue;
-        const int64_t end = first + POD_SGD_CHUNK < d.n ? first + POD_SGD_CHUNK : d.n;
-        for (int64_t i = first + 4 * (int64_t)threadIdx.x; i < end; i += 4 * SGD_THREADS) {
-            // the channel of element i and how far into it i lies: one division per trip, then a walk (per_channel may be 1)
-            int64_t c = 0, r = 0;
+// (the chunk walk: pod_tensor_table.h)
+__global__ void __launch_bounds__(TABLE_THREADS) k_sgd_step(const PodSgdTensor* __restrict__ table, const int32_t n_tensors, const int32_t* __restrict__ chunk_map,
+                                                            const int64_t n_chunks, const SgdHyper h) {
+    table_chunk_walk(
+        table, n_tensors, chunk_map, n_chunks,
+        [&](int32_t, const PodSgdTensor& d, const int64_t i) {                 // FrozenBN's s of the four elements at i (1 where there is none)
+            f32x4 s = {1.f, 1.f, 1.f, 1.f};
             if (d.scale) {
+                // the channel of element i and how far into it i lies: one division per trip, then a walk (per_channel may be 1)
+                int64_t c;
                 if (((uint64_t)i | (uint64_t)d.per_channel) >> 32) {
                     c = i / d.per_channel;
                 } else {
                     c = (int64_t)((uint32_t)i / (uint32_t)d.per_channel);
                 }
-                r = i - c * d.per_channel;
-            }
-            float s[4] = {1.f, 1.f, 1.f, 1.f};
-            if (d.scale) {
+                int64_t r = i - c * d.per_channel;
                 const int64_t c_last = (d.n - 1) / d.per_channel;              // (never read behind the last channel for lanes past a tail)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -61,31 +51,28 @@ __global__ void __launch_bounds__(SGD_THREADS) k_sgd_step(const PodSgdTensor* __
                     }
                 }
             }
-            if (i + 4 <= end) {
-                const f32x4 g = *reinterpret_cast<const f32x4*>(d.grad + i);
-                const f32x4 w4 = *reinterpret_cast<const f32x4*>(d.w + i);
-                const f32x4 m4 = *reinterpret_cast<const f32x4*>(d.momentum + i);
-                float w[4] = {w4.x, w4.y, w4.z, w4.w}, m[4] = {m4.x, m4.y, m4.z, m4.w};
-                const float a[4] = {g.x, g.y, g.z, g.w};
+            return s;
+        },
+        [&](const PodSgdTensor& d, const int64_t i, const f32x4 s) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(d.grad + i);
+            const f32x4 w4 = *reinterpret_cast<const f32x4*>(d.w + i);
+            const f32x4 m4 = *reinterpret_cast<const f32x4*>(d.momentum + i);
+            float w[4] = {w4.x, w4.y, w4.z, w4.w}, m[4] = {m4.x, m4.y, m4.z, m4.w};
+            const float a[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) sgd_one(w[j], m[j], d.scale ? s[j] * a[j] : a[j], h);
-                *reinterpret_cast<f32x4*>(d.momentum + i) = f32x4{m[0], m[1], m[2], m[3]};
-                *reinterpret_cast<f32x4*>(d.w + i) = f32x4{w[0], w[1], w[2], w[3]};
-                if (d.folded) *reinterpret_cast<f32x4*>(d.folded + i) = f32x4{w[0] * s[0], w[1] * s[1], w[2] * s[2], w[3] * s[3]};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {                                  // the tensor's tail: n % 4 floats
-                    if (i + j >= end) break;
-                    float w = d.w[i + j], m = d.momentum[i + j];
-                    const float g = d.grad[i + j];
-                    sgd_one(w, m, d.scale ? s[j] * g : g, h);
-                    d.momentum[i + j] = m;
-                    d.w[i + j] = w;
-                    if (d.folded) d.folded[i + j] = w * s[j];
-                }
-            }
-        }
-    }
+            for (int j = 0; j < 4; ++j) sgd_one(w[j], m[j], d.scale ? s[j] * a[j] : a[j], h);
+            *reinterpret_cast<f32x4*>(d.momentum + i) = f32x4{m[0], m[1], m[2], m[3]};
+            *reinterpret_cast<f32x4*>(d.w + i) = f32x4{w[0], w[1], w[2], w[3]};
+            if (d.folded) *reinterpret_cast<f32x4*>(d.folded + i) = f32x4{w[0] * s[0], w[1] * s[1], w[2] * s[2], w[3] * s[3]};
+        },
+        [&](const PodSgdTensor& d, const int64_t i, const int j, const f32x4 s) {
+            float w = d.w[i + j], m = d.momentum[i + j];
+            const float g = d.grad[i + j];
+            sgd_one(w, m, d.scale ? s[j] * g : g, h);
+            d.momentum[i + j] = m;
+            d.w[i + j] = w;
+            if (d.folded) d.folded[i + j] = w * s[j];
+        });
 }
 
 }  // namespace pod
@@ -123,12 +110,8 @@ extern "C" int pod_sgd_step(const PodSgdTensor* tensors, PodSgdTensor* tensors_d
     if (expect < 0 || n_chunks != expect) return POD_E_INVALID;
     if (n_chunks == 0) return POD_OK;
     if (!tensors_dev || !chunk_map || !pod_aligned(8, tensors_dev) || !pod_aligned(4, chunk_map)) return POD_E_INVALID;
-    // the table changes every step (gradients are fresh allocations): one copy, ordered on the stream before the launch.  From pinned memory
-    // it is asynchronous, and the caller keeps `tensors` unchanged until the copy has run (an event after this call)
-    if (hipMemcpyAsync(tensors_dev, tensors, sizeof(PodSgdTensor) * (size_t)n_tensors, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return POD_E_LAUNCH;
-    const unsigned blocks = (unsigned)(n_chunks < pod::SGD_MAX_BLOCKS ? n_chunks : pod::SGD_MAX_BLOCKS);
-    hipLaunchKernelGGL(pod::k_sgd_step, dim3(blocks), dim3(pod::SGD_THREADS), 0, (hipStream_t)stream, (const PodSgdTensor*)tensors_dev, n_tensors, chunk_map, n_chunks,
-                       pod::SgdHyper{lr, momentum, weight_decay});
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::table_copy_and_launch(tensors, tensors_dev, n_tensors, n_chunks, (hipStream_t)stream, [&](dim3 blocks, const PodSgdTensor* table) {
+        hipLaunchKernelGGL(pod::k_sgd_step, blocks, dim3(pod::TABLE_THREADS), 0, (hipStream_t)stream, table, n_tensors, chunk_map, n_chunks,
+                           pod::SgdHyper{lr, momentum, weight_decay});
+    });
 }

@@ -3,45 +3,33 @@
 //     bucket[offsets[t] + i] = scale * grad_t[i]
 // The layout (pod_grad_bucket_layout) puts tensor t at the running sum of the previous tensors' n, each rounded up to 4 floats: every
 // tensor starts on 16 bytes, and what K25 needs of a gradient pointer holds for the slice.  The padding floats between tensors are never
-// written: the owner zeroes the bucket once, and a SUM over ranks keeps them zero.  Work is cut as K25 cuts it -- the chunk map of the same
-// table (pod_sgd_chunk_map), chunks of POD_SGD_CHUNK elements of one tensor, 256 lanes x 16 bytes, grid stride -- and a tensor's last n % 4
-// floats go one at a time.  Plain vector loads and stores, nothing shared between lanes: two launches give the same bits, and with
-// scale == 1 the bucket holds the gradients' own bits.
+// written: the owner zeroes the bucket once, and a SUM over ranks keeps them zero.  Work is cut as K25 cuts it: the chunk map of the same
+// table (pod_sgd_chunk_map), walked by pod_tensor_table.h.  Plain vector loads and stores, nothing shared between lanes: two launches give
+// the same bits, and with scale == 1 the bucket holds the gradients' own bits.
 #include <cmath>
 
-#include "pod_device.h"
+#include "pod_tensor_table.h"
 
 namespace pod {
 
-constexpr int PACK_THREADS = 256;
-constexpr int PACK_MAX_BLOCKS = 2048;           // as K25: 256 CUs x 8 workgroups, the rest by grid stride
-
-__global__ void __launch_bounds__(PACK_THREADS) k_grad_pack(const PodSgdTensor* __restrict__ table, const int32_t n_tensors, const int32_t* __restrict__ chunk_map,
-                                                            const int64_t n_chunks, const int64_t* __restrict__ offsets, float* __restrict__ bucket,
-                                                            const int64_t bucket_floats, const float scale) {
-    for (int64_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
-        const int32_t t = chunk_map[2 * ci], chunk = chunk_map[2 * ci + 1];
-        if (t < 0 || t >= n_tensors || chunk < 0) continue;                    // (a map that does not belong to the table touches nothing)
-        const PodSgdTensor d = table[t];
-        const int64_t first = (int64_t)chunk * POD_SGD_CHUNK;
-        if (d.grad == nullptr || first >= d.n) continue;
-        const int64_t o = offsets[t];
-        if (o < 0 || (o & 3) || o > bucket_floats - d.n) continue;             // (offsets of another table: never a store outside the bucket)
-        const int64_t end = first + POD_SGD_CHUNK < d.n ? first + POD_SGD_CHUNK : d.n;
-        float* __restrict__ dst = bucket + o;
-        for (int64_t i = first + 4 * (int64_t)threadIdx.x; i < end; i += 4 * PACK_THREADS) {
-            if (i + 4 <= end) {
-                const f32x4 g = *reinterpret_cast<const f32x4*>(d.grad + i);
-                *reinterpret_cast<f32x4*>(dst + i) = f32x4{scale * g.x, scale * g.y, scale * g.z, scale * g.w};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {                                  // the tensor's tail: n % 4 floats
-                    if (i + j >= end) break;
-                    dst[i + j] = scale * d.grad[i + j];
-                }
-            }
-        }
-    }
+// (the chunk walk: pod_tensor_table.h)
+__global__ void __launch_bounds__(TABLE_THREADS) k_grad_pack(const PodSgdTensor* __restrict__ table, const int32_t n_tensors, const int32_t* __restrict__ chunk_map,
+                                                             const int64_t n_chunks, const int64_t* __restrict__ offsets, float* __restrict__ bucket,
+                                                             const int64_t bucket_floats, const float scale) {
+    table_chunk_walk(
+        table, n_tensors, chunk_map, n_chunks,
+        [&](const int32_t t, const PodSgdTensor& d, int64_t) -> float* {       // the tensor's slice (offsets of another table: never a store outside the bucket)
+            const int64_t o = offsets[t];
+            return (o < 0 || (o & 3) || o > bucket_floats - d.n) ? nullptr : bucket + o;
+        },
+        [&](const PodSgdTensor& d, const int64_t i, float* dst) {
+            if (!dst) return;
+            const f32x4 g = *reinterpret_cast<const f32x4*>(d.grad + i);
+            *reinterpret_cast<f32x4*>(dst + i) = f32x4{scale * g.x, scale * g.y, scale * g.z, scale * g.w};
+        },
+        [&](const PodSgdTensor& d, const int64_t i, const int j, float* dst) {
+            if (dst) dst[i + j] = scale * d.grad[i + j];
+        });
 }
 
 }  // namespace pod
@@ -75,11 +63,8 @@ extern "C" int pod_grad_pack(const PodSgdTensor* tensors, PodSgdTensor* tensors_
     if (n_chunks == 0) return POD_OK;
     if (!bucket || !tensors_dev || !chunk_map || !offsets_dev) return POD_E_INVALID;
     if (!pod_aligned(16, bucket) || !pod_aligned(8, tensors_dev, offsets_dev) || !pod_aligned(4, chunk_map)) return POD_E_INVALID;
-    // as pod_sgd_step: one copy of the table (the gradients are fresh allocations every step), ordered on the stream before the launch
-    if (hipMemcpyAsync(tensors_dev, tensors, sizeof(PodSgdTensor) * (size_t)n_tensors, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) return POD_E_LAUNCH;
-    const unsigned blocks = (unsigned)(n_chunks < pod::PACK_MAX_BLOCKS ? n_chunks : pod::PACK_MAX_BLOCKS);
-    hipLaunchKernelGGL(pod::k_grad_pack, dim3(blocks), dim3(pod::PACK_THREADS), 0, (hipStream_t)stream, (const PodSgdTensor*)tensors_dev, n_tensors, chunk_map, n_chunks,
-                       offsets_dev, bucket, bucket_floats, scale);
-    POD_CHECK_LAUNCH();
-    return POD_OK;
+    return pod::table_copy_and_launch(tensors, tensors_dev, n_tensors, n_chunks, (hipStream_t)stream, [&](dim3 blocks, const PodSgdTensor* table) {
+        hipLaunchKernelGGL(pod::k_grad_pack, blocks, dim3(pod::TABLE_THREADS), 0, (hipStream_t)stream, table, n_tensors, chunk_map, n_chunks, offsets_dev, bucket,
+                           bucket_floats, scale);
+    });
 }

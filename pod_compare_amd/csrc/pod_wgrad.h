@@ -1,6 +1,9 @@
-// What the weight-gradient kernels share (k22_conv3x3_wgrad.hip, k23_fpn_backward.hip): the bias gradient's fp64 column sums and the
-// second launch that adds the slices' partial sums in slice order -- and the 1x1 weight gradient's kernel, which K23 launches on consecutive
-// rows and K24 (k24_resnet_backward.hip) on the rows a stride selects.  Templates, so that each file that launches them carries its own copy.
+// What k22_conv3x3_wgrad.hip, k23_fpn_backward.hip and k24_resnet_backward.hip share.  The weight gradients: the bias gradient's fp64
+// column sums, the second launch that adds the slices' partial sums in slice order, the partial buffer's layout (WgradLayout), the entries'
+// argument checks and three launches (wgrad_launch), and the 1x1 kernel with its launcher (c1w_launch), which K23 runs on consecutive rows
+// and K24 on the rows a stride selects.  The element-wise passes: the grid-stride loop over 16-byte quads with its abs-max record
+// (quad_pass, map_quad_pass), the ReLU gate (gate4), the map gathers' host check and launch (map_gather).
+// Templates and static functions, so that each file that launches them carries its own copy.
 #pragma once
 #include "pod_split_gemm.h"
 
@@ -173,6 +176,103 @@ __global__ void __launch_bounds__(256, 2) k_conv1x1_wgrad(const float* __restric
             }
         }
     }
+}
+
+// Host.  The partial buffer of a weight gradient: the db partials [chunk][k < Kpad] in fp64 (two floats each), then the slices' partial sums
+// [slice][tap][k < Kpad][c < C].
+struct WgradLayout {
+    int64_t n_slices, n_chunks, db_floats, floats;
+    double* dbp(float* partials) const { return reinterpret_cast<double*>(partials); }
+    float* wp(float* partials) const { return partials + db_floats; }
+};
+static inline WgradLayout wgrad_layout(int64_t pixels, int64_t n_slices, int Kpad, int taps, int C) {
+    const int64_t n_chunks = (pixels + WG_DB_CHUNK - 1) / WG_DB_CHUNK, db_floats = 2 * n_chunks * Kpad;
+    return WgradLayout{n_slices, n_chunks, db_floats, db_floats + n_slices * taps * Kpad * C};
+}
+
+// Host.  What every weight-gradient entry does behind its geometry check.  The arguments: only db may be null (no bias gradient); dW, db and
+// partials alias neither each other nor an operand; the slices and chunks fit the grid's x.  Then the three launches: the db partials (if
+// db), main(wp) -- the caller's kernel, which writes the slices' partials -- and the fixed-order fp64 reduction into dW (K, C, TAPS), db (K).
+template <int TAPS, class Main>
+static inline int wgrad_launch(const float* x, const float* dy, int64_t pixels, int C, int K, int Kpad, const float* x_amax, const float* dy_amax, const WgradLayout& L,
+                               float* partials, float* dW, float* db, hipStream_t s, Main&& main) {
+    if (!x || !dy || !x_amax || !dy_amax || !dW || !partials) return POD_E_INVALID;
+    if (!pod_aligned(16, x, dy, partials) || !pod_aligned(4, x_amax, dy_amax, dW, db)) return POD_E_INVALID;
+    if (dW == x || dW == dy || dW == partials || x == partials || dy == partials) return POD_E_INVALID;
+    if (db && (db == dW || db == partials || db == x || db == dy)) return POD_E_INVALID;
+    if (L.n_slices > 0x7FFFFFFF || L.n_chunks > 0x7FFFFFFF) return POD_E_INVALID;
+    double* dbp = L.dbp(partials);
+    float* wp = L.wp(partials);
+    if (db) {
+        hipLaunchKernelGGL(k_wgrad_db<WG_DB_CHUNK>, dim3((unsigned)L.n_chunks, (unsigned)(Kpad / 64)), dim3(256), 0, s, dy, pixels, Kpad, dbp);
+        POD_CHECK_LAUNCH();
+    }
+    main(wp);
+    POD_CHECK_LAUNCH();
+    const int64_t n_out = (int64_t)TAPS * K * C + (db ? K : 0);
+    hipLaunchKernelGGL(k_wgrad_reduce<TAPS>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, wp, (int)L.n_slices, dbp, (int)L.n_chunks, C, K, Kpad, dW, db);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}
+
+// Host.  pod_conv1x1_wgrad (GATHER = false) and pod_conv1x1_wgrad_strided (false at stride 1, true at 2) behind their geometry checks.
+static inline WgradLayout c1w_layout(int64_t pixels, int C, int K) {
+    const int sp = c1w_slice_pixels(pixels, C, K);
+    return wgrad_layout(pixels, (pixels + sp - 1) / sp, K, 1, C);
+}
+template <bool GATHER>
+static inline int c1w_launch(const float* x, const float* dy, int64_t pixels, int C, int K, const C1wGather g, const float* x_amax, const float* dy_amax, float* dW,
+                             float* db, float* partials, hipStream_t s) {
+    const WgradLayout L = c1w_layout(pixels, C, K);
+    return wgrad_launch<1>(x, dy, pixels, C, K, K, x_amax, dy_amax, L, partials, dW, db, s, [&](float* wp) {
+        hipLaunchKernelGGL(k_conv1x1_wgrad<GATHER>, dim3((unsigned)L.n_slices, (unsigned)(K / C1W_KT), (unsigned)((C + C1W_CT - 1) / C1W_CT)), dim3(256), 0, s, x, dy, pixels,
+                           C, K, c1w_slice_pixels(pixels, C, K), x_amax, dy_amax, wp, g);
+    });
+}
+
+// scale v where the gate's activation was positive, zero elsewhere: the backward of a ReLU (and dropout's 1 / (1 - p)) read off its stored output
+__device__ __forceinline__ f32x4 gate4(f32x4 v, const f32x4 g, const float scale = 1.0f) {
+    v.x = g.x > 0.f ? v.x * scale : 0.f;
+    v.y = g.y > 0.f ? v.y * scale : 0.f;
+    v.z = g.z > 0.f ? v.z * scale : 0.f;
+    v.w = g.w > 0.f ? v.w * scale : 0.f;
+    return v;
+}
+
+// out quad i = value(i) for the n4 quads of a launch, by grid stride; the abs-max of what is stored goes to `amax` (null: no record; the
+// publish is uniform: the whole workgroup calls this).  `out` may be what value() reads at quad i: the read comes first.
+template <class F>
+__device__ __forceinline__ void quad_pass(float* out, const int64_t n4, float* __restrict__ amax, F&& value) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    float m = 0.0f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 v = value(i);
+        reinterpret_cast<f32x4*>(out)[i] = v;
+        m = wino_absmax4(m, v);
+    }
+    if (amax) wino_publish_amax_block(amax, m);
+}
+
+// The same over a channels-last (H, W, 4 C4) map: value(i, c4, x, y) for quad c4 of pixel (y, x).
+template <class F>
+__device__ __forceinline__ void map_quad_pass(float* out, const int H, const int W, const int C4, float* __restrict__ amax, F&& value) {
+    quad_pass(out, (int64_t)H * W * C4, amax, [&](const int64_t i) {
+        const int c4 = (int)(i % C4);
+        const int64_t pix = i / C4;
+        return value(i, c4, (int)(pix % W), (int)(pix / W));
+    });
+}
+
+// Host: the check and launch the three map gathers share: `src` into the (out_pixels, C) map `out` behind an optional gate and addend of
+// out's shape (`out` may be the addend); H, W: the larger of the two maps; launch(grid) enqueues the kernel.
+template <class Launch>
+static inline int map_gather(const float* src, const float* gate, const float* add, const float* out, int32_t H, int32_t W, int32_t C, const float* amax,
+                             int64_t out_pixels, Launch&& launch) {
+    if (!src || !out || src == out || gate == out || H < 1 || W < 1 || H > 16384 || W > 16384 || C < 4 || (C & 3) != 0) return POD_E_INVALID;
+    if (!pod_aligned(16, src, gate, add, out) || !pod_aligned(4, amax)) return POD_E_INVALID;
+    launch(dim3(pod_grid_stride_blocks(out_pixels * (C / 4), 4096)));
+    POD_CHECK_LAUNCH();
+    return POD_OK;
 }
 
 }  // namespace pod

@@ -3,8 +3,8 @@ split over the processes, gradients averaged -- here by ONE gradient bucket and 
 
     * `GradBucket` owns one flat fp32 device buffer that holds every trained tensor's gradient (pod_grad_bucket_layout: each tensor on 16
       bytes) plus a 4-float tail.  `pack()` is ONE launch (K26, csrc/k26_grad_bucket.hip) that writes scale * grad, scale = 1 / world, for
-      all tensors through K25's chunk map; its descriptor table lives in pinned host memory twice and is guarded by events, exactly as
-      FusedSGD's.  `set_tail` puts the two loss scalars, scaled alike, behind the gradients: the rank mean of the log line (detectron2's
+      all tensors through K25's chunk map; its descriptor table is a sgd_step.TensorTable (pinned host memory, twice, guarded by
+      events).  `set_tail` puts the two loss scalars, scaled alike, behind the gradients: the rank mean of the log line (detectron2's
       reduce_dict) rides in the same collective and costs no synchronisation of its own.
     * `all_reduce_flat` is the collective: a SUM all-reduce of the flat buffer.  RCCL reduces the device buffer in place; any other backend
       (gloo: several ranks on one GPU, the CPU tests) cannot move device memory, so the buffer is staged through pinned host memory -- the
@@ -12,13 +12,13 @@ split over the processes, gradients averaged -- here by ONE gradient bucket and 
     * FusedSGD(grads_from=bucket) then steps straight from the bucket's slices (sgd_step.py).
 The padding floats between tensors are zeroed once and never written: a sum of zeros stays zero.  GPU only for the pack: a table
 pod_grad_pack refuses, or a trained tensor without a gradient, raises hip.PodError."""
-import ctypes
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
 from . import hip
+from .sgd_step import TensorTable
 
 TAIL = 4                                               # floats behind the gradients: loss_cls, loss_box_reg, two spare (16 bytes)
 
@@ -112,24 +112,12 @@ class GradBucket:
         self._offsets_dev = offsets.to(dev)
         self.host_staged = self.world > 1 and host_staged(self.flat, group)
         self._staging = torch.empty(self.flat.shape, dtype=torch.float32).pin_memory() if self.host_staged else None
-        # the pack's table, as FusedSGD's: pinned, twice, the copy not in flight is the one a pack fills.  The pack reads grad and n; w is the
-        # weight and `momentum` names the slice the gradient lands in, which makes it a table pod_sgd_chunk_map accepts
-        nbytes = ctypes.sizeof(hip.PodSgdTensor) * n
-        self._tables, self._pinned, self._events, self._turn = [], [], [None, None], 0
-        for _ in range(2):
-            host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-            table = (hip.PodSgdTensor * n).from_address(host.data_ptr())
-            for i, (d, e) in enumerate(zip(table, self.entries)):
-                d.w, d.grad, d.momentum, d.n = e.w.data_ptr(), None, self.slice_ptr(i), e.w.numel()
-            self._pinned.append(host)
-            self._tables.append(table)
-        self._n_chunks = int(lib.pod_sgd_chunk_map(self._tables[0], n, None, 0))
-        if self._n_chunks < 0:
-            raise hip.PodError("pod_sgd_chunk_map refused the parameter table (a null, misaligned or aliased tensor)")
-        chunk_map = torch.zeros((max(1, self._n_chunks), 2), dtype=torch.int32)
-        assert lib.pod_sgd_chunk_map(self._tables[0], n, chunk_map.data_ptr(), self._n_chunks) == self._n_chunks
-        self._map_dev = chunk_map.to(dev)
-        self._table_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        # the pack reads grad and n of its table; w is the weight and `momentum` names the slice the gradient lands in, which makes it a table
+        # pod_sgd_chunk_map accepts
+
+        def fill(i, d, e):
+            d.w, d.grad, d.momentum, d.n = e.w.data_ptr(), None, self.slice_ptr(i), e.w.numel()
+        self.table = TensorTable(self.entries, dev, fill)
 
     def slice_ptr(self, i: int) -> int:
         """Device address of entry i's gradient inside the bucket (16-byte aligned)."""
@@ -142,25 +130,15 @@ class GradBucket:
 
     def pack(self) -> None:
         """ONE launch: every entry's gradient, times 1 / world, into its slice.  The entries' .grad stay (the caller clears them)."""
-        k = self._turn
-        self._turn ^= 1
-        if self._events[k] is not None:
-            self._events[k].synchronize()              # the copy enqueued from this table two packs ago has long run
-        for i, (d, e) in enumerate(zip(self._tables[k], self.entries)):
-            g = e.grad_of.grad
-            if g is None:
-                raise hip.PodError("GradBucket: trained tensor {} of shape {} has no gradient this step; under data parallelism every rank "
-                                   "reduces every tensor".format(i, tuple(e.w.shape)))
-            if not (g.is_contiguous() and g.dtype == torch.float32 and g.device == self.device and tuple(g.shape) == tuple(e.w.shape)):
-                raise hip.PodError("GradBucket: a gradient that is not a contiguous fp32 tensor of its weight's shape on its GPU")
-            d.grad = g.data_ptr()
+        table = self.table.begin()
+        self.table.refresh_grads(table, "GradBucket", require_all=True)
         with torch.cuda.device(self.device):
-            hip.check(hip.load().pod_grad_pack(self._tables[k], self._table_dev.data_ptr(), len(self.entries), self._map_dev.data_ptr(), self._n_chunks,
-                                               self._offsets_dev.data_ptr(), self.flat.data_ptr(), self.floats, self.scale, hip.current_stream()),
-                      "pod_grad_pack")
-            if self._events[k] is None:
-                self._events[k] = torch.cuda.Event()
-            self._events[k].record()
+            hip.check(hip.load().pod_grad_pack(table, *self.table.launch_args(), *self.pack_args(), self.scale, hip.current_stream()), "pod_grad_pack")
+            self.table.end()
+
+    def pack_args(self) -> tuple:
+        """What pod_grad_pack takes of the bucket: the tensors' offsets on the device, the buffer, its gradient floats."""
+        return self._offsets_dev.data_ptr(), self.flat.data_ptr(), self.floats
 
     def set_tail(self, loss_cls: torch.Tensor, loss_box_reg: torch.Tensor) -> None:
         """The two loss scalars (device tensors), times 1 / world, into the tail -- from the device, no read-back."""

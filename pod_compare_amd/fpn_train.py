@@ -8,7 +8,7 @@ they are of):
                      gate = p6, add = the gradient p6 has from the head)
     p6               dW, db = pod_conv1x1_wgrad(cols(c5), dP6) -- c5 is the frozen backbone's: no input gradient
     output convs     dW, db = pod_conv3x3_wgrad(l_i, dP_i) (K22); dL_i = the GEMM of dP_i's patch matrix with the flipped, transposed filter
-                     (head_train.input_grad_gemm)
+                     (head_train.backward_gemm)
     top-down         dL4 += up2_sum(dL3), dL5 += up2_sum(dL4) (pod_upsample2_sum_cl), l3 first
     laterals         dW, db = pod_conv1x1_wgrad(c_i, dL_i)
     below            only when the maps c3 - c5 require it (the ResNet trains: resnet_train.py): dC_i = dL_i W_lateral_i, the GEMM with the
@@ -19,8 +19,8 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import amax, conv1x1, conv_forms, hip, modeling, wgrad, wino
-from .head_train import input_grad_gemm, patch_matrix
+from . import amax, conv1x1, hip, modeling, wgrad, wino
+from .head_train import backward_gemm, conv_params, flat_grads, flipped3x3, patch_matrix, transposed1x1, transposed3x3s2
 
 
 def fpn_convs(fpn) -> list:
@@ -36,33 +36,6 @@ def _require(fpn) -> None:
     if not ok:
         raise hip.PodError("fpn_forward_train: this FPN has no HIP training path (three biased 1x1 laterals of Cin % 16 == 0, 3x3 output convs and "
                            "stride-2 p6 / p7 of one width in (64, 128, 256, 512), the split kernels selected)")
-
-
-def _dcols_gemm(conv):
-    """dcols = dY W9, W9 (K, ty, tx, Cin) the stride-2 conv's filter in the patch matrix's column order: a GEMM with the transposed filter on
-    pod_conv1x1_split, split once and cached by the weight's version (conv_forms.derived)."""
-    def make(c):
-        K, C = c.out_channels, c.in_channels
-        w9 = c.weight.detach().permute(0, 2, 3, 1).reshape(K, 9 * C)
-        try:
-            return conv1x1.Conv1x1(w9.t().reshape(9 * C, K, 1, 1).contiguous(), None, 1)
-        except ValueError as e:
-            raise hip.PodError("FPN backward: the input gradient of a stride-2 {} -> {} conv has no pod_conv1x1_split form ({})".format(C, K, e))
-    return conv_forms.derived(conv, "_pod_dcols_gemm", make)
-
-
-def transposed_gemm(conv, negated: bool = False):
-    """dX = dY W for a 1x1 conv's (K, C) filter: the GEMM with the transposed filter on pod_conv1x1_split, split once and cached by the
-    weight's version (conv_forms.derived).  Called as gemm(dY (pixels, K), pixels, 1[, residual=...]) -> (pixels, C).  negated: the same
-    with -W (every f16 term and every product the exact negative: what differs from -(dY W) is the accumulation's error alone)."""
-    def make(c):
-        K, C = c.out_channels, c.in_channels
-        wt = c.weight.detach().reshape(K, C).t().reshape(C, K, 1, 1).contiguous()
-        try:
-            return conv1x1.Conv1x1(-wt if negated else wt, None, 1)
-        except ValueError as e:
-            raise hip.PodError("backward: the input gradient of a 1x1 {} -> {} conv has no pod_conv1x1_split form ({})".format(C, K, e))
-    return conv_forms.derived(conv, "_pod_dx_t_neg" if negated else "_pod_dx_t", make)
 
 
 def _cols(x: torch.Tensor, h: int, w: int, relu: bool, out: torch.Tensor) -> None:
@@ -123,11 +96,8 @@ class _FpnTrain(torch.autograd.Function):
         p6s = [s["p6"] for s in saved]
         dW, db = wgrad.conv1x1_wgrad(_batched_cols(p6s, h6, w6, True), dP[4])
         grads[fpn.p7] = (dW.view(K, 3, 3, K).permute(0, 3, 1, 2).contiguous(), db)
-        dcols = _dcols_gemm(fpn.p7)(dP[4], B * h7 * w7, 1)
-        rec, n6, n7 = amax.word(dev), h6 * w6, h7 * w7
-        for b in range(B):
-            wgrad.col2im3x3s2_cl(dcols[b * n7:(b + 1) * n7], h6, w6, gate=p6s[b], add=dP[3][b * n6:(b + 1) * n6], out=dP[3][b * n6:(b + 1) * n6], record=rec)
-        amax.attach(dP[3], rec)
+        dcols = backward_gemm(fpn.p7, transposed3x3s2)(dP[4], B * h7 * w7, 1)
+        wgrad.over_images(B, dP[3], lambda b, rows, rec: wgrad.col2im3x3s2_cl(rows(dcols), h6, w6, gate=p6s[b], add=rows(dP[3]), out=rows(dP[3]), record=rec))
         # p6 on c5
         C5 = fpn.p6.in_channels
         dW, db = wgrad.conv1x1_wgrad(_batched_cols([s["c"][2] for s in saved], h5, w5, False), dP[3])
@@ -137,14 +107,11 @@ class _FpnTrain(torch.autograd.Function):
         for i in range(3):
             level, conv = [hw[i]], fpn.output[i]
             grads[conv] = wgrad.conv3x3_wgrad(_stacked([s["l"][i] for s in saved]), dP[i], level, B, K)
-            dL.append(input_grad_gemm(conv)(patch_matrix(dP[i], level, B), int(dP[i].shape[0]), 1))
+            dL.append(backward_gemm(conv, flipped3x3)(patch_matrix(dP[i], level, B), int(dP[i].shape[0]), 1))
         # top-down, l3 first: a summed lateral's gradient also reaches the coarser one it was upsampled from
         for i in (0, 1):
-            (h, w), rec = hw[i], amax.word(dev)
-            n, nt = h * w, ((h + 1) // 2) * ((w + 1) // 2)
-            for b in range(B):
-                wgrad.upsample2_sum_cl(dL[i][b * n:(b + 1) * n], h, w, dL[i + 1][b * nt:(b + 1) * nt], record=rec)
-            amax.attach(dL[i + 1], rec)
+            (h, w), child, top = hw[i], dL[i], dL[i + 1]
+            wgrad.over_images(B, top, lambda b, rows, rec: wgrad.upsample2_sum_cl(rows(child), h, w, rows(top), record=rec))
         # laterals
         for i in range(3):
             dW, db = wgrad.conv1x1_wgrad(_stacked([s["c"][i] for s in saved]), dL[i])
@@ -154,20 +121,16 @@ class _FpnTrain(torch.autograd.Function):
         if any(ctx.needs_input_grad[3:3 + 3 * B]):
             for i in range(3):
                 (h, w), n = hw[i], hw[i][0] * hw[i][1]
-                dC = transposed_gemm(fpn.lateral[i])(dL[i], B * n, 1)
+                dC = backward_gemm(fpn.lateral[i], transposed1x1)(dL[i], B * n, 1)
                 if i == 2:
-                    dcols, rec = _dcols_gemm(fpn.p6)(dP[3], B * n6, 1), amax.word(dev)
-                    for b in range(B):
-                        wgrad.col2im3x3s2_cl(dcols[b * n6:(b + 1) * n6], h, w, add=dC[b * n:(b + 1) * n], out=dC[b * n:(b + 1) * n], record=rec)
-                    amax.attach(dC, rec)
+                    dcols = backward_gemm(fpn.p6, transposed3x3s2)(dP[3], B * h6 * w6, 1)
+                    wgrad.over_images(B, dC, lambda b, rows, rec: wgrad.col2im3x3s2_cl(rows(dcols), h, w, add=rows(dC), out=rows(dC), record=rec))
                 for b in range(B):
                     d_maps[3 * b + i] = dC[b * n:(b + 1) * n]
         tap = getattr(fpn, "train_tap", None)               # tests: a dict that receives what this pass hands below the FPN
         if tap is not None:
             tap["d_maps"] = list(d_maps)
-        flat = []
-        for conv in fpn_convs(fpn):
-            flat += list(grads[conv])
+        flat = flat_grads(fpn_convs(fpn), grads)
         assert len(flat) == ctx.n_params
         ctx.state = None
         return (None, None, None) + tuple(d_maps) + tuple(flat)
@@ -180,12 +143,9 @@ def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int
     feats = [list(f) for f in feats]
     if not feats or any(len(f) != 3 for f in feats):
         raise hip.PodError("fpn_forward_train: per image the three maps (c3, h, w), (c4, h, w), (c5, h, w)")
-    dev = feats[0][0][0].device
-    for f in feats:
-        for (t, h, w), (_, h0, w0), conv in zip(f, feats[0], fpn.lateral):
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
-                    and tuple(t.shape) == (int(h) * int(w), conv.in_channels) and (int(h), int(w)) == (int(h0), int(w0))):
-                raise hip.PodError("fpn_forward_train runs on contiguous fp32 channels-last (h * w, C) maps of one size on one GPU: there is no CPU path")
+    dev = getattr(feats[0][0][0], "device", None)
+    for i, conv in enumerate(fpn.lateral):
+        wgrad.require_maps("fpn_forward_train", [f[i] for f in feats], conv.in_channels, dev)
     _require(fpn)
     (h3, w3), (h4, w4), (h5, w5) = [(int(h), int(w)) for _, h, w in feats[0]]
     for (ht, wt), (h, w) in (((h4, w4), (h3, w3)), ((h5, w5), (h4, w4))):
@@ -193,12 +153,9 @@ def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int
             raise hip.PodError("fpn_forward_train: a top-down step from {} x {} to {} x {} is not a factor of two".format(ht, wt, h, w))
     if fpn.p6.weight.device != dev:
         raise hip.PodError("fpn_forward_train: the FPN is on {}, the maps on {}".format(fpn.p6.weight.device, dev))
-    params = []
-    for c in fpn_convs(fpn):
-        params += [c.weight, c.bias]
     with torch.cuda.device(dev):
         maps = [t for f in feats for t, _, _ in f]
-        return list(_FpnTrain.apply(fpn, feats, len(maps), *maps, *params))
+        return list(_FpnTrain.apply(fpn, feats, len(maps), *maps, *conv_params(fpn_convs(fpn))))
 
 
 def backbone_maps(model, image: torch.Tensor):

@@ -33,20 +33,45 @@ def transposed_weight(weight: torch.Tensor) -> torch.Tensor:
     return wt
 
 
-def input_grad_gemm(conv, negated: bool = False):
-    """The conv's input gradient as a GEMM: W' laid out (C, ty, tx, Kpad) and split once for pod_conv1x1_split (conv1x1.Conv3x3S2's form,
-    stride 1), cached by the weight's version as conv_forms.wino_of caches the forward filter.  negated: the same with -W' (every f16 term
-    and product the exact negative; resnet_train.centred uses the pair)."""
+def flipped3x3(conv) -> torch.Tensor:
+    """Layout of backward_gemm: a 3x3 / stride-1 conv's W' as (C, ty, tx, Kpad) rows, against the patch matrix of dZ."""
+    wt = transposed_weight(conv.weight)
+    return wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1)
+
+
+def transposed1x1(conv) -> torch.Tensor:
+    """Layout of backward_gemm: dX = dY W for a 1x1 conv's (K, C) filter."""
+    return conv.weight.detach().reshape(conv.out_channels, conv.in_channels).t().reshape(conv.in_channels, conv.out_channels, 1, 1)
+
+
+def transposed3x3s2(conv) -> torch.Tensor:
+    """Layout of backward_gemm: dcols = dY W9, W9 (K, ty, tx, Cin) a stride-2 conv's filter in the patch matrix's column order."""
+    return conv.weight.detach().permute(0, 2, 3, 1).reshape(conv.out_channels, -1).t().reshape(9 * conv.in_channels, conv.out_channels, 1, 1)
+
+
+def backward_gemm(conv, layout, negated: bool = False):
+    """The conv's input gradient as a GEMM on pod_conv1x1_split: layout(conv) -- flipped3x3, transposed1x1 or transposed3x3s2 -- is the
+    rearranged (Cin', Cout', 1, 1) filter, split once and cached by the weight's version (conv_forms.derived), one form per layout and sign.
+    Called as gemm(dY (pixels, Cin'), pixels, 1[, residual=...]) -> (pixels, Cout').  negated: the same with the negated filter (every f16
+    term and product the exact negative: the accumulation's error alone differs; resnet_train.centred uses the pair)."""
     def make(c):
-        wt = transposed_weight(c.weight)
-        if negated:
-            wt = -wt
+        w = layout(c).contiguous()
         try:
-            return conv1x1.Conv1x1(wt.permute(0, 2, 3, 1).reshape(wt.shape[0], 9 * wt.shape[1], 1, 1).contiguous(), None, 1)
+            return conv1x1.Conv1x1(-w if negated else w, None, 1)
         except ValueError as e:
-            raise hip.PodError("head backward: the input gradient of a {} -> {} conv has no pod_conv1x1_split form ({})".format(
-                c.in_channels, c.out_channels, e))
-    return conv_forms.derived(conv, "_pod_dx_gemm_neg" if negated else "_pod_dx_gemm", make)
+            raise hip.PodError("backward: the input gradient ({}) of a {} -> {} conv has no pod_conv1x1_split form ({})".format(
+                layout.__name__, c.in_channels, c.out_channels, e))
+    return conv_forms.derived(conv, "_pod_bwd_{}{}".format(layout.__name__, "_neg" if negated else ""), make)
+
+
+def conv_params(convs, bias: bool = True) -> list:
+    """The convs' parameters in the order they enter an autograd function (bias=False: the weights alone)."""
+    return [p for c in convs for p in ((c.weight, c.bias) if bias else (c.weight,))]
+
+
+def flat_grads(convs, grads: dict) -> list:
+    """grads[conv] = one gradient per parameter conv_params lists, flattened in its order."""
+    return [g for c in convs for g in grads[c]]
 
 
 def patch_matrix(dz: torch.Tensor, levels, B: int) -> torch.Tensor:
@@ -106,7 +131,7 @@ class _HeadTrain(torch.autograd.Function):
         need_x = ctx.needs_input_grad[3]
 
         def input_grad(conv, dz):
-            return input_grad_gemm(conv)(patch_matrix(dz, levels, B), pixels, 1)
+            return backward_gemm(conv, flipped3x3)(patch_matrix(dz, levels, B), pixels, 1)
 
         d_trunk = [None, None]
         for (conv, sid), g in zip(preds, g_planes):
@@ -127,9 +152,7 @@ class _HeadTrain(torch.autograd.Function):
                     d = input_grad(sub[l], dz)
             if need_x:
                 dx0 = d if dx0 is None else dx0 + d
-        flat = []
-        for conv in head_convs(head):
-            flat += list(grads[conv])
+        flat = flat_grads(head_convs(head), grads)
         assert len(flat) == ctx.n_params
         ctx.state = None
         return (None, None, None, dx0) + tuple(flat)
@@ -152,10 +175,7 @@ def forward_train(head, features: Sequence[torch.Tensor], anchors: Optional[List
     if any(int(f.shape[0]) != B or int(f.shape[1]) != C or f.device != f0.device for f in features):
         raise hip.PodError("head.forward_train: every level holds the same images and channels")
     x0 = torch.cat([f.permute(0, 2, 3, 1).reshape(-1, C) for f in features]).contiguous()      # channels-last, level-major (autograd sees it)
-    params = []
-    for c in convs:
-        params += [c.weight, c.bias]
-    flats = _HeadTrain.apply(head, levels, B, x0, *params)
+    flats = _HeadTrain.apply(head, levels, B, x0, *conv_params(convs))
     A = head.num_anchors
 
     def per_level(flat, K):

@@ -6,7 +6,7 @@ Forward: Bottleneck.forward_cl's own launches, per image, unchanged; the input x
 every block are kept.  Backward, on the B images at once, from the last block of res5 down to the first block of res3:
     the output gate  dZ = (dY from above + dC from the FPN) (y > 0)    pod_relu_dropout_backward at p = 0, or the scatter below
     conv3            dW3 = pod_conv1x1_wgrad_strided(b, dZ) (K24); dB = dZ W3 on pod_conv1x1_split with the transposed filter, gated on b > 0
-    conv2            dW2 = pod_conv3x3_wgrad(a, dB) (K22); dA = the GEMM of dB's patch matrix (head_train.input_grad_gemm), gated on a > 0
+    conv2            dW2 = pod_conv3x3_wgrad(a, dB) (K22); dA = the GEMM of dB's patch matrix (head_train.backward_gemm), gated on a > 0
     conv1            dW1 = pod_conv1x1_wgrad_strided(x, dA, the block's stride)
     identity block   dX = dA W1 + dZ, dZ as the GEMM's residual
     conv shortcut    dWs = pod_conv1x1_wgrad_strided(x, dZ, 2); the half-resolution dA W1 + dZ Ws is one GEMM with the other's result as
@@ -22,9 +22,9 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import nn
 
-from . import amax, hip, modeling, wgrad, wino
-from .fpn_train import _stacked, transposed_gemm
-from .head_train import input_grad_gemm, patch_matrix
+from . import hip, modeling, wgrad, wino
+from .fpn_train import _stacked
+from .head_train import backward_gemm, conv_params, flat_grads, flipped3x3, patch_matrix, transposed1x1
 
 STAGES = ("res3", "res4", "res5")
 
@@ -94,16 +94,16 @@ def res2_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
         return model.bottom_up.forward_cl(None, frame=(image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded), stop_after_res2=True)
 
 
-def centred(gemm, conv, d: torch.Tensor, n: int, residual=None) -> torch.Tensor:
-    """d W (+ residual) for one of the backward's input-gradient GEMMs (gemm = transposed_gemm or input_grad_gemm).  The matrix cores'
+def centred(layout, conv, d: torch.Tensor, n: int, residual=None) -> torch.Tensor:
+    """d W (+ residual) for one of the backward's input-gradient GEMMs (head_train.backward_gemm of `layout`).  The matrix cores'
     accumulation leaves every pod_conv1x1_split result an error whose MEAN is not zero and does not depend on the operands' signs
     (measured: -0.05 .. -0.19 of its rms; profiles/resnet_backward.md).  One launch's is far below fp32's own error, but it is the same
     for every pixel of a channel, the shortcuts hand it down unchanged, 13 blocks' add up, and a weight gradient sums it over every pixel
     against non-negative activations.  So the GEMM runs on W and on -W -- the f16 terms and products of the second are the exact
     negatives of the first's -- and half their difference keeps the product and drops what the two have in common:
     P = d W + r + e, M = -d W + e, (P - M + r) / 2 = d W + r."""
-    y = gemm(conv)(d, n, 1, residual=residual)
-    y.sub_(gemm(conv, negated=True)(d, n, 1))
+    y = backward_gemm(conv, layout)(d, n, 1, residual=residual)
+    y.sub_(backward_gemm(conv, layout, negated=True)(d, n, 1))
     if residual is not None:
         y.add_(residual)
     return y.mul_(0.5)
@@ -169,39 +169,36 @@ class _BlocksTrain(torch.autograd.Function):
             keep_dz(i, "z", dz)
             # conv3
             dW, _ = wgrad.conv1x1_wgrad_strided(b_, dz, B, h1, w1, 1)
-            grads[c3] = dW.view(c3.weight.shape)
-            db_ = wgrad.relu_dropout_backward(b_, centred(transposed_gemm, c3, dz, n1), 0.0)
+            grads[c3] = (dW.view(c3.weight.shape),)
+            db_ = wgrad.relu_dropout_backward(b_, centred(transposed1x1, c3, dz, n1), 0.0)
             keep_dz(i, "b", db_)
             # conv2 (K22's bias gradient is discarded: the bias is FrozenBN's shift)
             level = [(h1, w1)]
-            grads[c2] = wgrad.conv3x3_wgrad(a, db_, level, B, c2.out_channels)[0]
-            da = wgrad.relu_dropout_backward(a, centred(input_grad_gemm, c2, patch_matrix(db_, level, B), n1), 0.0)
+            grads[c2] = wgrad.conv3x3_wgrad(a, db_, level, B, c2.out_channels)[:1]
+            da = wgrad.relu_dropout_backward(a, centred(flipped3x3, c2, patch_matrix(db_, level, B), n1), 0.0)
             keep_dz(i, "a", da)
             # conv1 and the shortcut
             dW, _ = wgrad.conv1x1_wgrad_strided(x, da, B, h, w, stride)
-            grads[c1] = dW.view(c1.weight.shape)
+            grads[c1] = (dW.view(c1.weight.shape),)
             if block.shortcut is not None:
                 sc = _conv_of(block.shortcut)
                 dW, _ = wgrad.conv1x1_wgrad_strided(x, dz, B, h, w, stride)
-                grads[sc] = dW.view(sc.weight.shape)
+                grads[sc] = (dW.view(sc.weight.shape),)
             if i == 0 and not need_x:
                 break                                       # nothing trains below the first block
             if block.shortcut is None:
-                d, gated = centred(transposed_gemm, c1, da, n1, residual=dz), False
+                d, gated = centred(transposed1x1, c1, da, n1, residual=dz), False
                 continue
             # the half-resolution dA W1 + dZ Ws, expanded per image behind the gate of the block below, with what its output already carries
-            half = centred(transposed_gemm, c1, da, n1, residual=centred(transposed_gemm, sc, dz, n1))
-            n, nh, below = h * w, h1 * w1, from_above(i - 1) if i else None
-            d, rec = torch.empty((B * n, c1.in_channels), dtype=torch.float32, device=dev), amax.word(dev)
-            for b in range(B):
-                wgrad.subsample2_scatter_cl(half[b * nh:(b + 1) * nh], h, w, gate=saved[b][i]["x"] if i else None, add=None if below is None else below[b],
-                                            out=d[b * n:(b + 1) * n], record=rec)
-            amax.attach(d, rec)
-            gated = True
+            half = centred(transposed1x1, c1, da, n1, residual=centred(transposed1x1, sc, dz, n1))
+            below = from_above(i - 1) if i else None
+            d, gated = torch.empty((B * h * w, c1.in_channels), dtype=torch.float32, device=dev), True
+            wgrad.over_images(B, d, lambda b, rows, rec: wgrad.subsample2_scatter_cl(
+                rows(half), h, w, gate=saved[b][i]["x"] if i else None, add=None if below is None else below[b], out=rows(d), record=rec))
         if need_x:                                          # (the input is a leaf here, whatever made it: no gate of this pass's)
             n = int(d.shape[0]) // B
             dx = [d[b * n:(b + 1) * n] for b in range(B)]
-        flat = [grads[c] for block in blocks for c in block_convs(block)]
+        flat = flat_grads([c for block in blocks for c in block_convs(block)], grads)
         assert len(flat) == ctx.n_params
         ctx.state = None
         return (None, None, None, None) + tuple(dx or [None] * B) + tuple(flat)
@@ -214,17 +211,14 @@ def blocks_forward_train(blocks: Sequence, maps: Sequence[Tuple[torch.Tensor, in
     blocks, maps = list(blocks), [tuple(m) for m in maps]
     if not blocks or not maps or any(len(m) != 3 for m in maps):
         raise hip.PodError("blocks_forward_train: at least one block, and per image the (x, h, w) it starts from")
+    wgrad.require_maps("blocks_forward_train", maps)
     t0, h0, w0 = maps[0]
-    for t, h, w in maps:
-        if not (torch.is_tensor(t) and t.is_cuda and t.device == t0.device and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
-                and tuple(t.shape) == (int(h) * int(w), int(t0.shape[1])) and (int(h), int(w)) == (int(h0), int(w0))):
-            raise hip.PodError("blocks_forward_train runs on contiguous fp32 channels-last (h * w, C) maps of one size on one GPU: there is no CPU path")
     _require(blocks)
     first = _conv_of(blocks[0].conv1)
     if first.in_channels != int(t0.shape[1]) or first.weight.device != t0.device:
         raise hip.PodError("blocks_forward_train: the first block takes {} channels on {}, the maps have {} on {}".format(
             first.in_channels, first.weight.device, int(t0.shape[1]), t0.device))
-    weights = [c.weight for block in blocks for c in block_convs(block)]
+    weights = conv_params([c for block in blocks for c in block_convs(block)], bias=False)
     with torch.cuda.device(t0.device):
         flat = _BlocksTrain.apply(blocks, (int(h0), int(w0)), tap, len(maps), *[t for t, _, _ in maps], *weights)
     hw, (h, w) = [], (int(h0), int(w0))

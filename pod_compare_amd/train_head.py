@@ -65,7 +65,7 @@ from .anchors import padded_size as _padded_size, resize_shortest_edge
 from .config import setup_config
 from .data_parallel import GradBucket, broadcast_tensors, gather_objects, rank_slice
 from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
-from .head_train import head_convs
+from .head_train import conv_params, head_convs
 from .resnet_train import FoldedMasters, res2_maps, resnet_forward_train, trainable_convs, unfolded_pairs
 from .probabilistic_inference import build_model
 from .sgd_step import FusedSGD, SgdEntry
@@ -106,9 +106,9 @@ class HeadTrainer:
             raise ValueError("data_parallel needs fused_step: the averaged gradients are stepped from the bucket by pod_sgd_step")
         self.model, self.train_backbone = model, bool(train_backbone)
         self.train_fpn = bool(train_fpn) or self.train_backbone
-        self.params = [p for c in head_convs(model.head) for p in (c.weight, c.bias)]
+        self.params = conv_params(head_convs(model.head))
         if self.train_fpn:
-            self.params += [p for c in fpn_convs(model.fpn) for p in (c.weight, c.bias)]
+            self.params += conv_params(fpn_convs(model.fpn))
         for p in model.parameters():
             p.requires_grad_(False)               # what is frozen (the backbone; the FPN unless train_fpn) has no backward pass here
         for p in self.params:

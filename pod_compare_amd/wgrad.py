@@ -21,10 +21,8 @@ def _level_array(levels: Sequence[Tuple[int, int]]):
 def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, levels: Sequence[Tuple[int, int]], copies: int, K: int):
     """x (pixels, C), dy (pixels, Kpad): channels-last, `copies` images per level, level-major (wino.level_pixel_offsets).  Returns
     (dW (K, C, 3, 3), db (K,)) in fp32.  The operands' abs-max records are their producers' (pod_compare_amd.amax), else computed now."""
-    for name, t in (("x", x), ("dy", dy)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
-            raise hip.PodError("pod_conv3x3_wgrad: {} must be a contiguous fp32 (pixels, channels) tensor on the GPU, got {} {} on {}".format(
-                name, t.dtype, tuple(t.shape), t.device))
+    _cl("pod_conv3x3_wgrad", "x", x)
+    _cl("pod_conv3x3_wgrad", "dy", dy)
     pixels, C, Kpad = int(copies) * sum(h * w for h, w in levels), int(x.shape[1]), int(dy.shape[1])
     if int(x.shape[0]) != pixels or int(dy.shape[0]) != pixels:
         raise hip.PodError("pod_conv3x3_wgrad: the geometry holds {} pixels, x has {} and dy {}".format(pixels, x.shape[0], dy.shape[0]))
@@ -61,52 +59,81 @@ def _cl(name: str, what: str, t: torch.Tensor) -> None:
             name, what, t.dtype, tuple(t.shape), t.device))
 
 
+def _c1w(name: str, x: torch.Tensor, dy: torch.Tensor, geometry: tuple, bias: bool, refusal: str):
+    """The allocation and call behind conv1x1_wgrad and conv1x1_wgrad_strided: entry `name` takes `geometry` between dy and C; what
+    `name`_partials(*geometry, C, K) answers with 0, the entry refuses: PodError(refusal)."""
+    C, K, lib = int(x.shape[1]), int(dy.shape[1]), hip.load()
+    n = int(getattr(lib, name + "_partials")(*geometry, C, K))
+    if n <= 0:
+        raise hip.PodError(refusal)
+    partials = torch.empty(n, dtype=torch.float32, device=x.device)
+    dW = torch.empty((K, C), dtype=torch.float32, device=x.device)
+    db = torch.empty((K,), dtype=torch.float32, device=x.device) if bias else None
+    with torch.cuda.device(x.device):
+        hip.check(getattr(lib, name)(x.data_ptr(), dy.data_ptr(), *geometry, C, K, amax.of(x).data_ptr(), amax.of(dy).data_ptr(), dW.data_ptr(), hip.ptr(db),
+                                     partials.data_ptr(), hip.current_stream()), name)
+    return dW, db
+
+
 def conv1x1_wgrad(x: torch.Tensor, dy: torch.Tensor, bias: bool = True):
     """x (pixels, C), dy (pixels, K), channels-last: (dW (K, C), db (K,) or None) in fp32, dW[k][c] = sum_p dy[p][k] x[p][c].  The weight
     gradient of a 1x1 convolution and, on the patch matrix of pod_im2col3x3s2_cl, of a 3x3 / stride-2 one laid out (K, ty, tx, Cin).  The
     operands' abs-max records are their producers' (pod_compare_amd.amax), else computed now."""
     _cl("pod_conv1x1_wgrad", "x", x)
     _cl("pod_conv1x1_wgrad", "dy", dy)
-    pixels, C, K = int(x.shape[0]), int(x.shape[1]), int(dy.shape[1])
+    pixels = int(x.shape[0])
     if int(dy.shape[0]) != pixels or dy.device != x.device:
         raise hip.PodError("pod_conv1x1_wgrad: x has {} pixels on {}, dy {} on {}".format(pixels, x.device, dy.shape[0], dy.device))
-    lib = hip.load()
-    n = int(lib.pod_conv1x1_wgrad_partials(pixels, C, K))
-    if n <= 0:
-        raise hip.PodError("pod_conv1x1_wgrad: pixels >= 1, C % 16 == 0, C <= 18432, K % 64 == 0 and K <= 512 required, got pixels={} C={} K={}".format(
-            pixels, C, K))
-    partials = torch.empty(n, dtype=torch.float32, device=x.device)
-    dW = torch.empty((K, C), dtype=torch.float32, device=x.device)
-    db = torch.empty((K,), dtype=torch.float32, device=x.device) if bias else None
-    with torch.cuda.device(x.device):
-        hip.check(lib.pod_conv1x1_wgrad(x.data_ptr(), dy.data_ptr(), pixels, C, K, amax.of(x).data_ptr(), amax.of(dy).data_ptr(), dW.data_ptr(),
-                                        hip.ptr(db), partials.data_ptr(), hip.current_stream()), "pod_conv1x1_wgrad")
-    return dW, db
+    return _c1w("pod_conv1x1_wgrad", x, dy, (pixels,), bias,
+                "pod_conv1x1_wgrad: pixels >= 1, C % 16 == 0, C <= 18432, K % 64 == 0 and K <= 512 required, got pixels={} C={} K={}".format(
+                    pixels, x.shape[1], dy.shape[1]))
 
 
-def _record_of(out: torch.Tensor, record: Optional[torch.Tensor]) -> torch.Tensor:
-    """The record a gather max'es into: the caller's (one record over the images of a batch: the caller attaches it) or a fresh one."""
-    return amax.produced(out) if record is None else record
+def _map_gather(name: str, src: torch.Tensor, h: int, w: int, C: int, rule: str, gate, add, out, record) -> torch.Tensor:
+    """The call behind col2im3x3s2_cl and subsample2_scatter_cl: entry `name` gathers the ho * wo rows of src, which hold C channels each
+    (0: they cannot; `rule` names what they should be), into dx (h * w, C).  record: the caller's (one over a batch's images, which the
+    caller attaches: over_images), None = dx's own."""
+    h, w = int(h), int(w)
+    rows = ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1)
+    if h < 1 or w < 1 or C < 1 or C % 4 or int(src.shape[0]) != rows:
+        raise hip.PodError("{}: a {} x {} map has {} with C % 4 == 0, got {}".format(name, h, w, rule.format(rows), tuple(src.shape)))
+    dx = torch.empty((h * w, C), dtype=torch.float32, device=src.device) if out is None else out
+    for what, t in (("gate", gate), ("add", add), ("dx", dx)):
+        if t is not None:
+            _cl(name, what, t)
+            if tuple(t.shape) != (h * w, C) or t.device != src.device:
+                raise hip.PodError("{}: {} must be ({}, {}) on {}, got {} on {}".format(name, what, h * w, C, src.device, tuple(t.shape), t.device))
+    with torch.cuda.device(src.device):
+        hip.check(getattr(hip.load(), name)(src.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), h, w, C, (amax.produced(dx) if record is None else record).data_ptr(),
+                                            hip.current_stream()), name)
+    return dx
+
+
+def over_images(B: int, out: torch.Tensor, op) -> torch.Tensor:
+    """A per-image gather on the B images of a batch under ONE abs-max record, attached to `out`: op(b, rows, record) for every image b;
+    rows(t): image b's rows of a tensor that stacks the B images."""
+    rec = amax.word(out.device)
+    for b in range(B):
+        op(b, lambda t: t[b * (int(t.shape[0]) // B):(b + 1) * (int(t.shape[0]) // B)], rec)
+    return amax.attach(out, rec)
+
+
+def require_maps(who: str, maps, channels: Optional[int] = None, device=None) -> None:
+    """maps: per image the (t, h, w) a training pass starts from (channels, device: None = the first map's)."""
+    t0, h0, w0 = maps[0]
+    for t, h, w in maps:
+        if not (torch.is_tensor(t) and torch.is_tensor(t0) and t.is_cuda and t.device == (t0.device if device is None else device) and t.dtype == torch.float32
+                and t.is_contiguous() and t.dim() == 2 and tuple(t.shape) == (int(h) * int(w), int(t0.shape[1]) if channels is None else channels)
+                and (int(h), int(w)) == (int(h0), int(w0))):
+            raise hip.PodError("{} runs on contiguous fp32 channels-last (h * w, C) maps of one size on one GPU: there is no CPU path".format(who))
 
 
 def col2im3x3s2_cl(dcols: torch.Tensor, h: int, w: int, gate: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The input gradient of pod_im2col3x3s2_cl for one (h, w) image: dcols (ho * wo, 9 C) -> dx (h * w, C) = (gate > 0) * gathered sum + add."""
     _cl("pod_col2im3x3s2_cl", "dcols", dcols)
-    ho, wo = (int(h) - 1) // 2 + 1, (int(w) - 1) // 2 + 1
-    if h < 1 or w < 1 or int(dcols.shape[1]) % 36 or int(dcols.shape[0]) != ho * wo:
-        raise hip.PodError("pod_col2im3x3s2_cl: a {} x {} map has ({}, 9 C) patch rows with C % 4 == 0, got {}".format(h, w, ho * wo, tuple(dcols.shape)))
-    C = int(dcols.shape[1]) // 9
-    dx = torch.empty((h * w, C), dtype=torch.float32, device=dcols.device) if out is None else out
-    for what, t in (("gate", gate), ("add", add), ("dx", dx)):
-        if t is not None:
-            _cl("pod_col2im3x3s2_cl", what, t)
-            if tuple(t.shape) != (h * w, C) or t.device != dcols.device:
-                raise hip.PodError("pod_col2im3x3s2_cl: {} must be ({}, {}) on {}, got {} on {}".format(what, h * w, C, dcols.device, tuple(t.shape), t.device))
-    with torch.cuda.device(dcols.device):
-        hip.check(hip.load().pod_col2im3x3s2_cl(dcols.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), int(h), int(w), C,
-                                                _record_of(dx, record).data_ptr(), hip.current_stream()), "pod_col2im3x3s2_cl")
-    return dx
+    C9 = int(dcols.shape[1])
+    return _map_gather("pod_col2im3x3s2_cl", dcols, h, w, 0 if C9 % 36 else C9 // 9, "({}, 9 C) patch rows", gate, add, out, record)
 
 
 def upsample2_sum_cl(d_child: torch.Tensor, h: int, w: int, add: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -124,7 +151,7 @@ def upsample2_sum_cl(d_child: torch.Tensor, h: int, w: int, add: torch.Tensor, o
             h, w, ht * wt, tuple(d_child.shape), tuple(add.shape), tuple(d_top.shape)))
     with torch.cuda.device(d_child.device):
         hip.check(hip.load().pod_upsample2_sum_cl(d_child.data_ptr(), int(h), int(w), add.data_ptr(), d_top.data_ptr(), C,
-                                                  _record_of(d_top, record).data_ptr(), hip.current_stream()), "pod_upsample2_sum_cl")
+                                                  (amax.produced(d_top) if record is None else record).data_ptr(), hip.current_stream()), "pod_upsample2_sum_cl")
     return d_top
 
 
@@ -136,23 +163,14 @@ def conv1x1_wgrad_strided(x: torch.Tensor, dy: torch.Tensor, images: int, h: int
     _cl("pod_conv1x1_wgrad_strided", "x", x)
     _cl("pod_conv1x1_wgrad_strided", "dy", dy)
     images, h, w, stride = int(images), int(h), int(w), int(stride)
-    C, K = int(x.shape[1]), int(dy.shape[1])
-    lib = hip.load()
-    n = int(lib.pod_conv1x1_wgrad_strided_partials(images, h, w, stride, C, K))
-    if n <= 0:
-        raise hip.PodError("pod_conv1x1_wgrad_strided: images >= 1, stride 1 or 2, C % 16 == 0, C <= 18432, K % 64 == 0 and K <= 2048 required, got "
-                           "images={} {} x {} stride={} C={} K={}".format(images, h, w, stride, C, K))
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    if int(x.shape[0]) != images * h * w or int(dy.shape[0]) != images * ho * wo or dy.device != x.device:
-        raise hip.PodError("pod_conv1x1_wgrad_strided: {} images of {} x {} at stride {} pair {} rows of x with {} of dy, got {} on {} and {} on {}".format(
-            images, h, w, stride, images * h * w, images * ho * wo, x.shape[0], x.device, dy.shape[0], dy.device))
-    partials = torch.empty(n, dtype=torch.float32, device=x.device)
-    dW = torch.empty((K, C), dtype=torch.float32, device=x.device)
-    db = torch.empty((K,), dtype=torch.float32, device=x.device) if bias else None
-    with torch.cuda.device(x.device):
-        hip.check(lib.pod_conv1x1_wgrad_strided(x.data_ptr(), dy.data_ptr(), images, h, w, stride, C, K, amax.of(x).data_ptr(), amax.of(dy).data_ptr(),
-                                                dW.data_ptr(), hip.ptr(db), partials.data_ptr(), hip.current_stream()), "pod_conv1x1_wgrad_strided")
-    return dW, db
+    if stride in (1, 2):                                # (any other the entry refuses, below)
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        if int(x.shape[0]) != images * h * w or int(dy.shape[0]) != images * ho * wo or dy.device != x.device:
+            raise hip.PodError("pod_conv1x1_wgrad_strided: {} images of {} x {} at stride {} pair {} rows of x with {} of dy, got {} on {} and {} on {}".format(
+                images, h, w, stride, images * h * w, images * ho * wo, x.shape[0], x.device, dy.shape[0], dy.device))
+    return _c1w("pod_conv1x1_wgrad_strided", x, dy, (images, h, w, stride), bias,
+                "pod_conv1x1_wgrad_strided: images >= 1, stride 1 or 2, C % 16 == 0, C <= 18432, K % 64 == 0 and K <= 2048 required, got "
+                "images={} {} x {} stride={} C={} K={}".format(images, h, w, stride, x.shape[1], dy.shape[1]))
 
 
 def subsample2_scatter_cl(d_small: torch.Tensor, h: int, w: int, gate: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
@@ -160,17 +178,4 @@ def subsample2_scatter_cl(d_small: torch.Tensor, h: int, w: int, gate: Optional[
     """The input gradient of a stride-2 pixel selection for one (h, w) image: d_small (ho * wo, C) -> dx (h * w, C) = (gate > 0) * (d_small on
     the pixels with even coordinates, zero elsewhere, + add).  out may be `add`."""
     _cl("pod_subsample2_scatter_cl", "d_small", d_small)
-    h, w = int(h), int(w)
-    ho, wo, C = (h - 1) // 2 + 1, (w - 1) // 2 + 1, int(d_small.shape[1])
-    if h < 1 or w < 1 or C % 4 or int(d_small.shape[0]) != ho * wo:
-        raise hip.PodError("pod_subsample2_scatter_cl: a {} x {} map has ({}, C) selected rows with C % 4 == 0, got {}".format(h, w, ho * wo, tuple(d_small.shape)))
-    dx = torch.empty((h * w, C), dtype=torch.float32, device=d_small.device) if out is None else out
-    for what, t in (("gate", gate), ("add", add), ("dx", dx)):
-        if t is not None:
-            _cl("pod_subsample2_scatter_cl", what, t)
-            if tuple(t.shape) != (h * w, C) or t.device != d_small.device:
-                raise hip.PodError("pod_subsample2_scatter_cl: {} must be ({}, {}) on {}, got {} on {}".format(what, h * w, C, d_small.device, tuple(t.shape), t.device))
-    with torch.cuda.device(d_small.device):
-        hip.check(hip.load().pod_subsample2_scatter_cl(d_small.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), h, w, C,
-                                                       _record_of(dx, record).data_ptr(), hip.current_stream()), "pod_subsample2_scatter_cl")
-    return dx
+    return _map_gather("pod_subsample2_scatter_cl", d_small, h, w, int(d_small.shape[1]), "({}, C) selected rows", gate, add, out, record)

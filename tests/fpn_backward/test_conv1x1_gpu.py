@@ -123,6 +123,20 @@ def test_col2im_equals_autograd_through_unfold(h, w, C, with_gate, with_add):
         assert wgrad.col2im3x3s2_cl(dev(dcols), h, w, gate=dev(gate), add=buf, out=buf) is buf and torch.equal(buf, dx)
 
 
+def test_col2im_beyond_one_grid_trip():
+    """The element-wise loop the gathers share (pod_wgrad.h), past what one trip of the grid covers: 4096 workgroups x 256 lanes =
+    1 048 576 quads, and a 129 x 129 map of 256 channels has 1 065 024 -- the second trip takes the last 16 448.  Gate and add, whole map
+    against the fp64 reference (about a second on the CPU), to the bit; the record is the result's abs-max."""
+    h = w = 129
+    C, g = 256, torch.Generator().manual_seed(129)
+    assert h * w * C // 4 == 1065024 > 4096 * 256
+    dcols, gate, add = _ints((65 * 65, 9 * C), g), _ints((h * w, C), g, -2, 3), _ints((h * w, C), g)
+    want = fb.ref_col2im(dcols.double(), h, w, gate, add)
+    dx = wgrad.col2im3x3s2_cl(dcols.to(DEV), h, w, gate=gate.to(DEV), add=add.to(DEV))
+    assert torch.equal(dx.cpu().double(), want)
+    assert float(amax.of(dx).max()) == float(dx.abs().max())
+
+
 @pytest.mark.parametrize("h,w", [(5, 7), (4, 6)])
 def test_upsample2_sum_equals_autograd_through_nearest_interpolation(h, w):
     C, g = 64, torch.Generator().manual_seed(h)

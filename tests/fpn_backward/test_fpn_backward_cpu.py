@@ -46,6 +46,13 @@ def test_null_and_misaligned_arguments_are_refused_before_any_launch():
     assert lib.pod_conv1x1_wgrad(None, None, 16, 16, 64, None, None, None, None, None, None) == -1
     assert lib.pod_conv1x1_wgrad(16, 16, 0, 16, 64, 16, 16, 16, 16, 16, None) == -1          # no pixels
     assert lib.pod_conv1x1_wgrad(8, 16, 16, 16, 64, 16, 16, 16, 16, 16, None) == -1          # x not 16-byte aligned
+    # what pod_conv1x1_wgrad_strided refuses, every weight gradient refuses.  Pointers that are never dereferenced, distinct but for the defect
+    good = dict(x=0x1000, dy=0x2000, xa=0x3000, da=0x3800, dW=0x4000, db=0x5000, part=0x6000)
+    call = lambda **kw: (lambda a: lib.pod_conv1x1_wgrad(a["x"], a["dy"], 16, 16, 64, a["xa"], a["da"], a["dW"], a["db"], a["part"], None))({**good, **kw})
+    assert call(dW=good["x"]) == -1 and call(dW=good["part"]) == -1 and call(db=good["dW"]) == -1              # aliased
+    assert call(dW=good["dy"]) == -1 and call(part=good["x"]) == -1 and call(part=good["dy"]) == -1 and call(db=good["part"]) == -1
+    assert call(xa=0x3002) == -1 and call(da=0x3802) == -1 and call(dW=0x4002) == -1 and call(db=0x5002) == -1  # a record or output off 4 bytes
+    assert call(x=0x1008) == -1 and call(part=0x6008) == -1 and call(xa=None) == -1 and call(part=None) == -1
     assert lib.pod_col2im3x3s2_cl(None, None, None, None, 4, 4, 16, None, None) == -1
     assert lib.pod_col2im3x3s2_cl(16, None, None, 32, 4, 4, 6, None, None) == -1             # C % 4
     assert lib.pod_col2im3x3s2_cl(16, None, None, 16, 4, 4, 16, None, None) == -1            # in place on dcols

@@ -107,15 +107,20 @@ def test_partials_query_follows_the_slice_rule():
 
 def test_backward_entry_points_reject_invalid_arguments_without_a_gpu():
     lib = hip.load()
-    buf = ctypes.create_string_buffer(256)
+    buf = ctypes.create_string_buffer(2048)
     X = (ctypes.addressof(buf) + 15) & ~15
     lv = _levels((5, 7))
 
-    def wg(x=X, dy=X, levels=lv, n=1, copies=1, C=16, K=64, Kpad=64, xa=X, da=X, dW=X, db=X, partials=X):
+    # (never dereferenced; distinct, so that each call below has the one defect it names)
+    def wg(x=X, dy=X + 256, levels=lv, n=1, copies=1, C=16, K=64, Kpad=64, xa=X + 512, da=X + 516, dW=X + 768, db=X + 1024, partials=X + 1280):
         return lib.pod_conv3x3_wgrad(x, dy, levels, n, copies, C, K, Kpad, xa, da, dW, db, partials, None)
 
     for kw in ({"x": None}, {"dy": None}, {"levels": None}, {"xa": None}, {"da": None}, {"dW": None}, {"db": None}, {"partials": None},
-               {"n": 0}, {"copies": 0}, {"C": 8}, {"C": 24}, {"K": 0}, {"K": 65}, {"Kpad": 32}, {"x": X + 4}, {"partials": X + 8}):
+               {"n": 0}, {"copies": 0}, {"C": 8}, {"C": 24}, {"K": 0}, {"K": 65}, {"Kpad": 32}, {"x": X + 4}, {"partials": X + 1288}):
+        assert wg(**kw) == -1, kw
+    # what pod_conv1x1_wgrad_strided refuses, every weight gradient refuses: aliased outputs, a record or output off 4 bytes
+    for kw in ({"dW": X}, {"dW": X + 1280}, {"db": X + 768}, {"xa": X + 514}, {"da": X + 518}, {"dW": X + 770}, {"db": X + 1026},
+               {"dW": X + 256}, {"partials": X}, {"partials": X + 256}, {"db": X + 1280}):
         assert wg(**kw) == -1, kw
     gate = lambda out=X, d=X, dz=X, n=64, p=0.1: lib.pod_relu_dropout_backward(out, d, dz, n, p, None, None)
     for kw in ({"out": None}, {"d": None}, {"dz": None}, {"n": -4}, {"n": 6}, {"p": 1.0}, {"p": -0.1}, {"out": X + 4}):

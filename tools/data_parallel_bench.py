@@ -97,11 +97,11 @@ def main():
                         whole[name].append(w)
     # the kernel: 20 calls back to back from the C entry on one unchanged table
     b = trainers["data_parallel"].bucket
-    lib, k = hip.load(), 0
-    for d, e in zip(b._tables[k], b.entries):
+    torch.cuda.synchronize()
+    lib, table = hip.load(), b.table.begin()
+    for d, e in zip(table, b.entries):
         d.grad = e.w.data_ptr()                         # any fp32 tensor of the size: the weights stand in for gradients that were cleared
-    call = lambda: hip.check(lib.pod_grad_pack(b._tables[k], b._table_dev.data_ptr(), len(b.entries), b._map_dev.data_ptr(), b._n_chunks,
-                                               b._offsets_dev.data_ptr(), b.flat.data_ptr(), b.floats, 1.0, hip.current_stream()), "pod_grad_pack")
+    call = lambda: hip.check(lib.pod_grad_pack(table, *b.table.launch_args(), *b.pack_args(), 1.0, hip.current_stream()), "pod_grad_pack")
     reps, per_call, host_call = 20, [], []
     for r in range(2 + 6):
         torch.cuda.synchronize()
@@ -117,7 +117,7 @@ def main():
             per_call.append(e0.elapsed_time(e1) / reps)
             host_call.append(1e3 * (t1 - t0) / reps)
     elements = sum(e.w.numel() for e in b.entries)
-    out = {"frames": [args.batch, H, W], "tensors": len(b.entries), "elements": elements, "bucket_floats": b.floats, "chunks": b._n_chunks,
+    out = {"frames": [args.batch, H, W], "tensors": len(b.entries), "elements": elements, "bucket_floats": b.floats, "chunks": b.table.n_chunks,
            "pack_bytes": 8 * elements, "pack_ms_per_call": stats(per_call), "pack_host_ms_per_call": stats(host_call),
            "pack_TBps": 8 * elements / (statistics.median(per_call) * 1e-3) / 1e12,
            "section": {k: {m: stats(v) for m, v in s.items()} for k, s in section.items()}, "whole_step_ms": {k: stats(v) for k, v in whole.items()},
