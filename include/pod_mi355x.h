@@ -857,6 +857,48 @@ int64_t pod_grad_bucket_layout(const PodSgdTensor* tensors, int32_t n_tensors, i
 int pod_grad_pack(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks,
                   const int64_t* offsets_dev, float* bucket, int64_t bucket_floats, float scale, pod_stream_t stream);
 
+/* ---- K27  the box covariance trained with the energy score or by moment matching (csrc/k27_reg_score_loss.hip) ----------------
+ * Serves: ProbabilisticRetinaNet.losses, probabilistic_retinanet.py:285-331, for BBOX_COV_LOSS.NAME `second_moment_matching` and
+ * `energy_loss` -- names the reference's model YAMLs list (with NUM_SAMPLES = 1000, core/setup.py:107, read at PR:35) and its `losses`
+ * refuses (PR:308-311); the reference defines neither, so the definitions are the ones below.  Either sum takes the NLL sum's place: the
+ * caller divides it by the normaliser and mixes it with the standard regression loss by the annealing weight (PR:313-322) through w[2].
+ * Two new symbols and three constants under POD_ABI_VERSION 18, as for K20 - K26: no entry or structure that existed changed, so the number
+ * stands.
+ *
+ * Both losses act on the anchors with a label in [0, K) (and a matched box) and need the diagonal head.  Per anchor and coordinate j:
+ * t = get_deltas(anchor, matched box) with cfg->box_weights, formed as pod_train_loss forms it; delta the predicted delta, lv the
+ * predicted log-variance, c = clamp(lv, -7, 7) (d clamp = 1 on [-7, 7], 0 outside); sl1 = pod_train_loss's smooth-L1 term (|u| with
+ * derivative sign(u), sign(0) = 0, below beta < 1e-5).
+ *   POD_REG_LOSS_MOMENTS: d = delta - t, v = exp(c); loss = sum_j sl1(d_j) + sl1(v_j - d_j^2);
+ *     d / d delta_j = sl1'(d_j) - 2 d_j sl1'(v_j - d_j^2) (the error is not detached);  d / d lv_j = sl1'(v_j - d_j^2) v_j 1[-7 <= lv_j <= 7].
+ *   POD_REG_LOSS_ENERGY: M = num_samples, sigma = exp(0.5 c), z_s = delta + sigma eps_s for s = 0 .. M (M + 1 samples, eps iid N(0, 1));
+ *     ES = (2 / M) sum_{s < M} sum_j sl1(z_sj - t_j)  -  (1 / M) sum_{s < M} sum_j sl1(sigma_j (eps_sj - eps_{s+1,j}))
+ *     d / d delta_j = (2 / M) sum_s sl1'(u1),  u1 = (delta_j - t_j) + sigma_j eps_sj;
+ *     d / d lv_j = 0.5 sigma_j [(2 / M) sum_s sl1'(u1) eps_sj - (1 / M) sum_s sl1'(u2) (eps_sj - eps_{s+1,j})] 1[-7 <= lv_j <= 7],
+ *     u2 = sigma_j (eps_sj - eps_{s+1,j}), formed so and never as z_s - z_{s+1}: its sign is that of an exact fp32 difference.
+ * pod_reg_score_loss: cfg / levels / labels / matched_gt / gt_boxes / anchors / R as pod_train_loss takes them (cfg->n_runs = the image
+ *   count); every condition pod_train_loss refuses is refused here, and: cfg->cov_dims other than 4, a level without reg_var, `kind` outside
+ *   {1, 2}, for the energy loss num_samples < 1 or > POD_MAX_REG_SAMPLES, eps_reg / eps_out off 16 bytes -- POD_E_INVALID before anything is
+ *   enqueued.  sum dev double[1]: the loss over all positives of all images; fp32 terms accumulated in fp64, lanes -> wavefront butterfly ->
+ *   workgroup -> partials[workgroup] (partials: dev double[pod_reg_score_partials(cfg, levels)]) -> one pass in index order.  No
+ *   floating-point atomics: two launches give the same bits.
+ *   grads: NULL, or the planes pod_train_loss has written earlier on the same stream (w: the same dev float[3]).  To each `delta` plane the
+ *   launch adds w[2] d / d delta at the positive anchors -- one owner per element: load, add, store -- and touches no other element; it
+ *   writes EVERY element of each `reg_var` plane, w[2] d / d lv at the positives and exact zeros elsewhere; cls / cls_var are ignored.
+ *   Draws (energy loss): eps_reg NULL = in-kernel Philox4x32-10 normals on a stream word of their own, keyed by cfg->philox_seed and
+ *   (image, anchor index within R, sample, coordinate) ALONE -- eight normals per call = the samples (2c, 2c + 1) of one anchor -- so a
+ *   normal depends neither on the grid, nor on the batch size, nor on which other anchors are positive; or dev (num_samples + 1,
+ *   n_images * R, 4) normals to replay, dense by anchor.  eps_out: NULL or a buffer of that shape receiving the normals used, zeros at every
+ *   row that is not a positive anchor.  The dense arrays are a test and replay facility for small R: the product passes NULL for both. */
+#define POD_REG_LOSS_MOMENTS 1
+#define POD_REG_LOSS_ENERGY  2
+#define POD_MAX_REG_SAMPLES  4096   /* BBOX_COV_LOSS.NUM_SAMPLES (1000 by default) */
+int64_t pod_reg_score_partials(const PodConfig* cfg, const PodLevel* levels);
+int pod_reg_score_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelGrad* grads, const int32_t* labels,
+                       const int32_t* matched_gt, const float* gt_boxes, int32_t n_gt, const float* anchors, int32_t R,
+                       int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
+                       const float* w, double* partials, double* sum, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
  * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

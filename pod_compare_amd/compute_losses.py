@@ -6,7 +6,8 @@
 Per image: the loader, the model construction and the category maps are apply_net's (imported, unchanged); the ground-truth boxes are
 XYWH -> XYXY, scaled by the loader's resize factors, `iscrowd` boxes dropped, dataset category ids mapped to the model's contiguous ones
 (annotations of a category the model does not have are dropped); the forward runs with dropout off (--train-mode: on, as the
-reference's training forward); the anchors are labelled and the losses evaluated on the GPU (K21) with the normaliser
+reference's training forward); the anchors are labelled and the losses evaluated on the GPU (K21; K27 for the covariance term of
+--bbox-cov-loss energy_loss / second_moment_matching) with the normaliser
 max(1, positives of the image) and the annealing weight of --iteration (default SOLVER.STEPS[1]: annealing complete).  An image
 without annotations counts as all-background.  Prints and returns the data-set means of loss_cls, loss_box_reg and positives per image.
 """
@@ -48,6 +49,10 @@ def main(argv=None):
     ap.add_argument("--random-init", action="store_true", help="clear MODEL.WEIGHTS / OUTPUT_DIR and keep the seeded random initialisation")
     ap.add_argument("--random-seed", type=int, default=0)
     ap.add_argument("--iteration", type=int, default=-1, help="the training iteration the annealing weight is taken at (PR:320-321); default SOLVER.STEPS[1]")
+    ap.add_argument("--bbox-cov-loss", default=None, choices=losses.BBOX_COV_LOSSES,
+                    help="overrides MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS.NAME: the covariance term of loss_box_reg -- energy_loss on any "
+                         "checkpoint with the covariance head is its validation energy score, whatever it was trained under")
+    ap.add_argument("--bbox-cov-samples", type=int, default=0, help="overrides BBOX_COV_LOSS.NUM_SAMPLES, the energy loss's samples per positive anchor")
     ap.add_argument("--train-mode", action="store_true", help="dropout active in the head subnets, as in the reference's training forward")
     ap.add_argument("--min-size-test", type=int, default=0, help="overrides INPUT.MIN_SIZE_TEST")
     ap.add_argument("--max-size-test", type=int, default=0, help="overrides INPUT.MAX_SIZE_TEST")
@@ -64,6 +69,11 @@ def main(argv=None):
     if args.max_size_test > 0:
         cfg.INPUT.MAX_SIZE_TEST = args.max_size_test
     cfg.MODEL.DEVICE = args.device
+    cov = cfg.MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS
+    if args.bbox_cov_loss is not None:
+        cov.NAME = args.bbox_cov_loss
+    if args.bbox_cov_samples > 0:
+        cov.NUM_SAMPLES = args.bbox_cov_samples
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     torch.manual_seed(args.random_seed)
@@ -81,7 +91,8 @@ def main(argv=None):
     anneal = int(cfg.SOLVER.STEPS[1])
     crit = losses.ProbabilisticLosses(num_classes=K, cls_var_num_samples=cfg.MODEL.PROBABILISTIC_MODELING.CLS_VAR_LOSS.NUM_SAMPLES,
                                       smooth_l1_beta=float(cfg.MODEL.RETINANET.get("SMOOTH_L1_LOSS_BETA", 0.0)),
-                                      box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=anneal, seed=args.random_seed)
+                                      box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=anneal, seed=args.random_seed,
+                                      bbox_cov_loss=cov.NAME, bbox_cov_num_samples=int(cov.NUM_SAMPLES))
     crit.current_step = anneal if args.iteration < 0 else args.iteration
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
     total = torch.zeros(3, dtype=torch.float64, device=dev)          # loss_cls, loss_box_reg, positives: summed on the device
@@ -98,8 +109,9 @@ def main(argv=None):
             n += 1
     mean = (total / max(n, 1)).cpu().tolist()
     result = {"images": n, "loss_cls": mean[0], "loss_box_reg": mean[1], "positives_per_image": mean[2], "iteration": int(crit.current_step),
-              "annealing_weight": losses.annealing_weight(crit.current_step, anneal), "train_mode": bool(args.train_mode)}
-    print("%d images: loss_cls %.6f  loss_box_reg %.6f  positives per image %.2f  (iteration %d, NLL weight %.4f%s)" % (
+              "annealing_weight": losses.annealing_weight(crit.current_step, anneal), "train_mode": bool(args.train_mode),
+              "bbox_cov_loss": str(cov.NAME)}
+    print("%d images: loss_cls %.6f  loss_box_reg %.6f  positives per image %.2f  (iteration %d, covariance-loss weight %.4f%s)" % (
         n, result["loss_cls"], result["loss_box_reg"], result["positives_per_image"], result["iteration"], result["annealing_weight"],
         ", dropout on" if args.train_mode else ""))
     return result

@@ -11,12 +11,11 @@
 //                    K x S focal-loss terms, 4 smooth-L1 terms, every gradient element of the anchor written (zeros where it adds nothing).
 //                    fp32 terms, fp64 accumulation: lane -> wavefront butterfly -> workgroup -> partials[workgroup].
 //   k_loss_finish  : one workgroup adds the partials in a fixed order.  No floating-point atomics anywhere: the same bits every run.
-#include "pod_device.h"
+#include "pod_train_loss.h"
 
 namespace pod {
 
 constexpr uint32_t STREAM_LOSS = 0x6c6f7300u;   // classification logit samples of the loss (PR:245-246)
-constexpr int LOSS_BLOCK = 256;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // labelling
@@ -116,21 +115,6 @@ __device__ __forceinline__ void focal_term(float x, bool positive, float alpha, 
     dx = positive ? -dz : dz;
 }
 
-__device__ __forceinline__ void smooth_l1_term(float d, float beta, float& loss, float& dd) {
-    const float ad = fabsf(d);
-    const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-    if (beta < 1e-5f) {
-        loss = ad;
-        dd = sgn;
-    } else if (ad < beta) {
-        loss = __fdiv_rn(0.5f * d * d, beta);
-        dd = __fdiv_rn(d, beta);
-    } else {
-        loss = ad - 0.5f * beta;
-        dd = sgn;
-    }
-}
-
 __global__ void __launch_bounds__(LOSS_BLOCK) k_train_loss(const KLossParams P) {
     __shared__ double s_part[4][LOSS_BLOCK / 64];
     const int img = blockIdx.y;
@@ -201,17 +185,7 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_train_loss(const KLossParams P) 
         const int mg = fg ? P.matched_gt[row] : -1;
         const bool reg = fg && mg >= 0 && mg < P.n_gt;
         float tgt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (reg) {                       // Box2BoxTransform.get_deltas
-            const Box s = load_box(P.anchors, r), g = load_box(P.gt_boxes, mg);
-            const float sw = s.x2 - s.x1, sh = s.y2 - s.y1;
-            const float scx = s.x1 + 0.5f * sw, scy = s.y1 + 0.5f * sh;
-            const float tw = g.x2 - g.x1, th = g.y2 - g.y1;
-            const float tcx = g.x1 + 0.5f * tw, tcy = g.y1 + 0.5f * th;
-            tgt[0] = __fdiv_rn(P.wts[0] * (tcx - scx), sw);
-            tgt[1] = __fdiv_rn(P.wts[1] * (tcy - scy), sh);
-            tgt[2] = P.wts[2] * logf(__fdiv_rn(tw, sw));
-            tgt[3] = P.wts[3] * logf(__fdiv_rn(th, sh));
-        }
+        if (reg) box_deltas(load_box(P.anchors, r), load_box(P.gt_boxes, mg), P.wts, tgt);
         if (fg) acc_pos = 1.0;
         const size_t d_base = (size_t)img * L.run_stride_delta + (size_t)(a * 4) * HW + cell;
         const size_t v_base = (size_t)img * L.run_stride_reg + (size_t)(a * 4) * HW + cell;
@@ -269,23 +243,6 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_loss_finish(const double* partia
         __syncthreads();
     }
     if (threadIdx.x < 4) sums[threadIdx.x] = s_sum[threadIdx.x][0];
-}
-
-static int64_t loss_blocks(const PodConfig* cfg, const PodLevel* levels, int32_t* first_block) {
-    int64_t n = 0;
-    for (int l = 0; l < cfg->n_levels; ++l) {
-        if (first_block) first_block[l] = (int32_t)n;
-        if (levels[l].H < 1 || levels[l].W < 1) return -1;
-        n += ((int64_t)cfg->num_anchors * levels[l].H * levels[l].W + LOSS_BLOCK - 1) / LOSS_BLOCK;
-        if (n > 0x7FFFFFFF) return -1;
-    }
-    if (first_block) first_block[cfg->n_levels] = (int32_t)n;
-    return n;
-}
-
-static bool loss_cfg_ok(const PodConfig* cfg, const PodLevel* levels) {
-    return cfg && levels && cfg->n_levels >= 1 && cfg->n_levels <= POD_MAX_LEVELS && cfg->n_runs >= 1 && cfg->n_runs <= 65535 &&
-           cfg->num_anchors >= 1 && cfg->num_classes >= 1 && cfg->num_classes < POD_MAX_CLASSES;
 }
 
 }  // namespace pod

@@ -4,6 +4,8 @@
     crit = ProbabilisticLosses(num_classes=7, cls_var_num_samples=10)
     out = crit(head_outputs, labels, matched_gt, gt_boxes, anchors)           # {"loss_cls", "loss_box_reg"}: device scalars, PR:333
     (out["loss_cls"] + out["loss_box_reg"]).backward()                        # gradients at the four head outputs
+    crit = ProbabilisticLosses(num_classes=7, bbox_cov_loss="energy_loss", bbox_cov_num_samples=1000)          # BBOX_COV_LOSS.NAME: the
+    # covariance term of loss_box_reg is the energy score (or "second_moment_matching") in place of the NLL: a second launch, K27
 
 Everything stays on the device: no call here reads a value back.  The convolutions have no backward pass -- the gradients stop at the
 per-level head tensors (`(N, A*C, H, W)` planes, N = images), which is what a trainer of the head, or a checkpoint selection by
@@ -66,14 +68,9 @@ def annealing_weight(current_step: float, annealing_step: float) -> float:
     return (100 ** x - 1.0) / (100.0 - 1.0)
 
 
-def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, *,
-                    box_weights=(1.0, 1.0, 1.0, 1.0), alpha: float = 0.25, gamma: float = 2.0, beta: float = 0.0, cls_samples: int = 0,
-                    eps: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
-                    want_grads: bool = False, seed: int = 0, cov_dims: Optional[int] = None):
-    """One pod_train_loss launch.  cls / delta / cls_var / reg_var: per-level lists of contiguous fp32 (N, A*C, H, W) planes (cls_var /
-    reg_var None without that head).  Returns (sums double[4] = cls sum, standard regression sum, NLL regression sum, positives;
-    grads = None or (g_cls, g_delta, g_cls_var, g_reg_var) per-level lists of d(w . sums[:3]) / d input)."""
-    lib = hip.load()
+def _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, box_weights,
+                   cls_samples: int, seed: int, cov_dims: Optional[int]):
+    """What pod_train_loss and pod_reg_score_loss take alike: (cfg, levels, anchors (R, 4), gt (G, 4)), every plane and index tensor checked."""
     L, n = len(cls), int(cls[0].shape[0])
     dev = cls[0].device
     D = (0 if reg_var is None else int(reg_var[0].shape[1]) // num_anchors) if cov_dims is None else int(cov_dims)
@@ -110,7 +107,26 @@ def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, 
         if not (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n, r) and t.device == dev):
             raise hip.PodError("{}: expected contiguous int32 {} on {}".format(name, (n, r), dev))
     gt = gt_boxes.to(dev, torch.float32).reshape(-1, 4).contiguous()
-    g = int(gt.shape[0])
+    return cfg, lv, a, gt
+
+
+def _weights_ok(w, dev) -> torch.Tensor:
+    if w is None or w.dtype != torch.float32 or w.numel() != 3 or w.device != dev:
+        raise hip.PodError("w: three fp32 weights on {} are needed with gradient planes".format(dev))
+    return w.contiguous()
+
+
+def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, *,
+                    box_weights=(1.0, 1.0, 1.0, 1.0), alpha: float = 0.25, gamma: float = 2.0, beta: float = 0.0, cls_samples: int = 0,
+                    eps: Optional[torch.Tensor] = None, eps_out: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+                    want_grads: bool = False, seed: int = 0, cov_dims: Optional[int] = None):
+    """One pod_train_loss launch.  cls / delta / cls_var / reg_var: per-level lists of contiguous fp32 (N, A*C, H, W) planes (cls_var /
+    reg_var None without that head).  Returns (sums double[4] = cls sum, standard regression sum, NLL regression sum, positives;
+    grads = None or (g_cls, g_delta, g_cls_var, g_reg_var) per-level lists of d(w . sums[:3]) / d input)."""
+    lib = hip.load()
+    cfg, lv, a, gt = _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors, num_classes, box_weights,
+                                    cls_samples, seed, cov_dims)
+    L, n, dev, r, g = len(cls), int(cls[0].shape[0]), cls[0].device, int(a.shape[0]), int(gt.shape[0])
     S = int(cls_samples) if cls_var is not None else 0
     for name, t in (("eps", eps), ("eps_out", eps_out)):
         if t is not None and not (cls_var is not None and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
@@ -118,9 +134,7 @@ def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, 
             raise hip.PodError("{}: expected contiguous fp32 {} on {} and a variance head".format(name, (S, n * r, num_classes), dev))
     grads = garr = None
     if want_grads:
-        if w is None or w.dtype != torch.float32 or w.numel() != 3 or w.device != dev:
-            raise hip.PodError("w: three fp32 weights on {} are needed with gradient planes".format(dev))
-        w = w.contiguous()
+        w = _weights_ok(w, dev)
         grads = ([torch.empty_like(t) for t in cls], [torch.empty_like(t) for t in delta],
                  None if cls_var is None else [torch.empty_like(t) for t in cls_var],
                  None if reg_var is None else [torch.empty_like(t) for t in reg_var])
@@ -139,9 +153,58 @@ def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, 
     return sums, grads
 
 
+BBOX_COV_LOSSES = ("none", "negative_log_likelihood", "second_moment_matching", "energy_loss")      # BBOX_COV_LOSS.NAME
+REG_SCORE_KINDS = {"second_moment_matching": hip.POD_REG_LOSS_MOMENTS, "energy_loss": hip.POD_REG_LOSS_ENERGY}
+
+
+def reg_score_sum(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, *, kind: str,
+                  num_samples: int = 1000, box_weights=(1.0, 1.0, 1.0, 1.0), beta: float = 0.0, cls_samples: int = 0,
+                  eps_reg: Optional[torch.Tensor] = None, eps_reg_out: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+                  grads=None, seed: int = 0):
+    """One pod_reg_score_loss launch (K27): the `second_moment_matching` or `energy_loss` sum over the positive anchors, planes as
+    train_loss_sums takes them.  grads: None, or train_loss_sums' planes of the SAME inputs and `w`, written earlier on this stream: the
+    launch adds w[2] d sum / d delta to their delta planes in place, and the reg_var planes are allocated here.  eps_reg / eps_reg_out:
+    the dense (num_samples + 1, N*R, 4) normals to replay / to receive the ones used (energy loss; tests and replay at small R only).
+    Returns (sum double[1], grads with the new reg_var planes in fourth place, or None)."""
+    if kind not in REG_SCORE_KINDS:
+        raise ValueError("reg_score_sum: kind is one of {}, got {!r}".format(sorted(REG_SCORE_KINDS), kind))
+    if reg_var is None:
+        raise hip.PodError("{} needs the box covariance head (reg_var planes)".format(kind))
+    lib = hip.load()
+    cfg, lv, a, gt = _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors, num_classes, box_weights,
+                                    cls_samples, seed, None)
+    L, n, dev, r, g = len(cls), int(cls[0].shape[0]), cls[0].device, int(a.shape[0]), int(gt.shape[0])
+    M = int(num_samples)
+    for name, t in (("eps_reg", eps_reg), ("eps_reg_out", eps_reg_out)):
+        if t is not None and not (kind == "energy_loss" and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                                  and tuple(t.shape) == (M + 1, n * r, 4)):
+            raise hip.PodError("{}: expected contiguous fp32 {} on {} and the energy loss".format(name, (M + 1, n * r, 4), dev))
+    garr = None
+    if grads is not None:
+        w = _weights_ok(w, dev)
+        g_reg_var = [torch.empty_like(t) for t in reg_var]
+        grads = (grads[0], grads[1], grads[2], g_reg_var)
+        garr = (hip.PodLevelGrad * hip.POD_MAX_LEVELS)()
+        for l in range(L):
+            if tuple(grads[1][l].shape) != tuple(delta[l].shape) or not grads[1][l].is_contiguous():
+                raise hip.PodError("grads: delta plane {} is not laid out as delta[{}]".format(l, l))
+            garr[l].delta, garr[l].reg_var = grads[1][l].data_ptr(), g_reg_var[l].data_ptr()
+    n_part = int(lib.pod_reg_score_partials(cfg, lv))
+    partials = torch.empty((max(n_part, 1),), dtype=torch.float64, device=dev)
+    total = torch.empty((1,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        hip.check(lib.pod_reg_score_loss(cfg, lv, garr, hip.ptr(labels), hip.ptr(matched_gt), hip.ptr(gt) if g else None, g, hip.ptr(a), r,
+                                         REG_SCORE_KINDS[kind], M, float(beta), hip.ptr(eps_reg), hip.ptr(eps_reg_out),
+                                         hip.ptr(w) if grads is not None else None, hip.ptr(partials), hip.ptr(total), hip.current_stream()),
+                  "pod_reg_score_loss")
+    return total, grads
+
+
 class _TrainLoss(torch.autograd.Function):
-    """(loss_cls, loss_box_reg) = (w[0] cls_sum, w[1] std_reg_sum + w[2] nll_reg_sum), differentiable with respect to the per-level
-    head tensors: forward is one pod_train_loss launch that also writes the gradient planes, backward scales them."""
+    """(loss_cls, loss_box_reg) = (w[0] cls_sum, w[1] std_reg_sum + w[2] cov_reg_sum), differentiable with respect to the per-level
+    head tensors: forward is one pod_train_loss launch that also writes the gradient planes, backward scales them.  With
+    `second_moment_matching` or `energy_loss` the covariance sum and its gradients come from a second launch, pod_reg_score_loss, on the
+    planes the first one wrote without the reg_var head."""
 
     @staticmethod
     def forward(ctx, meta, w, *tensors):
@@ -150,10 +213,17 @@ class _TrainLoss(torch.autograd.Function):
         cls, delta = ts[:L], ts[L:2 * L]
         cls_var = ts[2 * L:3 * L] if has_cv else None
         reg_var = ts[(2 + has_cv) * L:(3 + has_cv) * L] if has_rv else None
-        sums, grads = train_loss_sums(cls, delta, cls_var, reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"], meta["anchors"],
-                                      meta["num_anchors"], meta["num_classes"], box_weights=meta["box_weights"], alpha=meta["alpha"],
+        score = meta.get("score_kind") if has_rv else None
+        sums, grads = train_loss_sums(cls, delta, cls_var, None if score else reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"],
+                                      meta["anchors"], meta["num_anchors"], meta["num_classes"], box_weights=meta["box_weights"], alpha=meta["alpha"],
                                       gamma=meta["gamma"], beta=meta["beta"], cls_samples=meta["cls_samples"], eps=meta["eps"],
                                       eps_out=meta.get("eps_out"), w=w, want_grads=True, seed=meta["seed"])
+        if score:
+            total, grads = reg_score_sum(cls, delta, cls_var, reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"], meta["anchors"],
+                                         meta["num_anchors"], meta["num_classes"], kind=score, num_samples=meta["score_samples"],
+                                         box_weights=meta["box_weights"], beta=meta["beta"], cls_samples=meta["cls_samples"],
+                                         eps_reg=meta.get("eps_reg"), eps_reg_out=meta.get("eps_reg_out"), w=w, grads=grads, seed=meta["seed"])
+            sums[2:3].copy_(total)
         ctx.meta = (L, has_cv, has_rv)
         ctx.planes = grads
         wd = w.double()
@@ -181,14 +251,18 @@ class ProbabilisticLosses:
 
     def __init__(self, num_classes: int = 7, cls_var_num_samples: int = 3, focal_loss_alpha: float = 0.25, focal_loss_gamma: float = 2.0,
                  smooth_l1_beta: float = 0.0, box_reg_weights=(1.0, 1.0, 1.0, 1.0), annealing_step: int = 80000, loss_normalizer: float = 100.0,
-                 loss_normalizer_momentum: float = 0.9, seed: int = 0):
+                 loss_normalizer_momentum: float = 0.9, seed: int = 0, bbox_cov_loss: str = "negative_log_likelihood",
+                 bbox_cov_num_samples: int = 1000):
+        if bbox_cov_loss not in BBOX_COV_LOSSES:          # PR:308-311
+            raise ValueError("Invalid regression loss name {!r}: BBOX_COV_LOSS.NAME is one of {}".format(bbox_cov_loss, ", ".join(BBOX_COV_LOSSES)))
+        self.bbox_cov_loss, self.bbox_cov_num_samples = bbox_cov_loss, int(bbox_cov_num_samples)
         self.num_classes, self.cls_var_num_samples = int(num_classes), int(cls_var_num_samples)
         self.focal_loss_alpha, self.focal_loss_gamma, self.smooth_l1_beta = float(focal_loss_alpha), float(focal_loss_gamma), float(smooth_l1_beta)
         self.box_reg_weights = tuple(float(x) for x in box_reg_weights)
         self.annealing_step, self.current_step = annealing_step, 0
         self.loss_normalizer, self.loss_normalizer_momentum = loss_normalizer, float(loss_normalizer_momentum)
         self.seed, self.draws = int(seed), 0
-        self.last_sums = None          # device double[4] of the last call: cls sum, standard / NLL regression sums, positives
+        self.last_sums = None          # device double[4] of the last call: cls sum, standard / covariance regression sums, positives
 
     def weights(self, normalizer: torch.Tensor, has_cls_var: bool, has_reg_var: bool) -> torch.Tensor:
         """Device float[3]: what multiplies the three sums (PR:268 / 282, PR:307, 319-322, 331)."""
@@ -198,11 +272,14 @@ class ProbabilisticLosses:
         return (torch.tensor([1.0 / s, 1.0 - lam, lam], dtype=torch.float64, device=norm.device) / norm).to(torch.float32)
 
     def __call__(self, head_outputs, labels: torch.Tensor, matched_gt: torch.Tensor, gt_boxes: torch.Tensor, anchors=None,
-                 eps: Optional[torch.Tensor] = None, normalizer=None, eps_out: Optional[torch.Tensor] = None):
+                 eps: Optional[torch.Tensor] = None, normalizer=None, eps_out: Optional[torch.Tensor] = None,
+                 eps_reg: Optional[torch.Tensor] = None, eps_reg_out: Optional[torch.Tensor] = None):
         """head_outputs: synthetic.HeadOutputs whose tensors are (N images, A*C, H, W); labels / matched_gt: `label_anchors`' (N, R);
         gt_boxes: the concatenated (G, 4) boxes matched_gt indexes; anchors: default head_outputs.anchors.  eps: None (in-kernel draws,
         fresh on every call) or the dense (S, N*R, K) normals to replay.  normalizer: None = the reference's moving average (PR:201-203,
-        updated here from the labels' positives, on the device), else the number or device scalar to divide by (max(1, .))."""
+        updated here from the labels' positives, on the device), else the number or device scalar to divide by (max(1, .)).  eps_reg /
+        eps_reg_out: the energy loss's dense (M + 1, N*R, 4) normals, as eps / eps_out (reg_score_sum).  With the covariance head, the
+        covariance term of loss_box_reg is the one `bbox_cov_loss` names ("none": the NLL, as for every head with reg_var planes)."""
         ho = head_outputs
         dev = ho.cls[0].device
         K = self.num_classes
@@ -220,7 +297,9 @@ class ProbabilisticLosses:
         meta = dict(levels=len(ho.cls), has_cls_var=int(has_cv), has_reg_var=int(has_rv), labels=labels, matched_gt=matched_gt, gt_boxes=gt_boxes,
                     anchors=ho.anchors if anchors is None else anchors, num_anchors=ho.num_anchors, num_classes=K, box_weights=self.box_reg_weights,
                     alpha=self.focal_loss_alpha, gamma=self.focal_loss_gamma, beta=self.smooth_l1_beta, cls_samples=self.cls_var_num_samples,
-                    eps=eps, eps_out=eps_out, seed=(self.seed & 0xFFFFFFFF) | ((self.draws & 0xFFFFFFFF) << 32))
+                    eps=eps, eps_out=eps_out, seed=(self.seed & 0xFFFFFFFF) | ((self.draws & 0xFFFFFFFF) << 32),
+                    score_kind=self.bbox_cov_loss if self.bbox_cov_loss in REG_SCORE_KINDS else None, score_samples=self.bbox_cov_num_samples,
+                    eps_reg=eps_reg, eps_reg_out=eps_reg_out)
         self.draws += 1
         tensors = list(ho.cls) + list(ho.delta) + (list(ho.cls_var) if has_cv else []) + (list(ho.reg_var) if has_rv else [])
         loss_cls, loss_reg = _TrainLoss.apply(meta, w, *tensors)

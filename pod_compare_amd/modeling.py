@@ -822,9 +822,10 @@ class ProbabilisticRetinaNet(_TracksStorage):
 
     def __init__(self, num_classes=7, dropout_rate=0.0, cls_var_loss="none", cls_var_num_samples=3,
                  bbox_cov_loss="none", bbox_cov_type="diagonal", test_score_thresh=0.05, test_topk_candidates=1000,
-                 test_nms_thresh=0.5, max_detections_per_image=100, min_size_test=800, max_size_test=1333):
+                 test_nms_thresh=0.5, max_detections_per_image=100, min_size_test=800, max_size_test=1333, bbox_cov_num_samples=1000):
         super().__init__()
         self.num_classes = num_classes
+        self.bbox_cov_loss, self.bbox_cov_num_samples = bbox_cov_loss, bbox_cov_num_samples      # PR:33-35
         self.compute_cls_var = cls_var_loss != "none"                  # PR:29-30
         self.cls_var_num_samples = cls_var_num_samples
         self.compute_bbox_cov = bbox_cov_loss != "none"                # PR:33-34
@@ -879,7 +880,8 @@ class ProbabilisticRetinaNet(_TracksStorage):
         {"loss_cls", "loss_box_reg"} as device scalars.  The state the reference keeps on the model (loss_normalizer, current_step) lives in
         `self.loss_state` (losses.ProbabilisticLosses); eps / normalizer as in its __call__."""
         if getattr(self, "loss_state", None) is None:
-            self.loss_state = _losses.ProbabilisticLosses(num_classes=self.num_classes, cls_var_num_samples=self.cls_var_num_samples)
+            self.loss_state = _losses.ProbabilisticLosses(num_classes=self.num_classes, cls_var_num_samples=self.cls_var_num_samples,
+                                                          bbox_cov_loss=self.bbox_cov_loss, bbox_cov_num_samples=self.bbox_cov_num_samples)
         labels, matched, _ = _losses.label_anchors(outputs.anchors, gt_boxes, gt_classes, self.num_classes)
         boxes, _, _ = _losses.concat_ground_truth(gt_boxes, gt_classes, labels.device)
         return self.loss_state(outputs, labels, matched, boxes, eps=eps, normalizer=normalizer)

@@ -47,7 +47,7 @@ def build_model(cfg, save_dir: Optional[str] = "", load_weights: bool = True, fo
         bbox_cov_type=pm.BBOX_COV_LOSS.COVARIANCE_TYPE, test_score_thresh=cfg.MODEL.RETINANET.SCORE_THRESH_TEST,
         test_topk_candidates=cfg.MODEL.RETINANET.TOPK_CANDIDATES_TEST, test_nms_thresh=cfg.MODEL.RETINANET.NMS_THRESH_TEST,
         max_detections_per_image=cfg.TEST.DETECTIONS_PER_IMAGE, min_size_test=cfg.INPUT.MIN_SIZE_TEST,
-        max_size_test=cfg.INPUT.MAX_SIZE_TEST)
+        max_size_test=cfg.INPUT.MAX_SIZE_TEST, bbox_cov_num_samples=pm.BBOX_COV_LOSS.NUM_SAMPLES)
     model.loaded_from = ""
     if load_weights:
         if save_dir == "":

@@ -414,6 +414,10 @@ def main(argv=None):
     ap.add_argument("--output-dir", default="", help="overrides OUTPUT_DIR")
     ap.add_argument("--weights", default=None, help="overrides MODEL.WEIGHTS (the checkpoint to fine-tune)")
     ap.add_argument("--random-init", action="store_true", help="load nothing: keep the seeded random initialisation")
+    ap.add_argument("--bbox-cov-loss", default=None, choices=losses.BBOX_COV_LOSSES,
+                    help="overrides MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS.NAME: what trains the box covariance (energy_loss and "
+                         "second_moment_matching run on K27).  No checkpoint records the name: with --resume it is again the config's, or this flag's")
+    ap.add_argument("--bbox-cov-samples", type=int, default=0, help="overrides BBOX_COV_LOSS.NUM_SAMPLES, the energy loss's samples per positive anchor")
     ap.add_argument("--random-seed", type=int, default=0)
     ap.add_argument("--max-iter", type=int, default=-1, help="overrides SOLVER.MAX_ITER")
     ap.add_argument("--log-period", type=int, default=20, help="a loss line every this many iterations (the only host read-back); 0: none")
@@ -475,6 +479,11 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     if args.max_size_test > 0:
         cfg.INPUT.MAX_SIZE_TEST = args.max_size_test
     cfg.MODEL.DEVICE = args.device
+    cov = cfg.MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS
+    if args.bbox_cov_loss is not None:
+        cov.NAME = args.bbox_cov_loss
+    if args.bbox_cov_samples > 0:
+        cov.NUM_SAMPLES = args.bbox_cov_samples
     freeze_at = cfg.MODEL.BACKBONE.get("FREEZE_AT", 2)
     if int(freeze_at) != 2:
         raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: the stem and res2 are frozen and res3 - res5 train (detectron2's "
@@ -518,7 +527,7 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     model.loss_state = losses.ProbabilisticLosses(num_classes=K, cls_var_num_samples=cfg.MODEL.PROBABILISTIC_MODELING.CLS_VAR_LOSS.NUM_SAMPLES,
                                                   smooth_l1_beta=float(cfg.MODEL.RETINANET.get("SMOOTH_L1_LOSS_BETA", 0.0)),
                                                   box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=int(s.STEPS[1]),
-                                                  seed=args.random_seed + rank)
+                                                  seed=args.random_seed + rank, bbox_cov_loss=cov.NAME, bbox_cov_num_samples=int(cov.NUM_SAMPLES))
     model.head.dropout_seed += rank                        # a rank's loss samples and dropout masks are its own, as detectron2 seeds its ranks
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
                           warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=train_fpn, train_backbone=args.train_backbone,
