@@ -481,7 +481,10 @@ int pod_im2col3x3s2_cl(const float* x, float* y, int32_t H, int32_t W, int32_t C
  * Outputs: gt_fn[g] = 1 iff every IoU <= iou_min (EU:245); gt_match_count[g] detections with IoU >= iou_correct, their
  * global indices / IoUs in gt_match_idx / gt_match_iou (n_gt x 128) ordered by descending max class probability
  * (entry 0 = the true positive, the rest duplicates, EU:282-299); det_fp[d] = 1 iff IoU <= iou_min with every
- * ground truth of its image (EU:255; an image without ground truth makes all its detections false positives). */
+ * ground truth of its image (EU:255; an image without ground truth makes all its detections false positives).
+ * Pinned by tests/eval_instrument: equal max class probabilities rank by lower detection index; entries of gt_match_idx / gt_match_iou at
+ * rank >= gt_match_count[g] are not written; the IoU is detectron2's pairwise_iou in fp32, that operation order (bit-equal to a CPU
+ * evaluation), compared as fp32 with >= iou_correct and <= iou_min; a detection may be the match of several boxes. */
 int pod_match_groundtruth(const float* det_boxes, const float* det_probs, const int32_t* det_off, const int32_t* det_img,
                           int32_t n_det, const float* gt_boxes, const int32_t* gt_off, const int32_t* gt_img, int32_t n_gt,
                           int32_t num_classes, float iou_min, float iou_correct, int32_t* gt_fn, int32_t* gt_match_count,

@@ -25,7 +25,7 @@ def match_predictions_to_groundtruth(predicted_box_means: Dict, predicted_cls_pr
     dev = torch.device(device)
     keys = list(predicted_box_means.keys())
     f = lambda t: t.to(dev, torch.float32)
-    k = next(iter(predicted_cls_probs.values())).shape[1] if keys else 1
+    k = next(iter(predicted_cls_probs.values())).shape[1] if keys else 0          # no prediction: empty (0, 0) probabilities, as the oracle's
     pb = torch.cat([f(predicted_box_means[i]).reshape(-1, 4) for i in keys]) if keys else torch.zeros((0, 4), device=dev)
     pp = torch.cat([f(predicted_cls_probs[i]).reshape(-1, k) for i in keys]) if keys else torch.zeros((0, k), device=dev)
     pc = torch.cat([f(predicted_box_covariances[i]).reshape(-1, 4, 4) for i in keys]) if keys else torch.zeros((0, 4, 4), device=dev)
@@ -50,7 +50,7 @@ def match_predictions_to_groundtruth(predicted_box_means: Dict, predicted_cls_pr
     P = hip.ptr
     pb, pp, gb = pb.contiguous(), pp.contiguous(), gb.contiguous()
     hip.check(lib.pod_match_groundtruth(P(pb), P(pp), P(det_off), P(det_img.contiguous()), D, P(gb), P(gt_off), P(gt_img.contiguous()), G,
-                                        k, float(iou_min), float(iou_correct), P(gt_fn), P(cnt), P(midx), P(miou), P(det_fp),
+                                        max(k, 1), float(iou_min), float(iou_correct), P(gt_fn), P(cnt), P(midx), P(miou), P(det_fp),
                                         hip.current_stream()), "pod_match_groundtruth")
     gt_fn, cnt, midx, miou, det_fp = gt_fn[:G], cnt[:G], midx[:G], miou[:G], det_fp[:D]
     rank = torch.arange(MATCH_MAX_DET, device=dev)[None, :]
@@ -87,7 +87,8 @@ def compute_reg_scores_fn(false_positives: Dict, valid_idxs: torch.Tensor) -> Di
     covs = false_positives["predicted_box_covariances"][valid_idxs]
     if covs.shape[0] == 0:
         return {"total_entropy_mean": None}
-    sig = covs.double() + 1e-2 * torch.eye(4, dtype=torch.float64, device=covs.device)
+    # Sigma is formed in fp32, as SR:100-101 and pod_reg_nll form it (the sum rounds where a variance is >~ 1e5 * 1e-2), then scored in fp64
+    sig = (covs.float() + 1e-2 * torch.eye(4, dtype=torch.float32, device=covs.device)).double()
     ent = 0.5 * torch.logdet(sig) + 2.0 * (1.0 + math.log(2.0 * math.pi))
     return {"total_entropy_mean": float(ent.mean())}
 
