@@ -902,8 +902,8 @@ int pod_reg_score_loss(const PodConfig* cfg, const PodLevel* levels, const PodLe
                        int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
                        const float* w, double* partials, double* sum, pod_stream_t stream);
 
-/* (test support -- the dumps of the in-kernel Philox draws and of the f16 split -- is declared in include/pod_mi355x_test.h: the library
- * exports those three entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
+/* (test support -- the dumps of the in-kernel Philox draws, of the generator itself and of the f16 split -- is declared in
+ * include/pod_mi355x_test.h: the library exports those entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 
 /* ---- K13 conv1x1_split (round 4): the 1x1 convolutions of the backbone / FPN as a channels-last GEMM ------------------------
  * Replaces: detectron2 BottleneckBlock.conv1 / conv3 / shortcut (1x1, stride 1 or 2, FrozenBN folded, ReLU, residual add) and

@@ -22,6 +22,11 @@ int pod_dump_cls_normals(const PodConfig* cfg, const PodLevel* levels, int32_t l
 int pod_dump_box_normals(const PodConfig* cfg, const int32_t* global_anchor_ids, int32_t n, float* eps_prop, pod_stream_t stream);
 /* test support for the split kernels' arithmetic contract (tests/test_wino_conv_gpu.py): terms[2][n] f16 bit patterns (dev uint16, n even): x[i] * scale = t0 + t1 to 2^-23 |x[i] scale| (scale a power of two; the round-5 split kernels' own code) */
 int pod_debug_f16_split2(const float* x, float scale, void* terms, int64_t n, pod_stream_t stream);
+/* test support for the RNG contract (tests/rng/): the kernels' own philox4x32_10 and box_muller16 (csrc/pod_device.h) on given inputs.
+ *   pod_debug_philox4x32:   ctr_key dev uint32 (n, 6) = {counter[4], key[2]} -> out dev uint32 (n, 4), the four output words;
+ *   pod_debug_box_muller16: words dev uint32 (n) -> out dev float (n, 2), the two normals of a word (low half: radius, high half: angle). */
+int pod_debug_philox4x32(const uint32_t* ctr_key, uint32_t* out, int64_t n, pod_stream_t stream);
+int pod_debug_box_muller16(const uint32_t* words, float* out, int64_t n, pod_stream_t stream);
 
 #ifdef __cplusplus
 }

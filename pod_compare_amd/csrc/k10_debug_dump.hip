@@ -1,7 +1,7 @@
 // pod_dump_cls_normals / pod_dump_box_normals -- test support: the in-kernel (native-RNG) draws, written out.
 //
 // The product path never stores a normal: K1b / K2b re-derive the classification draws of PI:291-294 from Philox counters
-// (pod_device.h: class_prob_cell) and K3 the box-delta draws of PI:351-356 (pod_candidate.h: decode_candidate).  These two
+// (pod_merge_score.h: class_prob_cell) and K3 the box-delta draws of PI:351-356 (pod_candidate.h: decode_candidate).  These two
 // entry points evaluate the SAME counter -> normal maps and write the values in the reference's tensor layouts
 //     eps_cls  : (cls_samples, H*W*A, K)   one tensor per level          (Normal(...).rsample((S,)),   PI:291-294)
 //     eps_prop : (prop_samples, n, 4)      rows = the given anchors      (MVN.rsample((1000,)),        PI:351-356)
@@ -9,6 +9,7 @@
 // (tests/test_native_exact_gpu.py).  Not on the inference path; nothing else calls them.
 #include "pod_device.h"
 #include "../../include/pod_mi355x_test.h"
+#include "pod_merge_score.h"
 #include "pod_split_gemm.h"
 
 namespace pod {
@@ -61,6 +62,7 @@ extern "C" int pod_dump_cls_normals(const PodConfig* cfg, const PodLevel* levels
     if (!cfg || !levels || !eps_cls || level < 0 || level >= cfg->n_levels || cfg->n_levels > POD_MAX_LEVELS) return POD_E_INVALID;
     if (cfg->cls_samples < 1 || cfg->cls_samples > POD_MAX_CLS_SAMPLES || cfg->num_classes < 1 || cfg->num_classes > POD_MAX_CLASSES)
         return POD_E_INVALID;
+    if (cfg->num_anchors < 1 || !pod_cls_counter_fields_ok(cfg)) return POD_E_INVALID;
     const int HW = levels[level].H * levels[level].W;
     const int64_t items = (int64_t)HW * cfg->num_anchors * cfg->num_classes;
     hipLaunchKernelGGL(pod::k_dump_cls_normals, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cfg->philox_seed,
@@ -101,6 +103,42 @@ extern "C" int pod_debug_f16_split2(const float* x, float scale, void* terms, in
     if (n == 0) return POD_OK;
     hipLaunchKernelGGL(pod::k_debug_f16_split2, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, scale,
                        reinterpret_cast<uint16_t*>(terms), n);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}
+
+// pod_debug_philox4x32 / pod_debug_box_muller16 -- test support: the generator and the word -> normals step of pod_device.h, called on
+// given inputs, so that a host restatement can referee each on its own (tests/rng/): ctr_key[i] = {c0, c1, c2, c3, k0, k1} -> out[i] =
+// the four words; words[i] -> out[i] = {n0, n1}.
+namespace pod {
+__global__ void __launch_bounds__(256) k_debug_philox4x32(const uint32_t* __restrict__ ctr_key, uint32_t* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = ctr_key + i * 6;
+    const u32x4 r = philox4x32_10(u32x4{p[0], p[1], p[2], p[3]}, p[4], p[5]);
+    out[i * 4 + 0] = r.x; out[i * 4 + 1] = r.y; out[i * 4 + 2] = r.z; out[i * 4 + 3] = r.w;
+}
+__global__ void __launch_bounds__(256) k_debug_box_muller16(const uint32_t* __restrict__ words, float* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float n0, n1;
+    box_muller16(words[i], n0, n1);
+    out[i * 2 + 0] = n0; out[i * 2 + 1] = n1;
+}
+}  // namespace pod
+
+extern "C" int pod_debug_philox4x32(const uint32_t* ctr_key, uint32_t* out, int64_t n, pod_stream_t stream) {
+    if (!ctr_key || !out || n < 0 || (n + 255) / 256 > 0x7FFFFFFFLL) return POD_E_INVALID;
+    if (n == 0) return POD_OK;
+    hipLaunchKernelGGL(pod::k_debug_philox4x32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ctr_key, out, n);
+    POD_CHECK_LAUNCH();
+    return POD_OK;
+}
+
+extern "C" int pod_debug_box_muller16(const uint32_t* words, float* out, int64_t n, pod_stream_t stream) {
+    if (!words || !out || n < 0 || (n + 255) / 256 > 0x7FFFFFFFLL) return POD_E_INVALID;
+    if (n == 0) return POD_OK;
+    hipLaunchKernelGGL(pod::k_debug_box_muller16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, words, out, n);
     POD_CHECK_LAUNCH();
     return POD_OK;
 }

@@ -425,6 +425,7 @@ extern "C" int pod_mc_merge_score(const PodConfig* cfg, const PodLevel* levels, 
     }
     const int L = cfg->n_levels, K = cfg->num_classes, A = cfg->num_anchors, N = cfg->n_runs, D = cfg->cov_dims;
     if (!pod_merge_score_cfg_ok(cfg) || !(D == 0 || D == 4 || D == 10)) return POD_E_INVALID;
+    if (!pod_cls_counter_ok(cfg, levels)) return POD_E_INVALID;      // (prune mode draws nothing itself, but K1b's refusal would come after its work)
     pod::K1Params P;
     const int threads = 64 * K;
     for (int l = 0; l < L; ++l) {
@@ -503,6 +504,7 @@ extern "C" int pod_score_maybe(const PodConfig* cfg, const PodLevel* levels, con
     if (!cfg || !levels || !maybe_bits || !cand_keys || !cand_count) return POD_E_INVALID;
     const int L = cfg->n_levels, K = cfg->num_classes;
     if (!pod_merge_score_cfg_ok(cfg) || !cfg->has_cls_var) return POD_E_INVALID;
+    if (!pod_cls_counter_fields_ok(cfg)) return POD_E_INVALID;      // native draws only (eps_cls is refused below)
     if (cfg->n_runs > 1 && (!mean_cls || !mean_cls_var)) return POD_E_INVALID;
     pod::K1bParams P;
     pod_bitmap_layout(cfg, levels, P.wpa, P.word_begin);

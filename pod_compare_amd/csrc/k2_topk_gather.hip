@@ -459,6 +459,7 @@ extern "C" int pod_gather_candidates(const PodConfig* cfg, const PodLevel* level
         return POD_E_INVALID;
     if (cfg->cov_dims > 0 && !cand_reg_var) return POD_E_INVALID;
     if (!pod_candidate_cfg_ok(cfg, POD_CHECK_ROWS | POD_CHECK_CHANNELS)) return POD_E_INVALID;
+    if (!pod_cls_counter_ok(cfg, levels)) return POD_E_INVALID;
     const pod::K2bParams P = pod_k2b_params(cfg, levels, anchors, cat_keys, cat_level, n_total, cand_count, probs_dense, cand_anchor_idx, cand_level,
                                             cand_score, cand_class, cand_probs, cand_delta, cand_reg_var, cand_anchor, cand_run_delta);
     const int slots = cfg->n_levels * cfg->topk;

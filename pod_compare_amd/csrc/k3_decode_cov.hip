@@ -151,6 +151,7 @@ extern "C" int pod_gather_decode(const PodConfig* cfg, const PodLevel* levels, c
         return POD_E_INVALID;
     if (cfg->cov_dims > 0 && !cand_reg_var) return POD_E_INVALID;
     if (!pod_candidate_cfg_ok(cfg, POD_CHECK_LEVELS_RUNS | POD_CHECK_CHANNELS | POD_CHECK_PROP_SAMPLES | POD_CHECK_ROWS)) return POD_E_INVALID;
+    if (!pod_cls_counter_ok(cfg, levels)) return POD_E_INVALID;
     for (int l = 0; l < cfg->n_levels; ++l)
         if (levels[l].eps_cls) return POD_E_INVALID;   // native draws only: eps-replay uses pod_gather_candidates + pod_decode_cov
     pod::K23Params P;

@@ -412,7 +412,7 @@ __device__ __forceinline__ void decode_candidate(const K3Params& P, int i, int l
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // The cfg ranges the candidate entry points (pod_gather_candidates, pod_decode_cov, pod_gather_decode) rely on.  An entry point
-// names the checks it has always made: none of them checks more, or less, than it did.
+// names the checks it has always made; what the draws' counter can hold (pod_merge_score.h: pod_cls_counter_ok) each asks beside them.
 enum : unsigned {
     POD_CHECK_LEVELS_RUNS = 1u,    // 1 <= n_levels <= POD_MAX_LEVELS, 1 <= n_runs <= POD_MAX_RUNS
     POD_CHECK_CHANNELS = 2u,       // 2K + 4 + D channels fit the 64 lanes of gather_candidate

@@ -133,6 +133,21 @@ static inline float pod_prune_logit(float score_thresh) {
     return (t > 0.0 && t < 1.0) ? (float)(log(t / (1.0 - t)) - 0.02) : -INFINITY;   // margin covers the fast-math error
 }
 
+// class_prob_cell's counter word c1 = level << 16 | a << 8 | k: an anchor shape or a class past 8 bits (a level past 16) would run into
+// the neighbouring field and share its draws with another (level, shape, class).
+static inline bool pod_cls_counter_fields_ok(const PodConfig* cfg) {
+    return cfg->num_anchors <= 256 && cfg->num_classes <= 256 && cfg->n_levels <= 65536;
+}
+// What every entry point that may form that counter asks: a variance head whose samples are drawn in-kernel on at least one level (no
+// eps_cls to replay there) needs fields that hold the cfg; a launch that replays every level's normals, or has no variance head, forms no
+// counter and takes any anchor-shape count, as it always did.
+static inline bool pod_cls_counter_ok(const PodConfig* cfg, const PodLevel* levels) {
+    if (!cfg->has_cls_var) return true;
+    bool native = false;
+    for (int l = 0; l < cfg->n_levels && l < POD_MAX_LEVELS; ++l) native = native || !levels[l].eps_cls;
+    return !native || pod_cls_counter_fields_ok(cfg);
+}
+
 // The cfg ranges every merge-and-score entry point relies on.
 static inline bool pod_merge_score_cfg_ok(const PodConfig* cfg) {
     const int L = cfg->n_levels, K = cfg->num_classes, A = cfg->num_anchors, N = cfg->n_runs;

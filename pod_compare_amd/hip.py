@@ -53,8 +53,8 @@ _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scra
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
                  "pod_grad_bucket_layout", "pod_reg_score_partials")
-# include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws and of the f16 split) -- exported for tests/ and tools/, not part of the boundary
-TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2")
+# include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
+TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
 
 
@@ -167,7 +167,7 @@ def load() -> ctypes.CDLL:
     lib.pod_merge_score_fused.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, P, P, P, P]
     lib.pod_level_topk.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, P, P, P, P, P, P]
     lib.pod_gather_candidates.argtypes = [POINTER(PodConfig), POINTER(PodLevel)] + [P] * 16
-    lib.pod_gather_decode.argtypes = [POINTER(PodConfig), POINTER(PodLevel)] + [P] * 19
+    lib.pod_gather_decode.argtypes = [POINTER(PodConfig), POINTER(PodLevel)] + [P] * 18      # 17 pointers and the stream
     lib.pod_decode_cov.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, c_int32, P, P, P, P, P, P, P, c_int32, P, P, P]
     lib.pod_nms_cluster.argtypes = [POINTER(PodConfig), P, c_int32, P, P, P, P, P, P, P]
     lib.pod_bayes_fuse.argtypes = [POINTER(PodConfig), P, P, P, P, P, P, P, P, c_int32, c_int32, P, P, P, P, P, P]
@@ -191,6 +191,8 @@ def load() -> ctypes.CDLL:
     lib.pod_sparse_reach.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, P, P, P, P]
     lib.pod_sparse_live_blocks.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, c_int32, P, c_int32, c_int32, P, P]
     lib.pod_debug_f16_split2.argtypes = [P, c_float, P, c_int64, P]
+    lib.pod_debug_philox4x32.argtypes = [P, P, c_int64, P]
+    lib.pod_debug_box_muller16.argtypes = [P, P, c_int64, P]
     lib.pod_wino_reduce.argtypes = [P, c_int32, c_int64, P, P, c_int64, c_int32, c_int32, c_int32, P, P]
     lib.pod_reduce_partials.argtypes = [P, c_int32, c_int64, P, P, P, c_int64, c_int32, c_int32, P, P]
     lib.pod_stem7x7_filter_split.argtypes = [P, P, P]

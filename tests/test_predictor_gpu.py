@@ -332,6 +332,10 @@ def test_fused_relu_dropout_statistics():
     pos = x > 0
     assert bool((y[~pos] == 0).all())
     kept = y[pos] != 0
+    # the mask is the host restatement's (tests/rng/): the survivors among the positive elements are its, one for one
+    from tests.rng import rng_ref
+    host = torch.from_numpy(rng_ref.dropout_keep(1234, 0, x.numel(), p, "inplace")).reshape(x.shape).to(x.device)
+    assert torch.equal(kept, host[pos]) and int(kept.sum()) == int(host[pos].sum())
     assert abs(float(kept.float().mean()) - (1 - p)) < 5e-3
     assert torch.allclose(y[pos][kept], x[pos][kept] / (1 - p), rtol=1e-6, atol=0)
     # neighbouring elements are not correlated (one Philox call feeds 4 elements)
