@@ -699,7 +699,7 @@ int pod_label_anchors(const float* anchors, int32_t R, const float* gt_boxes, co
 /* pod_train_loss: replaces PR:168-333 (PR:194 get_deltas, PR:223-282 classification, PR:285-331 regression; the normaliser, the annealing
  *   weight and the division by the sample count, PR:201-203 / 268 / 320-322, are the caller's three weights).
  *   levels: the head outputs, cfg->n_runs = the IMAGE count and the run strides the image strides; cfg->cov_dims 0 or 4 (10: POD_E_INVALID,
- *   the reference defines no loss for the full covariance); cfg->num_classes <= 15.  labels / matched_gt dev int32 (n_images, R) as
+ *   the reference defines no loss for the full covariance: pod_full_cov_loss, K28, below); cfg->num_classes <= 15.  labels / matched_gt dev int32 (n_images, R) as
  *   pod_label_anchors writes them, gt_boxes dev (n_gt, 4), anchors dev (R, 4), R = the levels' anchors.
  *   Classification, anchors with label >= 0, one-hot target without the background column: fvcore's sigmoid focal loss
  *   (p = sigmoid(x), ce = BCE-with-logits, p_t = p t + (1 - p)(1 - t), ce (1 - p_t)^gamma (alpha t + (1 - alpha)(1 - t)); alpha < 0: no
@@ -901,6 +901,54 @@ int pod_reg_score_loss(const PodConfig* cfg, const PodLevel* levels, const PodLe
                        const int32_t* matched_gt, const float* gt_boxes, int32_t n_gt, const float* anchors, int32_t R,
                        int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
                        const float* w, double* partials, double* sum, pod_stream_t stream);
+
+/* ---- K28  the FULL box covariance trained: the Gaussian NLL, moment matching, the energy score (csrc/k28_full_cov_loss.hip) -----
+ * Serves: ProbabilisticRetinaNet.losses, probabilistic_retinanet.py:285-331, for BBOX_COV_LOSS.COVARIANCE_TYPE `full` -- a choice the
+ * reference's model YAMLs list (`'full', 'diagonal'`), whose ten-channel predictor it builds (PR:37-44) and whose output its inference turns
+ * into a Cholesky factor (covariance_output_to_cholesky, MU:4-22), but for which its `losses` has no branch (PR:289 falls through, PR:322
+ * dies on an unbound name).  The definitions are therefore the ones below, as K27's are.  One of the three sums takes the NLL sum's place
+ * through w[2].  Two new symbols and three constants under POD_ABI_VERSION 18, as for K20 - K27: no entry or structure that existed
+ * changed, so the number stands; pod_train_loss and pod_reg_score_loss refuse cfg->cov_dims = 10 as before.
+ *
+ * Per anchor with a label in [0, K) and a matched box (K27's selection): t = get_deltas(anchor, box) with cfg->box_weights, formed as
+ * pod_train_loss forms it; d = delta - t; rv[0..9] the anchor's ten reg_var channels (channel a * 10 + j of a plane belongs to anchor
+ * shape a); c_j = clamp(rv_j, -7, 7) for j < 4 (d clamp = 1 on [-7, 7], 0 outside); L lower triangular, L_jj = exp(0.5 c_j), its strict
+ * lower triangle in torch.tril_indices(4, 4, -1) order T = (1,0) (2,0) (2,1) (3,0) (3,1) (3,2) = rv[4..9], unclamped -- the order
+ * cholesky_from_head reads; sl1 / sl1' = pod_train_loss's smooth-L1 term and its derivative.  For all three kinds
+ * d / d rv_j = 0.5 L_jj (d / d L_jj) 1[-7 <= rv_j <= 7] for j < 4 and d / d rv_{4+k} = d / d L_{T[k]}.
+ *   POD_FULL_COV_NLL: the Gaussian's negative log-likelihood without its constant.  y solves L y = d (forward substitution, fp32,
+ *     correctly rounded divisions), loss = 0.5 sum_j y_j^2 + 0.5 sum_j c_j; q solves L^T q = y;
+ *     d / d delta_j = q_j;  d / d rv_j = 0.5 (1 - L_jj q_j y_j) 1[-7 <= rv_j <= 7] (j < 4);  d / d rv_{4+k} = - q_i y_j, (i, j) = T[k].
+ *     This does NOT reduce to pod_train_loss's diagonal form (PR:298-304) at zero off-diagonals: that form puts a smooth-L1 term where the
+ *     Gaussian has a square.  The diagonal path is unchanged.
+ *   POD_FULL_COV_MOMENTS: Sigma = L L^T, E = Sigma - d d^T; loss = sum_j sl1(d_j) + sum_{i >= j} sl1(E_ij) (ten terms);
+ *     m_ij = sl1'(E_ij) (i >= j), G = the symmetric extension of m plus diag(m_00 .. m_33);
+ *     d / d delta_a = sl1'(d_a) - (G d)_a;  d / d L_ab = (G L)_ab for b <= a.
+ *   POD_FULL_COV_ENERGY: M = num_samples, eps_s in R^4 for s = 0 .. M (iid N(0, 1));  u1_s = d + L eps_s,
+ *     u2_s = L (eps_s - eps_{s+1}), formed from the exact fp32 difference of the normals and never as a difference of samples;
+ *     ES = (2 / M) sum_{s < M} sum_j sl1(u1_sj)  -  (1 / M) sum_{s < M} sum_j sl1(u2_sj);
+ *     d / d delta_j = (2 / M) sum_s sl1'(u1_sj);
+ *     d / d L_jk = (2 / M) sum_s sl1'(u1_sj) eps_sk - (1 / M) sum_s sl1'(u2_sj) (eps_sk - eps_{s+1,k}) for k <= j.
+ * pod_full_cov_loss: pod_reg_score_loss's argument list, same order and meaning.  It refuses everything pod_reg_score_loss refuses, except
+ *   that it requires cfg->cov_dims == 10 (4 and 0: POD_E_INVALID) and `kind` in {1, 2, 3}; num_samples is checked for the energy kind only.
+ *   POD_E_INVALID before anything is enqueued.  sum dev double[1]; partials: dev double[pod_full_cov_partials(cfg, levels)]; fp32 terms
+ *   accumulated in fp64, lanes -> wavefront butterfly -> workgroup -> partials[workgroup] -> one pass in index order.  No floating-point
+ *   atomics: two launches give the same bits.
+ *   grads: NULL, or the planes pod_train_loss has written earlier on the same stream, run with cov_dims = 0 and no reg_var (w: the same dev
+ *   float[3]).  To each `delta` plane the launch adds w[2] d / d delta at the positive anchors -- one owner per element: load, add, store
+ *   -- and touches no other element; it writes EVERY element of each ten-channel `reg_var` plane, w[2] d / d rv at the positives and
+ *   exact zeros elsewhere; cls / cls_var are ignored.
+ *   Draws (energy kind): K27's -- the same stream word, keyed by cfg->philox_seed and (image, anchor index within R, sample pair) alone, so
+ *   under one seed an anchor sees the normals pod_reg_score_loss would give it; eps_reg / eps_out: dense (num_samples + 1, n_images * R, 4),
+ *   as for K27. */
+#define POD_FULL_COV_NLL     1
+#define POD_FULL_COV_MOMENTS 2
+#define POD_FULL_COV_ENERGY  3
+int64_t pod_full_cov_partials(const PodConfig* cfg, const PodLevel* levels);
+int pod_full_cov_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelGrad* grads, const int32_t* labels,
+                      const int32_t* matched_gt, const float* gt_boxes, int32_t n_gt, const float* anchors, int32_t R,
+                      int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
+                      const float* w, double* partials, double* sum, pod_stream_t stream);
 
 /* (test support -- the dumps of the in-kernel Philox draws, of the generator itself and of the f16 split -- is declared in
  * include/pod_mi355x_test.h: the library exports those entry points for tests/ and tools/, they are not part of the drop-in boundary.) */

@@ -7,7 +7,7 @@ Per image: the loader, the model construction and the category maps are apply_ne
 XYWH -> XYXY, scaled by the loader's resize factors, `iscrowd` boxes dropped, dataset category ids mapped to the model's contiguous ones
 (annotations of a category the model does not have are dropped); the forward runs with dropout off (--train-mode: on, as the
 reference's training forward); the anchors are labelled and the losses evaluated on the GPU (K21; K27 for the covariance term of
---bbox-cov-loss energy_loss / second_moment_matching) with the normaliser
+--bbox-cov-loss energy_loss / second_moment_matching; K28 for every name with --bbox-cov-type full) with the normaliser
 max(1, positives of the image) and the annealing weight of --iteration (default SOLVER.STEPS[1]: annealing complete).  An image
 without annotations counts as all-background.  Prints and returns the data-set means of loss_cls, loss_box_reg and positives per image.
 """
@@ -34,9 +34,20 @@ def image_ground_truth(annotations: List[dict], cat_map: Dict[int, int], scale_x
     return torch.tensor(boxes, dtype=torch.float32).reshape(-1, 4), torch.tensor(classes, dtype=torch.int64)
 
 
-def main(argv=None):
-    from .config import setup_config
-    from .probabilistic_inference import build_model
+def covariance_overrides(cfg, args):
+    """--bbox-cov-loss / --bbox-cov-type / --bbox-cov-samples set their BBOX_COV_LOSS keys (compute_losses and train_head alike); returns
+    that node of the config."""
+    cov = cfg.MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS
+    if args.bbox_cov_loss is not None:
+        cov.NAME = args.bbox_cov_loss
+    if args.bbox_cov_type is not None:
+        cov.COVARIANCE_TYPE = args.bbox_cov_type
+    if args.bbox_cov_samples > 0:
+        cov.NUM_SAMPLES = args.bbox_cov_samples
+    return cov
+
+
+def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     here = os.path.dirname(os.path.abspath(__file__))
     ap.add_argument("--config-file", default=os.path.join(here, "configs/BDD-Detection/retinanet/retinanet_R_50_FPN_1x_reg_cls_var_dropout.yaml"))
@@ -52,13 +63,21 @@ def main(argv=None):
     ap.add_argument("--bbox-cov-loss", default=None, choices=losses.BBOX_COV_LOSSES,
                     help="overrides MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS.NAME: the covariance term of loss_box_reg -- energy_loss on any "
                          "checkpoint with the covariance head is its validation energy score, whatever it was trained under")
+    ap.add_argument("--bbox-cov-type", default=None, choices=("diagonal", "full"),
+                    help="overrides BBOX_COV_LOSS.COVARIANCE_TYPE: the head the checkpoint is loaded into (`full`: ten covariance channels, K28)")
     ap.add_argument("--bbox-cov-samples", type=int, default=0, help="overrides BBOX_COV_LOSS.NUM_SAMPLES, the energy loss's samples per positive anchor")
     ap.add_argument("--train-mode", action="store_true", help="dropout active in the head subnets, as in the reference's training forward")
     ap.add_argument("--min-size-test", type=int, default=0, help="overrides INPUT.MIN_SIZE_TEST")
     ap.add_argument("--max-size-test", type=int, default=0, help="overrides INPUT.MAX_SIZE_TEST")
     ap.add_argument("--loader-workers", type=int, default=-1, help="host threads of the loader; -1 = the config's value")
     ap.add_argument("--device", default="cuda:0")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from .config import setup_config
+    from .probabilistic_inference import build_model
+    args = arg_parser().parse_args(argv)
     cfg = setup_config(args.config_file, args.inference_config, args.random_seed, data_dir=args.data_dir, is_testing=bool(args.data_dir))
     if args.weights is not None:
         cfg.MODEL.WEIGHTS = args.weights
@@ -69,11 +88,7 @@ def main(argv=None):
     if args.max_size_test > 0:
         cfg.INPUT.MAX_SIZE_TEST = args.max_size_test
     cfg.MODEL.DEVICE = args.device
-    cov = cfg.MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS
-    if args.bbox_cov_loss is not None:
-        cov.NAME = args.bbox_cov_loss
-    if args.bbox_cov_samples > 0:
-        cov.NUM_SAMPLES = args.bbox_cov_samples
+    cov = covariance_overrides(cfg, args)
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
     torch.manual_seed(args.random_seed)
@@ -110,7 +125,7 @@ def main(argv=None):
     mean = (total / max(n, 1)).cpu().tolist()
     result = {"images": n, "loss_cls": mean[0], "loss_box_reg": mean[1], "positives_per_image": mean[2], "iteration": int(crit.current_step),
               "annealing_weight": losses.annealing_weight(crit.current_step, anneal), "train_mode": bool(args.train_mode),
-              "bbox_cov_loss": str(cov.NAME)}
+              "bbox_cov_loss": str(cov.NAME), "bbox_cov_type": str(cov.COVARIANCE_TYPE)}
     print("%d images: loss_cls %.6f  loss_box_reg %.6f  positives per image %.2f  (iteration %d, covariance-loss weight %.4f%s)" % (
         n, result["loss_cls"], result["loss_box_reg"], result["positives_per_image"], result["iteration"], result["annealing_weight"],
         ", dropout on" if args.train_mode else ""))

@@ -11,52 +11,13 @@
 //                                       normals of a pair, sample 2c + 2 comes from the neighbouring lane (lane 63: from lane 0 of the next
 //                                       trip, drawn one trip ahead).  Butterfly sums, one lane stores the anchor's gradient.
 //   k_score_finish                    : one workgroup adds the partials in index order.
+// The launch record, the pair fetch, the listing, the workgroup sum and the finish kernel are pod_train_loss.h's: K28 (the full covariance)
+// runs on the same ones.
 // fp32 terms, fp64 accumulation: lane -> wavefront butterfly -> workgroup -> partials[workgroup].  No floating-point atomics: the same bits
 // every run.  A draw depends on (seed, image, anchor, sample, coordinate) alone -- not on the grid, the batch or the other positives.
 #include "pod_train_loss.h"
 
 namespace pod {
-
-constexpr uint32_t STREAM_REG_SCORE = 0x72656700u;   // box-delta samples of the energy score ("reg")
-constexpr int SCORE_WAVES = LOSS_BLOCK / 64;
-
-struct KScoreParams {
-    PodLevel lv[POD_MAX_LEVELS];
-    PodLevelGrad gr[POD_MAX_LEVELS];
-    int32_t first_block[POD_MAX_LEVELS + 1];
-    int32_t n_levels, A, K, R, n_images, n_gt, M, has_grads;
-    float beta;
-    float wts[4];
-    uint64_t seed;
-    const int32_t* labels;
-    const int32_t* matched_gt;
-    const float* gt_boxes;
-    const float* anchors;
-    const float* eps;
-    float* eps_out;
-    const float* w;
-    double* partials;
-};
-
-// the eight normals of sample pair c of one anchor: samples 2c and 2c + 1, four coordinates each (zeros past sample M)
-__device__ __forceinline__ f32x8n score_pair(const KScoreParams& P, int r, int img, size_t row, size_t n_rows, int c) {
-    f32x8n o;
-    if (P.eps) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int s = 2 * c + h;
-            float4 v = float4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (s <= P.M) v = *reinterpret_cast<const float4*>(P.eps + ((size_t)s * n_rows + row) * 4);
-            o.v[4 * h] = v.x; o.v[4 * h + 1] = v.y; o.v[4 * h + 2] = v.z; o.v[4 * h + 3] = v.w;
-        }
-    } else if (2 * c <= P.M) {
-        o = philox_normals8(P.seed, (uint32_t)r, (uint32_t)img, (uint32_t)c, STREAM_REG_SCORE);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = 0.0f;
-    }
-    return o;
-}
 
 template <int KIND>
 __global__ void __launch_bounds__(LOSS_BLOCK) k_reg_score(const KScoreParams P) {
@@ -109,22 +70,11 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_reg_score(const KScoreParams P) 
         } else if (!pos) {
             if (P.has_grads && P.gr[l].reg_var)
                 for (int j = 0; j < 4; ++j) P.gr[l].reg_var[v_base + (size_t)j * HW] = 0.0f;
-            if (P.eps_out)      // an anchor that is not positive draws nothing
-                for (int s = 0; s <= P.M; ++s) *reinterpret_cast<float4*>(P.eps_out + ((size_t)s * n_rows + row) * 4) = float4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (P.eps_out) score_zero_draws(P, row, n_rows);
         }
     }
     if (KIND == POD_REG_LOSS_ENERGY) {
-        // ---- the workgroup's positives, in thread order
-        const unsigned long long m = __ballot(pos);
-        if (lane == 0) s_count[wv] = __popcll(m);
-        __syncthreads();
-        int before = 0, n_pos = 0;
-        for (int i = 0; i < SCORE_WAVES; ++i) {
-            if (i < wv) before += s_count[i];
-            n_pos += s_count[i];
-        }
-        if (pos) s_list[before + __popcll(m & ((1ull << lane) - 1ull))] = threadIdx.x;
-        __syncthreads();
+        const int n_pos = score_list_positives(pos, s_list, s_count);          // the workgroup's positives, in thread order
         // ---- a wavefront per listed positive, a lane per sample pair
         const float inv_m = __fdiv_rn(1.0f, (float)P.M);
         const int trips = (P.M / 2 + 1 + 63) / 64;
@@ -205,77 +155,25 @@ __global__ void __launch_bounds__(LOSS_BLOCK) k_reg_score(const KScoreParams P) 
             }
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) s_part[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = s_part[0];
-        for (int i = 1; i < SCORE_WAVES; ++i) s += s_part[i];
-        P.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
-    }
-}
-
-// K21's k_loss_finish for one quantity: thread-strided sums in index order, then a fixed tree
-__global__ void __launch_bounds__(LOSS_BLOCK) k_score_finish(const double* partials, int64_t n, double* sum) {
-    __shared__ double s_sum[LOSS_BLOCK];
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += LOSS_BLOCK) a += partials[i];
-    s_sum[threadIdx.x] = a;
-    __syncthreads();
-    for (int step = LOSS_BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step) s_sum[threadIdx.x] += s_sum[threadIdx.x + step];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sum[0] = s_sum[0];
+    score_block_sum(acc, s_part, P.partials);
 }
 
 }  // namespace pod
 
-extern "C" int64_t pod_reg_score_partials(const PodConfig* cfg, const PodLevel* levels) {
-    if (!pod::loss_cfg_ok(cfg, levels)) return 0;
-    const int64_t n = pod::loss_blocks(cfg, levels, nullptr);
-    return n < 0 ? 0 : n * cfg->n_runs;
-}
+extern "C" int64_t pod_reg_score_partials(const PodConfig* cfg, const PodLevel* levels) { return pod::score_partials(cfg, levels); }
 
 extern "C" int pod_reg_score_loss(const PodConfig* cfg, const PodLevel* levels, const PodLevelGrad* grads, const int32_t* labels,
                                   const int32_t* matched_gt, const float* gt_boxes, int32_t n_gt, const float* anchors, int32_t R,
                                   int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
                                   const float* w, double* partials, double* sum, pod_stream_t stream) {
-    // ---- what pod_train_loss refuses
-    if (!pod::loss_cfg_ok(cfg, levels) || !labels || !matched_gt || !anchors || !partials || !sum || R < 1 || n_gt < 0) return POD_E_INVALID;
-    if (cfg->cov_dims != 4) return POD_E_INVALID;            // both losses need the diagonal covariance head
-    if (n_gt > 0 && !gt_boxes) return POD_E_INVALID;
-    if (grads && !w) return POD_E_INVALID;
-    if (cfg->has_cls_var && (cfg->cls_samples < 1 || cfg->cls_samples > POD_MAX_CLS_SAMPLES)) return POD_E_INVALID;
-    if (!(smooth_l1_beta >= 0.0f)) return POD_E_INVALID;
-    // ---- and what is this entry's own
-    if (kind != POD_REG_LOSS_MOMENTS && kind != POD_REG_LOSS_ENERGY) return POD_E_INVALID;
-    const bool energy = kind == POD_REG_LOSS_ENERGY;
-    if (energy && (num_samples < 1 || num_samples > POD_MAX_REG_SAMPLES)) return POD_E_INVALID;
-    if (!pod_aligned(16, eps_reg, eps_out)) return POD_E_INVALID;
     pod::KScoreParams P;
-    const int64_t n_blocks = pod::loss_blocks(cfg, levels, P.first_block);
-    if (n_blocks < 1) return POD_E_INVALID;
-    int64_t anchors_seen = 0;
-    for (int l = 0; l < cfg->n_levels; ++l) {
-        const PodLevel& L = levels[l];
-        if (!L.cls || !L.delta || (cfg->has_cls_var && !L.cls_var) || !L.reg_var) return POD_E_INVALID;
-        const int64_t n_l = (int64_t)cfg->num_anchors * L.H * L.W;
-        if (L.anchor_base < 0 || (int64_t)L.anchor_base + n_l > R) return POD_E_INVALID;      // every label / anchor row the kernel reads exists
-        anchors_seen += n_l;
-        P.lv[l] = L;
-        P.gr[l] = grads ? grads[l] : PodLevelGrad{nullptr, nullptr, nullptr, nullptr};
-    }
-    if (anchors_seen != R) return POD_E_INVALID;
-    P.n_levels = cfg->n_levels; P.A = cfg->num_anchors; P.K = cfg->num_classes; P.R = R; P.n_images = cfg->n_runs; P.n_gt = n_gt;
-    P.M = energy ? num_samples : 0; P.has_grads = grads ? 1 : 0; P.beta = smooth_l1_beta;
-    for (int i = 0; i < 4; ++i) P.wts[i] = cfg->box_weights[i];
-    P.seed = cfg->philox_seed;
-    P.labels = labels; P.matched_gt = matched_gt; P.gt_boxes = gt_boxes; P.anchors = anchors;
-    P.eps = energy ? eps_reg : nullptr; P.eps_out = energy ? eps_out : nullptr; P.w = w; P.partials = partials;
+    int64_t n_blocks = 0;
+    // what pod_train_loss refuses, and: both losses need the diagonal covariance head
+    if (pod::score_params(cfg, levels, grads, labels, matched_gt, gt_boxes, n_gt, anchors, R, 4, kind, 2, POD_REG_LOSS_ENERGY, num_samples,
+                          smooth_l1_beta, eps_reg, eps_out, w, partials, sum, P, n_blocks) != POD_OK) return POD_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)n_blocks, (unsigned)cfg->n_runs);
-    if (energy)
+    if (kind == POD_REG_LOSS_ENERGY)
         hipLaunchKernelGGL(pod::k_reg_score<POD_REG_LOSS_ENERGY>, grid, dim3(pod::LOSS_BLOCK), 0, st, P);
     else
         hipLaunchKernelGGL(pod::k_reg_score<POD_REG_LOSS_MOMENTS>, grid, dim3(pod::LOSS_BLOCK), 0, st, P);

@@ -108,8 +108,10 @@ class _HeadTrain(torch.autograd.Function):
         if not all(conv_forms.wino_of(c).split for c in head_convs(head)):
             raise hip.PodError("head.forward_train needs the split Winograd kernel for every conv of the head (C % 16 == 0, POD_WINO_SPLIT=1)")
         x0 = x0.detach()
-        # the training form of the head's launch plan (modeling._trunk_plan): B images per level, every layer's output kept
-        st = modeling.HeadPlan(x0=x0, levels=list(levels), dropout=False, grouped=True, images=int(B), channels=max(int(x0.shape[1]), 64))
+        # the training form of the head's launch plan (modeling._trunk_plan): B images per level, every layer's output kept; the tables'
+        # channel bound covers the widest conv of the head (the full covariance predictor: 90 outputs, padded to 128)
+        widest = max(conv_forms.wino_of(c).Kpad for c in head_convs(head))
+        st = modeling.HeadPlan(x0=x0, levels=list(levels), dropout=False, grouped=True, images=int(B), channels=max(int(x0.shape[1]), 64, widest))
         last = [buf for buf, _ in head._trunks([(0, B), (1, B)], st)]
         saved = st.saved                                # saved[sid][l] = (input, output) of trunk layer l
         preds = [(head.cls_score, 0), (head.bbox_pred, 1)] + ([(head.cls_var, 0)] if head.cls_var is not None else []) + \

@@ -32,6 +32,7 @@ POD_VIS_LABEL_BOX, POD_VIS_LABEL_GLYPH = 3, 4
 POD_RESIZE_MAX_SIDE = 32768
 POD_SGD_CHUNK = 4096
 POD_REG_LOSS_MOMENTS, POD_REG_LOSS_ENERGY, POD_MAX_REG_SAMPLES = 1, 2, 4096
+POD_FULL_COV_NLL, POD_FULL_COV_MOMENTS, POD_FULL_COV_ENERGY = 1, 2, 3
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
@@ -47,12 +48,12 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad", "pod_col2im3x3s2_cl", "pod_upsample2_sum_cl",
            "pod_conv1x1_wgrad_strided_partials", "pod_conv1x1_wgrad_strided", "pod_subsample2_scatter_cl",
            "pod_sgd_chunk_map", "pod_sgd_step", "pod_grad_bucket_layout", "pod_grad_pack",
-           "pod_reg_score_partials", "pod_reg_score_loss")
+           "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
-                 "pod_grad_bucket_layout", "pod_reg_score_partials")
+                 "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -261,6 +262,9 @@ def load() -> ctypes.CDLL:
     lib.pod_reg_score_partials.restype = c_int64
     lib.pod_reg_score_loss.argtypes = [POINTER(PodConfig), POINTER(PodLevel), POINTER(PodLevelGrad), P, P, P, c_int32, P, c_int32,
                                        c_int32, c_int32, c_float, P, P, P, P, P, P]
+    lib.pod_full_cov_partials.argtypes = lib.pod_reg_score_partials.argtypes
+    lib.pod_full_cov_partials.restype = c_int64
+    lib.pod_full_cov_loss.argtypes = lib.pod_reg_score_loss.argtypes
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -6,6 +6,8 @@
     (out["loss_cls"] + out["loss_box_reg"]).backward()                        # gradients at the four head outputs
     crit = ProbabilisticLosses(num_classes=7, bbox_cov_loss="energy_loss", bbox_cov_num_samples=1000)          # BBOX_COV_LOSS.NAME: the
     # covariance term of loss_box_reg is the energy score (or "second_moment_matching") in place of the NLL: a second launch, K27
+    # head outputs whose reg_var planes have A * 10 channels (BBOX_COV_LOSS.COVARIANCE_TYPE: full) take the same names to K28: the
+    # Gaussian NLL of the 4 x 4 Cholesky factor, moment matching or the energy score of the full covariance (`covariance_route`)
 
 Everything stays on the device: no call here reads a value back.  The convolutions have no backward pass -- the gradients stop at the
 per-level head tensors (`(N, A*C, H, W)` planes, N = images), which is what a trainer of the head, or a checkpoint selection by
@@ -97,7 +99,7 @@ def _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, a
         lv[l].delta, lv[l].run_stride_delta = plane("delta", delta[l], l, 4, h, w_)
         if cls_var is not None:
             lv[l].cls_var, _ = plane("cls_var", cls_var[l], l, num_classes, h, w_)
-        if reg_var is not None and D > 0:      # (D = 10 is refused by the entry point: the reference has no loss for it)
+        if reg_var is not None and D > 0:
             lv[l].reg_var, lv[l].run_stride_reg = plane("reg_var", reg_var[l], l, D, h, w_)
         lv[l].H, lv[l].W, lv[l].anchor_base = h, w_, base
         base += h * w_ * num_anchors
@@ -155,6 +157,43 @@ def train_loss_sums(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, 
 
 BBOX_COV_LOSSES = ("none", "negative_log_likelihood", "second_moment_matching", "energy_loss")      # BBOX_COV_LOSS.NAME
 REG_SCORE_KINDS = {"second_moment_matching": hip.POD_REG_LOSS_MOMENTS, "energy_loss": hip.POD_REG_LOSS_ENERGY}
+FULL_COV_KINDS = {"none": hip.POD_FULL_COV_NLL, "negative_log_likelihood": hip.POD_FULL_COV_NLL,          # COVARIANCE_TYPE: full (K28)
+                  "second_moment_matching": hip.POD_FULL_COV_MOMENTS, "energy_loss": hip.POD_FULL_COV_ENERGY}
+
+
+def _score_launch(entry: str, kind_id: int, kind: str, cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors, num_classes,
+                  num_samples, box_weights, beta, cls_samples, eps_reg, eps_reg_out, w, grads, seed, energy: bool):
+    """One launch of a covariance objective on the positive anchors, pod_reg_score_loss (K27) or pod_full_cov_loss (K28): the two take one
+    argument list.  Returns (sum double[1], grads with the new reg_var planes in fourth place, or None)."""
+    if reg_var is None:
+        raise hip.PodError("{} needs the box covariance head (reg_var planes)".format(kind))
+    lib = hip.load()
+    cfg, lv, a, gt = _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors, num_classes, box_weights,
+                                    cls_samples, seed, None)
+    L, n, dev, r, g = len(cls), int(cls[0].shape[0]), cls[0].device, int(a.shape[0]), int(gt.shape[0])
+    M = int(num_samples)
+    for name, t in (("eps_reg", eps_reg), ("eps_reg_out", eps_reg_out)):
+        if t is not None and not (energy and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                                  and tuple(t.shape) == (M + 1, n * r, 4)):
+            raise hip.PodError("{}: expected contiguous fp32 {} on {} and the energy loss".format(name, (M + 1, n * r, 4), dev))
+    garr = None
+    if grads is not None:
+        w = _weights_ok(w, dev)
+        g_reg_var = [torch.empty_like(t) for t in reg_var]
+        grads = (grads[0], grads[1], grads[2], g_reg_var)
+        garr = (hip.PodLevelGrad * hip.POD_MAX_LEVELS)()
+        for l in range(L):
+            if tuple(grads[1][l].shape) != tuple(delta[l].shape) or not grads[1][l].is_contiguous():
+                raise hip.PodError("grads: delta plane {} is not laid out as delta[{}]".format(l, l))
+            garr[l].delta, garr[l].reg_var = grads[1][l].data_ptr(), g_reg_var[l].data_ptr()
+    n_part = int(getattr(lib, entry.replace("_loss", "_partials"))(cfg, lv))
+    partials = torch.empty((max(n_part, 1),), dtype=torch.float64, device=dev)
+    total = torch.empty((1,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        hip.check(getattr(lib, entry)(cfg, lv, garr, hip.ptr(labels), hip.ptr(matched_gt), hip.ptr(gt) if g else None, g, hip.ptr(a), r,
+                                      kind_id, M, float(beta), hip.ptr(eps_reg), hip.ptr(eps_reg_out),
+                                      hip.ptr(w) if grads is not None else None, hip.ptr(partials), hip.ptr(total), hip.current_stream()), entry)
+    return total, grads
 
 
 def reg_score_sum(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, *, kind: str,
@@ -168,43 +207,47 @@ def reg_score_sum(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, an
     Returns (sum double[1], grads with the new reg_var planes in fourth place, or None)."""
     if kind not in REG_SCORE_KINDS:
         raise ValueError("reg_score_sum: kind is one of {}, got {!r}".format(sorted(REG_SCORE_KINDS), kind))
-    if reg_var is None:
-        raise hip.PodError("{} needs the box covariance head (reg_var planes)".format(kind))
-    lib = hip.load()
-    cfg, lv, a, gt = _launch_inputs(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors, num_classes, box_weights,
-                                    cls_samples, seed, None)
-    L, n, dev, r, g = len(cls), int(cls[0].shape[0]), cls[0].device, int(a.shape[0]), int(gt.shape[0])
-    M = int(num_samples)
-    for name, t in (("eps_reg", eps_reg), ("eps_reg_out", eps_reg_out)):
-        if t is not None and not (kind == "energy_loss" and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
-                                  and tuple(t.shape) == (M + 1, n * r, 4)):
-            raise hip.PodError("{}: expected contiguous fp32 {} on {} and the energy loss".format(name, (M + 1, n * r, 4), dev))
-    garr = None
-    if grads is not None:
-        w = _weights_ok(w, dev)
-        g_reg_var = [torch.empty_like(t) for t in reg_var]
-        grads = (grads[0], grads[1], grads[2], g_reg_var)
-        garr = (hip.PodLevelGrad * hip.POD_MAX_LEVELS)()
-        for l in range(L):
-            if tuple(grads[1][l].shape) != tuple(delta[l].shape) or not grads[1][l].is_contiguous():
-                raise hip.PodError("grads: delta plane {} is not laid out as delta[{}]".format(l, l))
-            garr[l].delta, garr[l].reg_var = grads[1][l].data_ptr(), g_reg_var[l].data_ptr()
-    n_part = int(lib.pod_reg_score_partials(cfg, lv))
-    partials = torch.empty((max(n_part, 1),), dtype=torch.float64, device=dev)
-    total = torch.empty((1,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        hip.check(lib.pod_reg_score_loss(cfg, lv, garr, hip.ptr(labels), hip.ptr(matched_gt), hip.ptr(gt) if g else None, g, hip.ptr(a), r,
-                                         REG_SCORE_KINDS[kind], M, float(beta), hip.ptr(eps_reg), hip.ptr(eps_reg_out),
-                                         hip.ptr(w) if grads is not None else None, hip.ptr(partials), hip.ptr(total), hip.current_stream()),
-                  "pod_reg_score_loss")
-    return total, grads
+    return _score_launch("pod_reg_score_loss", REG_SCORE_KINDS[kind], kind, cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors,
+                         num_anchors, num_classes, num_samples, box_weights, beta, cls_samples, eps_reg, eps_reg_out, w, grads, seed,
+                         kind == "energy_loss")
+
+
+def full_cov_sum(cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors, num_anchors: int, num_classes: int, *, kind: str,
+                 num_samples: int = 1000, box_weights=(1.0, 1.0, 1.0, 1.0), beta: float = 0.0, cls_samples: int = 0,
+                 eps_reg: Optional[torch.Tensor] = None, eps_reg_out: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None,
+                 grads=None, seed: int = 0):
+    """One pod_full_cov_loss launch (K28), as reg_score_sum is K27's: the sum the loss name `kind` selects for the FULL covariance head
+    (reg_var planes of A * 10 channels) -- `none` / `negative_log_likelihood`: the Gaussian NLL, `second_moment_matching`, `energy_loss` --
+    over the positive anchors.  Every argument and the result as reg_score_sum's; the reg_var planes allocated here have ten channels."""
+    if kind not in FULL_COV_KINDS:
+        raise ValueError("full_cov_sum: kind is one of {}, got {!r}".format(sorted(FULL_COV_KINDS), kind))
+    return _score_launch("pod_full_cov_loss", FULL_COV_KINDS[kind], kind, cls, delta, cls_var, reg_var, labels, matched_gt, gt_boxes, anchors,
+                         num_anchors, num_classes, num_samples, box_weights, beta, cls_samples, eps_reg, eps_reg_out, w, grads, seed,
+                         kind == "energy_loss")
+
+
+def covariance_route(bbox_cov_loss: str, num_anchors: int, reg_var_channels: Optional[int]):
+    """Which launch evaluates the covariance term of loss_box_reg, from the loss name and the reg_var planes' channel count: (None, None)
+    = pod_train_loss alone (no covariance head, or the diagonal head's NLL), else (the wrapper of the second launch, its kind).  A * 4
+    channels: the diagonal head, today's paths; A * 10: the full covariance, every name through pod_full_cov_loss."""
+    if bbox_cov_loss not in BBOX_COV_LOSSES:
+        raise ValueError("Invalid regression loss name {!r}: BBOX_COV_LOSS.NAME is one of {}".format(bbox_cov_loss, ", ".join(BBOX_COV_LOSSES)))
+    if reg_var_channels is None:
+        return None, None
+    if reg_var_channels == num_anchors * 4:
+        return (reg_score_sum, bbox_cov_loss) if bbox_cov_loss in REG_SCORE_KINDS else (None, None)
+    if reg_var_channels == num_anchors * 10:
+        return full_cov_sum, bbox_cov_loss
+    raise hip.PodError("reg_var planes of {} channels: {} anchor shapes have {} (COVARIANCE_TYPE diagonal) or {} (full)".format(
+        reg_var_channels, num_anchors, num_anchors * 4, num_anchors * 10))
 
 
 class _TrainLoss(torch.autograd.Function):
     """(loss_cls, loss_box_reg) = (w[0] cls_sum, w[1] std_reg_sum + w[2] cov_reg_sum), differentiable with respect to the per-level
     head tensors: forward is one pod_train_loss launch that also writes the gradient planes, backward scales them.  With
-    `second_moment_matching` or `energy_loss` the covariance sum and its gradients come from a second launch, pod_reg_score_loss, on the
-    planes the first one wrote without the reg_var head."""
+    `second_moment_matching` or `energy_loss`, and with the full covariance head under every name, the covariance sum and its gradients come
+    from a second launch, pod_reg_score_loss or pod_full_cov_loss (`covariance_route`), on the planes the first one wrote without the
+    reg_var head."""
 
     @staticmethod
     def forward(ctx, meta, w, *tensors):
@@ -213,16 +256,16 @@ class _TrainLoss(torch.autograd.Function):
         cls, delta = ts[:L], ts[L:2 * L]
         cls_var = ts[2 * L:3 * L] if has_cv else None
         reg_var = ts[(2 + has_cv) * L:(3 + has_cv) * L] if has_rv else None
-        score = meta.get("score_kind") if has_rv else None
-        sums, grads = train_loss_sums(cls, delta, cls_var, None if score else reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"],
+        second, score = (meta.get("score_launch"), meta.get("score_kind")) if has_rv else (None, None)
+        sums, grads = train_loss_sums(cls, delta, cls_var, None if second else reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"],
                                       meta["anchors"], meta["num_anchors"], meta["num_classes"], box_weights=meta["box_weights"], alpha=meta["alpha"],
                                       gamma=meta["gamma"], beta=meta["beta"], cls_samples=meta["cls_samples"], eps=meta["eps"],
                                       eps_out=meta.get("eps_out"), w=w, want_grads=True, seed=meta["seed"])
-        if score:
-            total, grads = reg_score_sum(cls, delta, cls_var, reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"], meta["anchors"],
-                                         meta["num_anchors"], meta["num_classes"], kind=score, num_samples=meta["score_samples"],
-                                         box_weights=meta["box_weights"], beta=meta["beta"], cls_samples=meta["cls_samples"],
-                                         eps_reg=meta.get("eps_reg"), eps_reg_out=meta.get("eps_reg_out"), w=w, grads=grads, seed=meta["seed"])
+        if second:
+            total, grads = second(cls, delta, cls_var, reg_var, meta["labels"], meta["matched_gt"], meta["gt_boxes"], meta["anchors"],
+                                  meta["num_anchors"], meta["num_classes"], kind=score, num_samples=meta["score_samples"],
+                                  box_weights=meta["box_weights"], beta=meta["beta"], cls_samples=meta["cls_samples"],
+                                  eps_reg=meta.get("eps_reg"), eps_reg_out=meta.get("eps_reg_out"), w=w, grads=grads, seed=meta["seed"])
             sums[2:3].copy_(total)
         ctx.meta = (L, has_cv, has_rv)
         ctx.planes = grads
@@ -279,7 +322,8 @@ class ProbabilisticLosses:
         fresh on every call) or the dense (S, N*R, K) normals to replay.  normalizer: None = the reference's moving average (PR:201-203,
         updated here from the labels' positives, on the device), else the number or device scalar to divide by (max(1, .)).  eps_reg /
         eps_reg_out: the energy loss's dense (M + 1, N*R, 4) normals, as eps / eps_out (reg_score_sum).  With the covariance head, the
-        covariance term of loss_box_reg is the one `bbox_cov_loss` names ("none": the NLL, as for every head with reg_var planes)."""
+        covariance term of loss_box_reg is the one `bbox_cov_loss` names ("none": the NLL, as for every head with reg_var planes); reg_var
+        planes of A * 10 channels are the full covariance (K28, `covariance_route`), any count but A * 4 and A * 10 raises."""
         ho = head_outputs
         dev = ho.cls[0].device
         K = self.num_classes
@@ -294,11 +338,12 @@ class ProbabilisticLosses:
             norm = normalizer.to(dev) if torch.is_tensor(normalizer) else torch.tensor(float(normalizer), device=dev)
         has_cv, has_rv = ho.cls_var is not None, ho.reg_var is not None
         w = self.weights(norm, has_cv, has_rv)
+        second, score = covariance_route(self.bbox_cov_loss, ho.num_anchors, int(ho.reg_var[0].shape[1]) if has_rv else None)
         meta = dict(levels=len(ho.cls), has_cls_var=int(has_cv), has_reg_var=int(has_rv), labels=labels, matched_gt=matched_gt, gt_boxes=gt_boxes,
                     anchors=ho.anchors if anchors is None else anchors, num_anchors=ho.num_anchors, num_classes=K, box_weights=self.box_reg_weights,
                     alpha=self.focal_loss_alpha, gamma=self.focal_loss_gamma, beta=self.smooth_l1_beta, cls_samples=self.cls_var_num_samples,
                     eps=eps, eps_out=eps_out, seed=(self.seed & 0xFFFFFFFF) | ((self.draws & 0xFFFFFFFF) << 32),
-                    score_kind=self.bbox_cov_loss if self.bbox_cov_loss in REG_SCORE_KINDS else None, score_samples=self.bbox_cov_num_samples,
+                    score_launch=second, score_kind=score, score_samples=self.bbox_cov_num_samples,
                     eps_reg=eps_reg, eps_reg_out=eps_reg_out)
         self.draws += 1
         tensors = list(ho.cls) + list(ho.delta) + (list(ho.cls_var) if has_cv else []) + (list(ho.reg_var) if has_rv else [])

@@ -60,7 +60,7 @@ import torch
 
 from . import checkpoint, losses
 from .apply_net import CocoImages, Prefetched, add_dataset_arguments, evaluation_category_map
-from .compute_losses import image_ground_truth
+from .compute_losses import covariance_overrides, image_ground_truth
 from .anchors import padded_size as _padded_size, resize_shortest_edge
 from .config import setup_config
 from .data_parallel import GradBucket, broadcast_tensors, gather_objects, rank_slice
@@ -400,7 +400,7 @@ def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
     ls.loss_normalizer = float(own["loss_normalizer"])
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
                                  epilog="A step takes SOLVER.IMS_PER_BATCH frames of ONE resized shape: the sampler batches frames of equal shape "
                                         "together, in data-set order; frames of a shape wait until a batch of them is complete.  Only the head "
@@ -417,6 +417,10 @@ def main(argv=None):
     ap.add_argument("--bbox-cov-loss", default=None, choices=losses.BBOX_COV_LOSSES,
                     help="overrides MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS.NAME: what trains the box covariance (energy_loss and "
                          "second_moment_matching run on K27).  No checkpoint records the name: with --resume it is again the config's, or this flag's")
+    ap.add_argument("--bbox-cov-type", default=None, choices=("diagonal", "full"),
+                    help="overrides BBOX_COV_LOSS.COVARIANCE_TYPE: `full` gives the head the ten-channel predictor of a 4 x 4 Cholesky factor, "
+                         "trained on K28 under every --bbox-cov-loss name.  With --resume the type is again the config's, or this flag's; a "
+                         "checkpoint of the other type is refused by its shapes")
     ap.add_argument("--bbox-cov-samples", type=int, default=0, help="overrides BBOX_COV_LOSS.NUM_SAMPLES, the energy loss's samples per positive anchor")
     ap.add_argument("--random-seed", type=int, default=0)
     ap.add_argument("--max-iter", type=int, default=-1, help="overrides SOLVER.MAX_ITER")
@@ -441,7 +445,11 @@ def main(argv=None):
                                                       "functional run, e.g. several ranks on one GPU with --share-gpu")
     ap.add_argument("--share-gpu", action="store_true", help="--data-parallel, functional check only: every rank uses cuda:0")
     ap.add_argument("--device", default="cuda:0")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = arg_parser().parse_args(argv)
     rank, world, group, own_group = 0, 1, None, False
     if args.data_parallel:
         import torch.distributed as dist
@@ -479,11 +487,7 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     if args.max_size_test > 0:
         cfg.INPUT.MAX_SIZE_TEST = args.max_size_test
     cfg.MODEL.DEVICE = args.device
-    cov = cfg.MODEL.PROBABILISTIC_MODELING.BBOX_COV_LOSS
-    if args.bbox_cov_loss is not None:
-        cov.NAME = args.bbox_cov_loss
-    if args.bbox_cov_samples > 0:
-        cov.NUM_SAMPLES = args.bbox_cov_samples
+    cov = covariance_overrides(cfg, args)
     freeze_at = cfg.MODEL.BACKBONE.get("FREEZE_AT", 2)
     if int(freeze_at) != 2:
         raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: the stem and res2 are frozen and res3 - res5 train (detectron2's "
