@@ -950,6 +950,64 @@ int pod_full_cov_loss(const PodConfig* cfg, const PodLevel* levels, const PodLev
                       int32_t kind, int32_t num_samples, float smooth_l1_beta, const float* eps_reg, float* eps_out,
                       const float* w, double* partials, double* sum, pod_stream_t stream);
 
+/* ---- K29  the optimiser's step under the whole SOLVER section: clipping, parameter groups, Nesterov, a guard (csrc/k29_sgd_solver.hip) ----
+ * Serves: detectron2's build_optimizer with SOLVER.NESTEROV, BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS and CLIP_GRADIENTS.* (maybe_add_gradient_clipping:
+ * `value` and `norm` per parameter tensor; `full_model`: one norm over all of them) and the trainer's stop at the first non-finite loss, on
+ * K25's table and chunk map.  Four new symbols, two new structures and four constants under POD_ABI_VERSION 18, as for K20 - K28: no entry or
+ * structure that existed changed, so the number stands.  pod_sgd_step, pod_sgd_chunk_map, pod_grad_pack and PodSgdTensor are what they were.
+ *
+ * For every element i of every tensor t of the table with a gradient, G = group[t], in fp32, each operation rounded on its own:
+ *     a0 = scale ? scale[i / per_channel] * grad[i] : grad[i]                       (K25's)
+ *     a  = a0                                          clip_type POD_SGD_CLIP_OFF
+ *        | a0 < -v ? -v : a0 > v ? v : a0              POD_SGD_CLIP_VALUE, v = clip_value (a NaN stays a NaN)
+ *        | coef[t] * a0                                POD_SGD_CLIP_NORM
+ *        | coef[n_tensors] * a0                        POD_SGD_CLIP_FULL_MODEL
+ *     g' = a + wd[G] * w[i];   m' = momentum * m[i] + g';   d = nesterov ? g' + momentum * m' : m';   w' = w[i] - lr[G] * d
+ *     m[i] = m';  w[i] = w';  if (folded) folded[i] = w' * scale[i / per_channel]
+ * With N_t^2 = sum_i a0_i^2: coef[t] = (float)c, c = clip_value / (sqrt(N_t^2) + 1e-6) in fp64, replaced by 1 where c > 1 (a NaN stays a NaN:
+ * torch's clip_grad_norm_, which always multiplies); coef[n_tensors] the same of N^2 = sum_t N_t^2 over the tensors with a gradient.  A
+ * tensor whose grad is NULL is in no norm, has coef 1 and is not stepped.  The squares and sums are fp64, of the fp32 a0, in an order that
+ * does not depend on the grid: per chunk of POD_SGD_CHUNK elements each lane in index order, wave_sum over the 64 lanes, the four
+ * wavefronts in order; a tensor's chunks in chunk order; the tensors in table order.  fp32 squares summed in fp64 cannot overflow: a finite
+ * gradient has a finite norm.
+ * The guard: a step is BAD when the N_t^2 of a tensor with a gradient, or a watched scalar, is not finite.  A bad step counts in
+ * status.bad_steps, the first one's `iteration` stays in status.first_bad_iteration; with `guard` set it also sets status.poisoned, and
+ * the step kernel of a poisoned workspace returns before its first store -- that step and every later one write no weight, momentum or
+ * folded filter, and leave the status as it is, until pod_sgd_solver_reset.  Nothing is read back: the owner reads the status when it likes.
+ * The workspace (device, 16-byte aligned, pod_sgd_solver_workspace_bytes(n_tensors, n_chunks) bytes, zeroed ONCE by its owner):
+ *     [0, 32) PodSgdSolverStatus;  [32, 32 + 8 n_chunks) partial, fp64, one per map entry;  then coef, fp32, n_tensors + 1.
+ * pod_sgd_step_solver: the table, its device room and the chunk map as for pod_sgd_step; `group` HOST and `group_dev` dev, n_tensors uint8
+ *   each, the same values (built once; the host copy is what is checked); `solver` HOST; `workspace` dev.  After K25's one table copy:
+ *   clip_type OFF or VALUE without guard is ONE launch, the step; otherwise THREE on `stream`, ordered by it: the squares per chunk
+ *   (partial), ONE workgroup that sums them per tensor and over the tensors and writes coef, status.last_norm = sqrt(N^2) and the rest of
+ *   the status, and the step, which reads coef and status.poisoned.  No atomics, no cooperative launch, no grid barrier, no read-back, no
+ *   scratch memory; two calls from one state give the same bits.  The default record (one group, OFF, no nesterov, no guard) is
+ *   handed to pod_sgd_step: K25's own launch, its bits and its time.  POD_E_INVALID before anything is enqueued: everything pod_sgd_step refuses (with lr[g], wd[g] in place of its lr
+ *   and weight_decay), solver NULL, n_groups outside 1..POD_SGD_MAX_GROUPS, group NULL with n_tensors > 0 or group[t] >= n_groups, lr[g] or
+ *   wd[g] (g < n_groups) negative or not finite, momentum outside [0, 1), nesterov with momentum 0, clip_type outside 0..3, clip_type != OFF
+ *   with a clip_value that is not finite and > 0, and with n_chunks > 0: workspace or group_dev NULL, workspace not on 16 bytes, a watch
+ *   pointer not on 4.  n_tensors == 0, or every n == 0: POD_OK, nothing enqueued.
+ * pod_sgd_solver_reset: zeroes the status (not partial or coef) on `stream`; POD_E_INVALID for a NULL or misaligned workspace. */
+#define POD_SGD_MAX_GROUPS 8
+#define POD_SGD_CLIP_OFF        0
+#define POD_SGD_CLIP_VALUE      1
+#define POD_SGD_CLIP_NORM       2
+#define POD_SGD_CLIP_FULL_MODEL 3
+typedef struct PodSgdSolver {
+    int32_t n_groups;  int32_t nesterov;  int32_t clip_type;  int32_t guard;
+    float lr[POD_SGD_MAX_GROUPS];  float wd[POD_SGD_MAX_GROUPS];
+    float momentum;  float clip_value;
+    int64_t iteration;                 /* what a bad step leaves in status.first_bad_iteration */
+    const float* watch[4];             /* dev fp32 scalars that must be finite (the step's losses), NULL where unused */
+} PodSgdSolver;
+typedef struct PodSgdSolverStatus {
+    int64_t bad_steps;  int64_t first_bad_iteration;  double last_norm;  int32_t poisoned;  int32_t reserved;
+} PodSgdSolverStatus;
+size_t pod_sgd_solver_workspace_bytes(int32_t n_tensors, int64_t n_chunks);
+int pod_sgd_step_solver(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, int32_t n_tensors, const int32_t* chunk_map, int64_t n_chunks,
+                        const uint8_t* group, const uint8_t* group_dev, const PodSgdSolver* solver, void* workspace, pod_stream_t stream);
+int pod_sgd_solver_reset(void* workspace, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws, of the generator itself and of the f16 split -- is declared in
  * include/pod_mi355x_test.h: the library exports those entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -30,29 +30,7 @@ __global__ void __launch_bounds__(TABLE_THREADS) k_sgd_step(const PodSgdTensor* 
                                                             const int64_t n_chunks, const SgdHyper h) {
     table_chunk_walk(
         table, n_tensors, chunk_map, n_chunks,
-        [&](int32_t, const PodSgdTensor& d, const int64_t i) {                 // FrozenBN's s of the four elements at i (1 where there is none)
-            f32x4 s = {1.f, 1.f, 1.f, 1.f};
-            if (d.scale) {
-                // the channel of element i and how far into it i lies: one division per trip, then a walk (per_channel may be 1)
-                int64_t c;
-                if (((uint64_t)i | (uint64_t)d.per_channel) >> 32) {
-                    c = i / d.per_channel;
-                } else {
-                    c = (int64_t)((uint32_t)i / (uint32_t)d.per_channel);
-                }
-                int64_t r = i - c * d.per_channel;
-                const int64_t c_last = (d.n - 1) / d.per_channel;              // (never read behind the last channel for lanes past a tail)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    s[j] = d.scale[c < c_last ? c : c_last];
-                    if (++r == d.per_channel) {
-                        r = 0;
-                        ++c;
-                    }
-                }
-            }
-            return s;
-        },
+        [&](int32_t, const PodSgdTensor& d, const int64_t i) { return table_scale4(d, i); },      // FrozenBN's s of the four elements at i
         [&](const PodSgdTensor& d, const int64_t i, const f32x4 s) {
             const f32x4 g = *reinterpret_cast<const f32x4*>(d.grad + i);
             const f32x4 w4 = *reinterpret_cast<const f32x4*>(d.w + i);

@@ -33,6 +33,8 @@ POD_RESIZE_MAX_SIDE = 32768
 POD_SGD_CHUNK = 4096
 POD_REG_LOSS_MOMENTS, POD_REG_LOSS_ENERGY, POD_MAX_REG_SAMPLES = 1, 2, 4096
 POD_FULL_COV_NLL, POD_FULL_COV_MOMENTS, POD_FULL_COV_ENERGY = 1, 2, 3
+POD_SGD_MAX_GROUPS = 8
+POD_SGD_CLIP_OFF, POD_SGD_CLIP_VALUE, POD_SGD_CLIP_NORM, POD_SGD_CLIP_FULL_MODEL = 0, 1, 2, 3
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
@@ -48,12 +50,13 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad", "pod_col2im3x3s2_cl", "pod_upsample2_sum_cl",
            "pod_conv1x1_wgrad_strided_partials", "pod_conv1x1_wgrad_strided", "pod_subsample2_scatter_cl",
            "pod_sgd_chunk_map", "pod_sgd_step", "pod_grad_bucket_layout", "pod_grad_pack",
-           "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss")
+           "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss",
+           "pod_sgd_solver_workspace_bytes", "pod_sgd_step_solver", "pod_sgd_solver_reset")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
-                 "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials")
+                 "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -130,6 +133,18 @@ class PodLevelGrad(Structure):
 class PodSgdTensor(Structure):
     """include/pod_mi355x.h: PodSgdTensor (K25, one tensor of pod_sgd_step's table)."""
     _fields_ = [(n, c_void_p) for n in ("w", "grad", "momentum", "folded", "scale")] + [("n", c_int64), ("per_channel", c_int64)]
+
+
+class PodSgdSolver(Structure):
+    """include/pod_mi355x.h: PodSgdSolver (K29, the settings of one pod_sgd_step_solver call)."""
+    _fields_ = [(n, c_int32) for n in ("n_groups", "nesterov", "clip_type", "guard")] + \
+               [("lr", c_float * POD_SGD_MAX_GROUPS), ("wd", c_float * POD_SGD_MAX_GROUPS), ("momentum", c_float), ("clip_value", c_float),
+                ("iteration", c_int64), ("watch", c_void_p * 4)]
+
+
+class PodSgdSolverStatus(Structure):
+    """include/pod_mi355x.h: PodSgdSolverStatus (K29, the first 32 bytes of the solver's workspace)."""
+    _fields_ = [("bad_steps", c_int64), ("first_bad_iteration", c_int64), ("last_norm", c_double), ("poisoned", c_int32), ("reserved", c_int32)]
 
 
 class PodError(RuntimeError):
@@ -265,6 +280,10 @@ def load() -> ctypes.CDLL:
     lib.pod_full_cov_partials.argtypes = lib.pod_reg_score_partials.argtypes
     lib.pod_full_cov_partials.restype = c_int64
     lib.pod_full_cov_loss.argtypes = lib.pod_reg_score_loss.argtypes
+    lib.pod_sgd_solver_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.pod_sgd_solver_workspace_bytes.restype = c_size_t
+    lib.pod_sgd_step_solver.argtypes = [POINTER(PodSgdTensor), P, c_int32, P, c_int64, P, P, POINTER(PodSgdSolver), P, P]
+    lib.pod_sgd_solver_reset.argtypes = [P, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -2,7 +2,7 @@
 
     python -m pod_compare_amd.train_head --coco-json <gt.json> --image-root <dir> --data-dir <checkpoints root> \
         --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn | --train-backbone]
-        [--fused-step] [--random-flip] [--resume] [--data-parallel [--backend nccl|gloo] [--share-gpu]]
+        [--fused-step] [--guard-nonfinite] [--random-flip] [--resume] [--data-parallel [--backend nccl|gloo] [--share-gpu]]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
 shape together; a shape's frames wait until a batch of them is complete), the frozen backbone + FPN per image under no_grad through the
@@ -28,6 +28,18 @@ W.  Only FREEZE_AT = 2 is supported.
 SGD + refold: the trainer owns the momentum buffers, the kernel scales a folded filter's gradient by s, steps the master and rewrites the
 folded filter, and the written tensors' versions are bumped so that the derived filters are rebuilt.  Without the flag torch.optim.SGD steps.
 
+The solver: beside BASE_LR, MOMENTUM, WEIGHT_DECAY, STEPS, GAMMA, WARMUP_ITERS and WARMUP_FACTOR, SOLVER.NESTEROV, BIAS_LR_FACTOR and
+WEIGHT_DECAY_BIAS (the biases of the head's and the FPN's convolutions as a parameter group of their own), CLIP_GRADIENTS.* (`value` and
+`norm` per parameter tensor, `full_model` over all of them), LR_SCHEDULER_NAME (WarmupMultiStepLR, WarmupCosineLR) and WARMUP_METHOD
+(linear, constant) are honoured by both optimisers -- torch's with two parameter groups, nesterov and torch's clipping utilities, the
+fused one with K29 (pod_sgd_step_solver) -- and a value this trainer does not run is refused by name before a model is built
+(`solver_settings`).  A YAML that names none of them runs what ran before them, call for call.
+
+--guard-nonfinite (implies --fused-step): detectron2's stop at the first non-finite loss, without a synchronisation per step.  The fused
+step checks every tensor's gradient norm and the step's two losses on the device; a bad step, and every step after it, writes nothing,
+and the next log line or checkpoint (`HeadTrainer.check_finite`) raises FloatingPointError naming the first bad iteration before
+anything is written: the weights are those from before it.
+
 --random-flip: detectron2's RandomFlip(horizontal), probability 0.5.  The draw is made in the main loop in data order from a generator
 seeded with --random-seed; the frame is flipped on the device and its boxes follow HFlipTransform (`hflip_boxes`).
 
@@ -48,11 +60,14 @@ losses) and writes checkpoints, whose `pod_trainer` then carries `world` and `ra
 the same world size only.  SOLVER.IMS_PER_BATCH must be a multiple of W.
 
 Still NOT the reference's full trainer: the all-reduce does not overlap the backward pass, and a data-parallel rank reads its frames
-without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies).
+without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies); under settings that
+compute a gradient norm, or the guard, the solver's 32-byte status is read with it and before a checkpoint.
 """
 import argparse
 import bisect
+import dataclasses
 import json
+import math
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -68,7 +83,7 @@ from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import conv_params, head_convs
 from .resnet_train import FoldedMasters, res2_maps, resnet_forward_train, trainable_convs, unfolded_pairs
 from .probabilistic_inference import build_model
-from .sgd_step import FusedSGD, SgdEntry
+from .sgd_step import LR_SCHEDULERS, WARMUP_METHODS, FusedSGD, SgdEntry, SolverSettings
 
 
 def warmup_multistep_lr(iteration: int, base_lr: float, steps: Sequence[int], gamma: float, warmup_iters: int, warmup_factor: float) -> float:
@@ -79,6 +94,80 @@ def warmup_multistep_lr(iteration: int, base_lr: float, steps: Sequence[int], ga
         a = iteration / float(warmup_iters)
         w = warmup_factor * (1.0 - a) + a
     return base_lr * w * gamma ** bisect.bisect_right(list(steps), iteration)
+
+
+def warmup_factor_at(iteration: int, warmup_iters: int, warmup_factor: float, method: str = "linear") -> float:
+    """detectron2's _get_warmup_factor_at_iter: 1 from warmup_iters on; below it `constant`: warmup_factor, `linear`: warmup_factor (1 - a) + a."""
+    if iteration >= warmup_iters:
+        return 1.0
+    if method == "constant":
+        return float(warmup_factor)
+    if method != "linear":
+        raise ValueError("unknown warm-up method {!r}".format(method))
+    a = iteration / float(warmup_iters)
+    return warmup_factor * (1.0 - a) + a
+
+
+def warmup_cosine_lr(iteration: int, base_lr: float, max_iter: int, warmup_iters: int, warmup_factor: float, method: str = "linear") -> float:
+    """detectron2's WarmupCosineLR: base_lr * w(it) * 0.5 (1 + cos(pi it / max_iter))."""
+    return base_lr * warmup_factor_at(iteration, warmup_iters, warmup_factor, method) * 0.5 * (1.0 + math.cos(math.pi * iteration / max_iter))
+
+
+def scheduled_lr(iteration: int, base_lr: float, steps: Sequence[int], gamma: float, warmup_iters: int, warmup_factor: float,
+                 lr_scheduler_name: str = "WarmupMultiStepLR", warmup_method: str = "linear", max_iter: int = 0) -> float:
+    """The learning rate of `iteration` for a group whose base rate is base_lr, in Python doubles as torch's LambdaLR forms it.  The default
+    names give warmup_multistep_lr itself, to the bit."""
+    if lr_scheduler_name == "WarmupCosineLR":
+        return warmup_cosine_lr(iteration, base_lr, max(1, int(max_iter)), warmup_iters, warmup_factor, warmup_method)
+    if lr_scheduler_name != "WarmupMultiStepLR":
+        raise ValueError("unknown learning rate schedule {!r}".format(lr_scheduler_name))
+    if warmup_method == "linear":
+        return warmup_multistep_lr(iteration, base_lr, steps, gamma, warmup_iters, warmup_factor)
+    return base_lr * warmup_factor_at(iteration, warmup_iters, warmup_factor, warmup_method) * gamma ** bisect.bisect_right(list(steps), iteration)
+
+
+def solver_settings(cfg, guard_nonfinite: bool = False) -> SolverSettings:
+    """SOLVER.* beyond what train_head always read, as SolverSettings; SystemExit naming the key for a value this trainer does not run.  A
+    key that is absent has detectron2's default, which is what ran before the keys were read: clipping that is not ENABLED is "off", a
+    WEIGHT_DECAY_BIAS equal to WEIGHT_DECAY is no group of its own.  WEIGHT_DECAY_NORM is accepted and has no effect (every norm is frozen)."""
+    s = cfg.SOLVER
+    clip = s.get("CLIP_GRADIENTS", None) or {}
+
+    def number(key, value, positive=False):
+        try:
+            x = float(value)
+        except (TypeError, ValueError):
+            x = float("nan")
+        if isinstance(value, bool) or not math.isfinite(x) or x < 0 or (positive and x == 0):
+            raise SystemExit("SOLVER.{} = {!r} is not supported: a finite {} number".format(key, value, "positive" if positive else "non-negative"))
+        return x
+
+    def one_of(key, value, known):
+        if value not in known:
+            raise SystemExit("SOLVER.{} = {!r} is not supported: one of {}".format(key, value, ", ".join(known)))
+        return value
+
+    clip_type = one_of("CLIP_GRADIENTS.CLIP_TYPE", clip.get("CLIP_TYPE", "value"), ("value", "norm", "full_model"))
+    clip_value = number("CLIP_GRADIENTS.CLIP_VALUE", clip.get("CLIP_VALUE", 1.0), positive=True)
+    if float(clip.get("NORM_TYPE", 2.0)) != 2.0:
+        raise SystemExit("SOLVER.CLIP_GRADIENTS.NORM_TYPE = {!r} is not supported: only the 2-norm is".format(clip.get("NORM_TYPE")))
+    enabled = bool(clip.get("ENABLED", False))
+    wd, wd_bias = float(s.WEIGHT_DECAY), s.get("WEIGHT_DECAY_BIAS", None)
+    wd_bias = None if wd_bias is None else number("WEIGHT_DECAY_BIAS", wd_bias)
+    nesterov = bool(s.get("NESTEROV", False))
+    if nesterov and float(s.MOMENTUM) <= 0:
+        raise SystemExit("SOLVER.NESTEROV needs SOLVER.MOMENTUM > 0, got {!r}".format(s.MOMENTUM))
+    return SolverSettings(nesterov=nesterov, bias_lr_factor=number("BIAS_LR_FACTOR", s.get("BIAS_LR_FACTOR", 1.0)),
+                          weight_decay_bias=None if wd_bias is None or wd_bias == wd else wd_bias,
+                          clip_type=clip_type if enabled else "off", clip_value=clip_value if enabled else 1.0,
+                          lr_scheduler_name=one_of("LR_SCHEDULER_NAME", s.get("LR_SCHEDULER_NAME", "WarmupMultiStepLR"), LR_SCHEDULERS),
+                          warmup_method=one_of("WARMUP_METHOD", s.get("WARMUP_METHOD", "linear"), WARMUP_METHODS), guard_nonfinite=bool(guard_nonfinite))
+
+
+def parameter_groups(names: Sequence[str], settings: SolverSettings) -> List[int]:
+    """The group of each trained tensor by its detectron2 name: 1 for a parameter named `bias` (the head's and the FPN's convolutions have
+    them; the master weights of res3 - res5 have none), 0 for a weight -- all 0 when the settings give the biases nothing of their own."""
+    return [1 if settings.two_groups and n.rsplit(".", 1)[-1] == "bias" else 0 for n in names]
 
 
 def hflip_boxes(boxes: torch.Tensor, width) -> torch.Tensor:
@@ -95,13 +184,23 @@ class HeadTrainer:
 
     def __init__(self, model, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, steps: Sequence[int] = (60000, 80000),
                  gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0, train_fpn: bool = False,
-                 train_backbone: bool = False, shadow=None, fused_step: bool = False, data_parallel=None):
+                 train_backbone: bool = False, shadow=None, fused_step: bool = False, data_parallel=None, solver: Optional[SolverSettings] = None,
+                 guard_nonfinite: bool = False, max_iter: int = 0):
         """train_backbone: res3 - res5 train too (and the FPN: it lies between them and the head); `shadow`, the same model unfolded, gives
         the master weights and FrozenBN scales (resnet_train.FoldedMasters).  fused_step: the optimiser's step is pod_sgd_step (K25) on
         momentum buffers the trainer owns (`self.fused`), not torch's SGD; `self.opt` is the torch.optim.SGD either way (unused when fused).
         data_parallel: (rank, world, process group or None = the default one) -- this trainer is one rank of `world`: its gradients go
         through a bucket (`self.bucket`, data_parallel.GradBucket: K26, one all-reduce) and the fused step reads the rank mean from it.
-        Needs fused_step.  The loss state stays the rank's own, as under DistributedDataParallel."""
+        Needs fused_step.  The loss state stays the rank's own, as under DistributedDataParallel.
+        solver: the SolverSettings (solver_settings(cfg); None: the defaults, under which both optimisers are built and called as before
+        the settings existed).  Torch's path honours them with two parameter groups, nesterov and torch's clipping utilities; the fused
+        one with pod_sgd_step_solver (K29).  guard_nonfinite (needs fused_step): a step with a non-finite gradient or loss, and every
+        step after it, writes nothing; check_finite() raises.  max_iter: WarmupCosineLR's horizon."""
+        self.solver = solver if solver is not None else SolverSettings()
+        if guard_nonfinite and not self.solver.guard_nonfinite:
+            self.solver = dataclasses.replace(self.solver, guard_nonfinite=True)
+        if self.solver.guard_nonfinite and not fused_step:
+            raise ValueError("guard_nonfinite needs fused_step: the guard is the fused step's (pod_sgd_step_solver)")
         if data_parallel is not None and not fused_step:
             raise ValueError("data_parallel needs fused_step: the averaged gradients are stepped from the bucket by pod_sgd_step")
         self.model, self.train_backbone = model, bool(train_backbone)
@@ -121,7 +220,19 @@ class HeadTrainer:
             self.params += self.masters.params
         self.schedule = dict(base_lr=float(base_lr), steps=tuple(int(s) for s in steps), gamma=float(gamma), warmup_iters=int(warmup_iters),
                              warmup_factor=float(warmup_factor))
-        self.opt = torch.optim.SGD(self.params, lr=float(base_lr), momentum=float(momentum), weight_decay=float(weight_decay))
+        self.max_iter = int(max_iter)
+        self.groups = parameter_groups(self.param_names(), self.solver) if self.solver.two_groups else [0] * len(self.params)
+        if self.solver.plain_step:
+            self.opt = torch.optim.SGD(self.params, lr=float(base_lr), momentum=float(momentum), weight_decay=float(weight_decay))
+        else:                                     # detectron2's build_optimizer: the biases in a group of their own
+            wd_bias = float(weight_decay) if self.solver.weight_decay_bias is None else float(self.solver.weight_decay_bias)
+            by_group = [[p for p, g in zip(self.params, self.groups) if g == k] for k in (0, 1)]
+            param_groups = [{"params": by_group[0]}]
+            if by_group[1]:
+                param_groups.append({"params": by_group[1], "lr": float(base_lr) * self.solver.bias_lr_factor, "weight_decay": wd_bias})
+            self.opt = torch.optim.SGD(param_groups, lr=float(base_lr), momentum=float(momentum), weight_decay=float(weight_decay),
+                                       nesterov=self.solver.nesterov)
+        self._grad_norm = None                    # torch's path: the norm clip_grad_norm_ returned over the full model (a device scalar)
         self.iteration = int(iteration)
         self.momentum_mu = float(momentum)
         self.fused, self.bucket, self.rank, self.world = None, None, 0, 1
@@ -135,9 +246,17 @@ class HeadTrainer:
                 if not 0 <= self.rank < self.world:
                     raise ValueError("data_parallel: rank {} of world {}".format(self.rank, self.world))
                 self.bucket = GradBucket(entries, self.world, group)
-            self.fused = FusedSGD(entries, momentum=float(momentum), weight_decay=float(weight_decay), grads_from=self.bucket)
-        self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
+            self.fused = FusedSGD(entries, momentum=float(momentum), weight_decay=float(weight_decay), grads_from=self.bucket,
+                                  solver=self.solver, groups=self.groups)
+        self._lrs = self.lrs_at(self.iteration)
+        self._lr = self._lrs[0]
         self._losses = None
+
+    def lrs_at(self, iteration: int) -> List[float]:
+        """The learning rate of `iteration` per parameter group: the schedule on each group's own base rate, as torch's LambdaLR forms it."""
+        sch = dict(self.schedule, lr_scheduler_name=self.solver.lr_scheduler_name, warmup_method=self.solver.warmup_method, max_iter=self.max_iter)
+        base = sch.pop("base_lr")
+        return [scheduled_lr(iteration, b, **sch) for b in ([base, base * self.solver.bias_lr_factor] if self.solver.two_groups else [base])]
 
     @property
     def lr(self) -> float:
@@ -221,9 +340,10 @@ class HeadTrainer:
     def forward_backward(self, feats, padded, image_hw, gt_boxes, gt_classes, eps=None, normalizer=None) -> Dict[str, torch.Tensor]:
         """The first part of a step: this iteration's learning rate, the head's forward, the losses and backward().  Leaves the gradients
         in .grad and returns the losses (device scalars)."""
-        lr = self._lr = warmup_multistep_lr(self.iteration, **self.schedule)
-        for g in self.opt.param_groups:
-            g["lr"] = lr
+        self._lrs = self.lrs_at(self.iteration)
+        self._lr = self._lrs[0]
+        for k, g in enumerate(self.opt.param_groups):
+            g["lr"] = self._lrs[min(k, len(self._lrs) - 1)]
         out = self.model.head.forward_train(feats, self.model.anchors_for(tuple(padded)), image_hw)
         res = self.model.losses(out, gt_boxes, gt_classes, eps=eps, normalizer=normalizer)
         self.opt.zero_grad(set_to_none=True)
@@ -254,16 +374,62 @@ class HeadTrainer:
         """From the gradients backward() left (data_parallel: from the averaged ones in the bucket) to the stepped weights and refolded
         filters."""
         if self.fused is not None:
-            self.fused.step(lr)                   # K25: s dW', the step on W and W' = W s in one launch; bumps the written tensors' versions
+            if self.solver.plain_step:
+                self.fused.step(lr)               # K25: s dW', the step on W and W' = W s in one launch; bumps the written tensors' versions
+            else:                                 # K29: the same under the solver's settings; the guard also watches the step's two losses
+                self.fused.step([lr] + self._lrs[1:], iteration=self.iteration, watch=self._watched_losses() if self.solver.computes_norm else ())
             if self.masters is not None:
                 for c in self.masters.convs:
                     c.weight.grad = None          # (as collect_grads leaves them)
             return
         if self.masters is not None:
             self.masters.collect_grads()          # W.grad = s dW': the optimiser steps the unfolded weights
+        self._clip_gradients()                    # (after collect_grads: what is clipped is s dW')
         self.opt.step()                           # bumps the weights' versions: the filters and HIP graphs derived from them are rebuilt
         if self.masters is not None:
             self.masters.refold()                 # conv.weight = W s, in place
+
+    def _watched_losses(self) -> List[torch.Tensor]:
+        """The step's two loss values as fp32 device scalars: the bucket's tail (the rank means) under data parallelism."""
+        if self.bucket is not None:
+            return [self.bucket.tail[0:1], self.bucket.tail[1:2]]
+        if self._losses is None:
+            return []
+        return [self._losses[k].reshape(1).to(torch.float32) for k in ("loss_cls", "loss_box_reg")]
+
+    def _clip_gradients(self) -> None:
+        """Torch's path: detectron2's maybe_add_gradient_clipping -- `value` and `norm` per parameter, `full_model` once over all."""
+        kind, v = self.solver.clip_type, self.solver.clip_value
+        have = [p for p in self.params if p.grad is not None]
+        if kind == "value":
+            for p in have:
+                torch.nn.utils.clip_grad_value_(p, v)
+        elif kind == "norm":
+            for p in have:
+                torch.nn.utils.clip_grad_norm_(p, v)
+        elif kind == "full_model" and have:
+            self._grad_norm = torch.nn.utils.clip_grad_norm_(have, v)
+
+    def check_finite(self) -> Optional[dict]:
+        """What log steps and checkpoints call before they read back or write: under guard_nonfinite the fused step's status is read (the
+        one synchronisation) and FloatingPointError raised if a step was bad -- the weights are then those from before that iteration.
+        Returns the status (None where there is none)."""
+        if self.fused is None or self.solver.plain_step:
+            return None
+        st = self.fused.status()
+        if st is not None and st["poisoned"]:
+            raise FloatingPointError("gradient or loss became infinite or NaN at iteration {}".format(st["first_bad_iteration"]))
+        return st
+
+    def grad_norm(self, status: Optional[dict] = None) -> Optional[float]:
+        """The last step's gradient norm over the full model where one was computed (a read-back: log steps only), else None.  status: what
+        check_finite() returned, if it was just called."""
+        if self.fused is not None:
+            if not self.solver.computes_norm:
+                return None
+            st = status if status is not None else self.fused.status()
+            return None if st is None else st["last_norm"]
+        return None if self._grad_norm is None else float(self._grad_norm)
 
 
 def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, train_fpn: bool = False, train_backbone: bool = False, masters=None,
@@ -394,7 +560,8 @@ def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
     except ValueError as e:
         raise SystemExit("--resume: {}: {}".format(path, e))
     trainer.iteration = int(state["iteration"])
-    trainer._lr = warmup_multistep_lr(trainer.iteration, **trainer.schedule)
+    trainer._lrs = trainer.lrs_at(trainer.iteration)
+    trainer._lr = trainer._lrs[0]
     ls, own = trainer.model.loss_state, state["ranks"][trainer.rank] if trainer.world > 1 else state["loss_state"]
     ls.current_step, ls.draws = int(own["current_step"]), int(own["draws"])
     ls.loss_normalizer = float(own["loss_normalizer"])
@@ -433,6 +600,10 @@ def arg_parser():
                                                                   "(implies --train-fpn; the stem and res2 stay frozen)")
     ap.add_argument("--fused-step", action="store_true", help="the optimiser's step as one launch of the project's own kernel (K25) in place of "
                                                               "torch.optim.SGD and the refold passes around it")
+    ap.add_argument("--guard-nonfinite", action="store_true", help="stop at the first non-finite gradient or loss as detectron2's trainer does, without a "
+                                                                   "synchronisation per step: the fused step (K29) checks on the device and writes nothing "
+                                                                   "from that iteration on; log steps and checkpoints read the status and raise "
+                                                                   "FloatingPointError before anything is written; implies --fused-step")
     ap.add_argument("--random-flip", action="store_true", help="detectron2's RandomFlip: every frame is mirrored with probability 0.5 (drawn in "
                                                                "data order from --random-seed), its boxes with it")
     ap.add_argument("--resume", action="store_true", help="continue the run OUTPUT_DIR/last_checkpoint stopped in: its weights and its trainer state "
@@ -451,6 +622,8 @@ def arg_parser():
 def main(argv=None):
     args = arg_parser().parse_args(argv)
     rank, world, group, own_group = 0, 1, None, False
+    if args.guard_nonfinite:
+        args.fused_step = True
     if args.data_parallel:
         import torch.distributed as dist
         args.fused_step = True
@@ -492,6 +665,7 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     if int(freeze_at) != 2:
         raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: the stem and res2 are frozen and res3 - res5 train (detectron2's "
                          "default, FREEZE_AT = 2), or with neither --train-backbone nor --train-fpn only the head does".format(freeze_at))
+    solver = solver_settings(cfg, guard_nonfinite=args.guard_nonfinite)      # (SystemExit for a key this trainer does not run, before a model is built)
     train_fpn = args.train_fpn or args.train_backbone
     # --resume: the file last_checkpoint names, if there is one (none: the run starts as without the flag, as detectron2's resume_or_load)
     resume_from = checkpoint.resolve_checkpoint(cfg.OUTPUT_DIR, "") if args.resume else ""
@@ -533,11 +707,11 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
                                                   box_reg_weights=tuple(cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS), annealing_step=int(s.STEPS[1]),
                                                   seed=args.random_seed + rank, bbox_cov_loss=cov.NAME, bbox_cov_num_samples=int(cov.NUM_SAMPLES))
     model.head.dropout_seed += rank                        # a rank's loss samples and dropout masks are its own, as detectron2 seeds its ranks
+    max_iter = args.max_iter if args.max_iter >= 0 else int(s.MAX_ITER)
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
                           warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=train_fpn, train_backbone=args.train_backbone,
                           shadow=shadow if args.train_backbone else None, fused_step=args.fused_step,
-                          data_parallel=(rank, world, group) if args.data_parallel else None)
-    max_iter = args.max_iter if args.max_iter >= 0 else int(s.MAX_ITER)
+                          data_parallel=(rank, world, group) if args.data_parallel else None, solver=solver, max_iter=max_iter)
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
     sampler = FrameSampler(batch, random_flip=args.random_flip, seed=args.random_seed)
@@ -572,7 +746,9 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         return images, list(gb), list(gc)
 
     def write(name: str, it: int):
-        """A checkpoint: every rank hands in its loss state (the one collective of a checkpoint), rank 0 writes the file."""
+        """A checkpoint: every rank hands in its loss state (the one collective of a checkpoint), rank 0 writes the file.  Under
+        --guard-nonfinite the status is read first: after a bad step nothing is written (every rank decides alike, before the collective)."""
+        trainer.check_finite()
         ranks = gather_objects(loss_state_of(trainer), world, group) if world > 1 else None
         if rank == 0:
             written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, name, it, ranks=ranks, **saved))
@@ -605,9 +781,12 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
             progressed = True
             it = trainer.iteration
             if args.log_period > 0 and (it % args.log_period == 0 or it == max_iter):
+                norm = trainer.grad_norm(trainer.check_finite())                      # (FloatingPointError after a bad step, under --guard-nonfinite)
                 shown = trainer.mean_losses() if args.data_parallel else res          # (the rank means, from the bucket's tail)
                 last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(shown["loss_cls"]), float(shown["loss_box_reg"]),
                                                                                   trainer.lr)
+                if norm is not None:
+                    last_line += "  grad_norm %.6g" % norm
                 say(last_line, flush=True)
             if period > 0 and it % period == 0 and it < max_iter:
                 write("model_%07d" % (it - 1), it)
