@@ -1008,6 +1008,36 @@ int pod_sgd_step_solver(const PodSgdTensor* tensors, PodSgdTensor* tensors_dev, 
                         const uint8_t* group, const uint8_t* group_dev, const PodSgdSolver* solver, void* workspace, pod_stream_t stream);
 int pod_sgd_solver_reset(void* workspace, pod_stream_t stream);
 
+/* ---- K30  backward of the ResNet stem and its max-pool (csrc/k30_stem_backward.hip) ---------------------------------------------
+ * Serves: the backward pass of detectron2's BasicStem (conv1 7x7 / stride 2 / pad 3 + FrozenBN + ReLU + max_pool2d(3, 2, 1)) in train
+ * mode behind `self.backbone(images.tensor)` (probabilistic_retinanet.py:96-100) under train_net.py's loop at MODEL.BACKBONE.FREEZE_AT
+ * 0; the reference gets it from autograd.  res2 (FREEZE_AT 1) runs on K13 / K22 / K24 at 64 channels.  Three new symbols under
+ * POD_ABI_VERSION 18, as for K20 - K29: no entry or structure that existed changed, so the number stands.
+ *
+ * pod_stem7x7_wgrad: x dev (images, 3, H_img, W_img) contiguous, uint8 (x_is_u8) or fp32: the frames as pod_stem7x7_split takes them,
+ *   normalised on load as there, (v - mean[c]) / stddev[c] in fp32 (mean, stddev dev, 3 floats each, both NULL: already normalised), zero
+ *   outside H_img x W_img -- the convolution's padding and the frame's padding up to (H, W).  dS dev (images * Ho * Wo, 64) channels-last
+ *   fp32, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  dW dev fp32 (64, 3, 7, 7):
+ *   dW[k][c][dy][dx] = sum over (b, oy, ox) of dS[(b, oy, ox)][k] xn[b][c][2 oy - 3 + dy][2 ox - 3 + dx].  No bias gradient: the bias is
+ *   FrozenBN's shift.  K22's arithmetic: both operands split at run time into two f16 terms of their power-of-two-scaled values (x_amax: the
+ *   record that bounds the NORMALISED input, pod_stem7x7_split's in_amax; ds_amax: dS's), three partial products on
+ *   v_mfma_f32_32x32x16_f16, fp32 accumulation inside a slice -- a run of 8 x 8 output tiles whose length depends on the tile count alone --
+ *   and the slices' partial sums (`partials`: pod_stem7x7_wgrad_partials(...) floats, 16-byte aligned, 64 * 192 per slice; 0 = invalid
+ *   geometry) added in slice order in fp64 by a second launch.  No atomics: the same bits on every run.  Every extent pod_stem7x7_split
+ *   accepts (1 <= H_img <= H <= 16384, the same for W) with images >= 1 and images * Ho * Wo < 2^30; POD_E_INVALID before any launch for
+ *   anything else, a NULL pointer (mean and stddev only together), dS or partials off 16 bytes, a record, dW, mean, stddev or an fp32 x off
+ *   4, or two of x, dS, dW and partials at one address.
+ * pod_maxpool3x3s2_backward_cl: the backward of pod_maxpool3x3s2_cl and of the stem's ReLU for one image.  s dev (H * W, C): the stem's
+ *   stored output; dP dev (Hq * Wq, C), Hq = (H - 1) / 2 + 1, Wq = (W - 1) / 2 + 1; dS dev (H * W, C):
+ *   dS[(y, x)][c] = s[(y, x)][c] > 0 ? the sum of dP[(oy, ox)][c] over the at most four windows (oy, ox) that hold (y, x) and whose arg-max
+ *   is (y, x) : 0, added in window order (oy ascending, then ox).  The arg-max is torch's: the window's pixels inside the map scanned
+ *   row-major, a new maximum only on strict >, so the first maximum wins.  C % 4 == 0, 1 <= H, W <= 16384; dS may be neither s nor dP.
+ *   ds_amax: NULL or the zeroed record that receives max |dS|. */
+int64_t pod_stem7x7_wgrad_partials(int32_t images, int32_t H_img, int32_t W_img, int32_t H, int32_t W);
+int pod_stem7x7_wgrad(const void* x, int32_t x_is_u8, int32_t images, int32_t H_img, int32_t W_img, const float* mean, const float* stddev, const float* dS,
+                      int32_t H, int32_t W, const float* x_amax, const float* ds_amax, float* dW, float* partials, pod_stream_t stream);
+int pod_maxpool3x3s2_backward_cl(const float* s, const float* dP, float* dS, int32_t H, int32_t W, int32_t C, float* ds_amax, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws, of the generator itself and of the f16 split -- is declared in
  * include/pod_mi355x_test.h: the library exports those entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

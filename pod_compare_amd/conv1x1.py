@@ -120,20 +120,25 @@ class Stem7x7:
         return y, ho, wo
 
     def _input_bound(self, x: torch.Tensor, mean: Optional[torch.Tensor], std: Optional[torch.Tensor]) -> torch.Tensor:
-        """A device record bounding max |normalised input| (the kernel's `in_amax`): |(x - mean) / std| <= (max |x| + max |mean|) / min |std|, with
-        max |x| = 255 for a uint8 frame (a constant word per (mean, std)) and the frame's own abs-max word otherwise."""
-        if mean is None:
-            return amax.of(x)
-        key = (mean.data_ptr(), mean._version, std.data_ptr(), std._version)
-        c = self._bounds.get(key)
-        if c is None:
-            inv = 1.0 / float(std.abs().min())
-            c = self._bounds[key] = (inv, torch.full((1,), float(mean.abs().max()) * inv, dtype=torch.float32, device=x.device),
-                                     torch.full((amax.RECORD,), (255.0 + float(mean.abs().max())) * inv, dtype=torch.float32, device=x.device))
-            torch.cuda.current_stream(x.device).synchronize()              # made once, then read from any stream
-        if x.dtype == torch.uint8:
-            return c[2]
-        return torch.add(c[1], amax.of(x), alpha=c[0])
+        return normalised_input_bound(x, mean, std, self._bounds)
+
+
+def normalised_input_bound(x: torch.Tensor, mean: Optional[torch.Tensor], std: Optional[torch.Tensor], cache: dict) -> torch.Tensor:
+    """A device record bounding max |normalised input| (pod_stem7x7_split's `in_amax`, pod_stem7x7_wgrad's `x_amax`): |(x - mean) / std| <=
+    (max |x| + max |mean|) / min |std|, with max |x| = 255 for a uint8 frame (a constant word per (mean, std), kept in `cache`) and the
+    frame's own abs-max word otherwise."""
+    if mean is None:
+        return amax.of(x)
+    key = (mean.data_ptr(), mean._version, std.data_ptr(), std._version)
+    c = cache.get(key)
+    if c is None:
+        inv = 1.0 / float(std.abs().min())
+        c = cache[key] = (inv, torch.full((1,), float(mean.abs().max()) * inv, dtype=torch.float32, device=x.device),
+                          torch.full((amax.RECORD,), (255.0 + float(mean.abs().max())) * inv, dtype=torch.float32, device=x.device))
+        torch.cuda.current_stream(x.device).synchronize()              # made once, then read from any stream
+    if x.dtype == torch.uint8:
+        return c[2]
+    return torch.add(c[1], amax.of(x), alpha=c[0])
 
 
 class Conv3x3S2:

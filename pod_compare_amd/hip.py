@@ -51,12 +51,14 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_conv1x1_wgrad_strided_partials", "pod_conv1x1_wgrad_strided", "pod_subsample2_scatter_cl",
            "pod_sgd_chunk_map", "pod_sgd_step", "pod_grad_bucket_layout", "pod_grad_pack",
            "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss",
-           "pod_sgd_solver_workspace_bytes", "pod_sgd_step_solver", "pod_sgd_solver_reset")
+           "pod_sgd_solver_workspace_bytes", "pod_sgd_step_solver", "pod_sgd_solver_reset",
+           "pod_stem7x7_wgrad_partials", "pod_stem7x7_wgrad", "pod_maxpool3x3s2_backward_cl")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
-                 "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes")
+                 "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes",
+                 "pod_stem7x7_wgrad_partials")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -284,6 +286,10 @@ def load() -> ctypes.CDLL:
     lib.pod_sgd_solver_workspace_bytes.restype = c_size_t
     lib.pod_sgd_step_solver.argtypes = [POINTER(PodSgdTensor), P, c_int32, P, c_int64, P, P, POINTER(PodSgdSolver), P, P]
     lib.pod_sgd_solver_reset.argtypes = [P, P]
+    lib.pod_stem7x7_wgrad_partials.argtypes = [c_int32] * 5
+    lib.pod_stem7x7_wgrad_partials.restype = c_int64
+    lib.pod_stem7x7_wgrad.argtypes = [P, c_int32, c_int32, c_int32, c_int32, P, P, P, c_int32, c_int32, P, P, P, P, P]
+    lib.pod_maxpool3x3s2_backward_cl.argtypes = [P, P, P, c_int32, c_int32, c_int32, P, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

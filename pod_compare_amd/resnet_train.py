@@ -1,6 +1,9 @@
 """res3 - res5 of the ResNet with a backward pass: detectron2's BottleneckBlocks above MODEL.BACKBONE.FREEZE_AT = 2 in training mode
 (probabilistic_retinanet.py:96-100, `self.backbone(images.tensor)`, under train_net.py's loop) as ONE torch.autograd.Function over the
-three stages (`_BlocksTrain`, over any chain of bottlenecks).  The stem and res2 stay frozen, as the reference's do (`res2_maps`, under no_grad).
+three stages (`_BlocksTrain`, over any chain of bottlenecks).  The stem and res2 stay frozen, as the reference's do (`res2_maps`, under no_grad),
+unless FREEZE_AT says otherwise: at 1 res2's three blocks lead the chain and only the stem and its max-pool run under no_grad (`pool_maps`);
+at 0 those two get a backward pass as well (`_StemTrain`, `stem_forward_train`: K30's pool backward with the stem's ReLU gate per image,
+then one 7x7 weight gradient over the batch's stacked frames; the stem computes no input gradient).
 
 Forward: Bottleneck.forward_cl's own launches, per image, unchanged; the input x, conv1's and conv2's outputs a and b and the output y of
 every block are kept.  Backward, on the B images at once, from the last block of res5 down to the first block of res3:
@@ -12,9 +15,10 @@ every block are kept.  Backward, on the B images at once, from the last block of
     conv shortcut    dWs = pod_conv1x1_wgrad_strided(x, dZ, 2); the half-resolution dA W1 + dZ Ws is one GEMM with the other's result as
                      residual, and pod_subsample2_scatter_cl (K24) expands it to the full map per image: its gate is the block below's
                      stored output, its `add` the FPN's gradient at that map -- the result is the block below's dZ
+                     (res2's first block has its conv shortcut at stride 1: the same GEMM pair at full resolution and no scatter)
 Every input-gradient GEMM above runs twice, on W and on -W, and half the difference is kept (`centred`): the two results share the mean of
 the matrix cores' accumulation error, which 39 chained GEMMs would otherwise add up and the weight gradients sum over every pixel.
-The first block of res3 computes no dX: nothing trains below it (a chain whose input requires grad gets it: tests).  The convs carry FrozenBN, folded: the gradients are those of the FOLDED
+The first block of the chain computes no dX where nothing trains below it (a chain whose input requires grad gets it: tests).  The convs carry FrozenBN, folded: the gradients are those of the FOLDED
 filters W' = W s, and no bias gradient exists (`FoldedMasters` hands the optimiser W with W.grad = s dW' and refolds after its step).
 GPU only -- anything this path cannot take raises (hip.PodError): there is no fallback."""
 from typing import List, Sequence, Tuple
@@ -22,11 +26,13 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import nn
 
-from . import hip, modeling, wgrad, wino
+from . import conv1x1, hip, modeling, wgrad, wino
+from .conv_forms import stem_of
 from .fpn_train import _stacked
 from .head_train import backward_gemm, conv_params, flat_grads, flipped3x3, patch_matrix, transposed1x1
 
 STAGES = ("res3", "res4", "res5")
+FREEZE_POINTS = (0, 1, 2)         # MODEL.BACKBONE.FREEZE_AT: what stays frozen is the first `freeze_at` of (stem, res2)
 
 
 def _conv_of(m) -> nn.Conv2d:
@@ -34,9 +40,17 @@ def _conv_of(m) -> nn.Conv2d:
     return m[0] if isinstance(m, nn.Sequential) else m
 
 
-def trainable_blocks(bottom_up) -> list:
-    """The bottlenecks of res3, res4 and res5, bottom to top."""
-    return [block for name in STAGES for block in getattr(bottom_up, name)]
+def _check_freeze_at(freeze_at) -> int:
+    if int(freeze_at) not in FREEZE_POINTS:
+        raise hip.PodError("MODEL.BACKBONE.FREEZE_AT = {} has no training path: 0 (everything trains), 1 (the stem is frozen) or 2 (the stem and "
+                           "res2 are)".format(freeze_at))
+    return int(freeze_at)
+
+
+def trainable_blocks(bottom_up, freeze_at: int = 2) -> list:
+    """The bottlenecks detectron2 trains at MODEL.BACKBONE.FREEZE_AT = freeze_at, bottom to top: res3, res4 and res5, below 2 res2 in front."""
+    stages = (("res2",) if _check_freeze_at(freeze_at) < 2 else ()) + STAGES
+    return [block for name in stages for block in getattr(bottom_up, name)]
 
 
 def block_convs(block) -> list:
@@ -44,19 +58,23 @@ def block_convs(block) -> list:
     return [_conv_of(m) for m in ((block.shortcut,) if block.shortcut is not None else ()) + (block.conv1, block.conv2, block.conv3)]
 
 
-def trainable_convs(bottom_up) -> list:
-    """The convs detectron2 trains at FREEZE_AT = 2 -- those of res3, res4 and res5 -- in a fixed order."""
-    return [c for block in trainable_blocks(bottom_up) for c in block_convs(block)]
+def trainable_convs(bottom_up, freeze_at: int = 2) -> list:
+    """The convs detectron2 trains at FREEZE_AT = freeze_at in a fixed order: the stem's (at 0), res2's (at 0 and 1), then those of res3,
+    res4 and res5."""
+    stem = [_conv_of(bottom_up.stem)] if _check_freeze_at(freeze_at) == 0 else []
+    return stem + [c for block in trainable_blocks(bottom_up, freeze_at) for c in block_convs(block)]
 
 
-def unfolded_pairs(bottom_up) -> list:
-    """The (conv, FrozenBatchNorm2d) pairs of an UNFOLDED res3 - res5, in trainable_convs' order."""
+def unfolded_pairs(bottom_up, freeze_at: int = 2) -> list:
+    """The (conv, FrozenBatchNorm2d) pairs of an UNFOLDED backbone, in trainable_convs' order."""
     pairs = []
-    for block in trainable_blocks(bottom_up):
-        for m in ((block.shortcut,) if block.shortcut is not None else ()) + (block.conv1, block.conv2, block.conv3):
-            if not (isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[1], modeling.FrozenBatchNorm2d) and m[0].bias is None):
-                raise hip.PodError("training the backbone needs the unfolded (conv, FrozenBN) pairs of res3 - res5 beside the folded model")
-            pairs.append((m[0], m[1]))
+    modules = [bottom_up.stem] if _check_freeze_at(freeze_at) == 0 else []
+    for block in trainable_blocks(bottom_up, freeze_at):
+        modules += ((block.shortcut,) if block.shortcut is not None else ()) + (block.conv1, block.conv2, block.conv3)
+    for m in modules:
+        if not (isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[1], modeling.FrozenBatchNorm2d) and m[0].bias is None):
+            raise hip.PodError("training the backbone needs the unfolded (conv, FrozenBN) pairs of res3 - res5 beside the folded model")
+        pairs.append((m[0], m[1]))
     return pairs
 
 
@@ -74,24 +92,92 @@ def _require(blocks) -> None:
             ok = ok and s == 1 and c1.in_channels == c3.out_channels
         else:
             sc = _conv_of(block.shortcut)
-            ok = ok and s == 2 and sc.stride[0] == 2 and sc.in_channels == c1.in_channels and sc.out_channels == c3.out_channels
+            ok = ok and s in (1, 2) and sc.stride[0] == s and sc.in_channels == c1.in_channels and sc.out_channels == c3.out_channels
     if not ok:
         raise hip.PodError("blocks_forward_train: these bottlenecks have no HIP training path (folded FrozenBN, the split kernels selected, bottlenecks of "
-                           "1x1 / 3x3 / 1x1 with widths in multiples of 64, 3x3 width <= 512, output width <= 2048, and a stride-2 1x1 shortcut "
-                           "exactly where conv1 has stride 2)")
+                           "1x1 / 3x3 / 1x1 with widths in multiples of 64, 3x3 width <= 512, output width <= 2048, and a 1x1 shortcut "
+                           "of conv1's stride, 1 or 2)")
 
 
-def res2_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
-    """The frozen stem, max-pool and res2 of one frame under no_grad, channels-last: (t (h * w, 256), h, w) -- what detectron2's FREEZE_AT = 2
-    leaves untrained.  The frame is padded as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size)."""
+def _require_frame(model, image) -> Tuple[int, int]:
+    """The padded (h, w) of a frame the channels-last HIP backbone takes, as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size)."""
     ok = (torch.is_tensor(image) and image.is_cuda and image.device == model.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
           and image.dtype in (torch.uint8, torch.float32) and model._cl_backbone(model.pixel_mean) and model.bottom_up.hip_stem_ok())
     if not ok:
         raise hip.PodError("training the backbone needs the channels-last HIP backbone (a (3, h, w) uint8 / fp32 frame on the model's GPU, FrozenBN "
                            "folded, the split kernels and the HIP stem selected)")
-    padded = modeling._anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
+    return modeling._anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
+
+
+def res2_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """The frozen stem, max-pool and res2 of one frame under no_grad, channels-last: (t (h * w, 256), h, w) -- what detectron2's FREEZE_AT = 2
+    leaves untrained.  The frame is padded as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size)."""
+    padded = _require_frame(model, image)
     with torch.no_grad():
         return model.bottom_up.forward_cl(None, frame=(image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded), stop_after_res2=True)
+
+
+def _stem_pool(stem: nn.Conv2d, image: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, padded):
+    """ResNet50.forward_cl's first two launches on one frame: (s, h, w), the stem's post-ReLU output, and (p, hq, wq), its max-pool."""
+    s, h, w = stem_of(stem)(image, relu=True, mean=mean, std=std, padded_hw=padded)
+    return (s, h, w), conv1x1.maxpool3x3s2_cl(s, h, w)
+
+
+def pool_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """The frozen stem and max-pool of one frame under no_grad, channels-last: (t (h * w, 64), h, w) -- what detectron2's FREEZE_AT = 1 leaves
+    untrained, res2's input."""
+    padded = _require_frame(model, image)
+    with torch.no_grad():
+        return _stem_pool(_conv_of(model.bottom_up.stem), image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded)[1]
+
+
+class _StemTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stem, frames, mean, std, padded, tap, weight):
+        # weight: the stem's folded filter (so that autograd asks for its gradient); the frames get none
+        kept, outs = [], []
+        for im in frames:
+            (s, h, w), (p, _, _) = _stem_pool(stem, im, mean, std, padded)
+            kept.append(s)
+            outs.append(p)
+        if tap is not None:                                 # tests: the stem's stored outputs, whose gates and arg-max routing the backward uses
+            tap["stem"] = (kept, (h, w))
+        ctx.state = (stem, frames, mean, std, padded, kept, (h, w))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_maps):
+        stem, frames, mean, std, padded, kept, (h, w) = ctx.state
+        B = len(frames)
+        dp = [torch.zeros(((h - 1) // 2 + 1) * ((w - 1) // 2 + 1), 64, dtype=torch.float32, device=kept[0].device) if g is None else g.contiguous() for g in g_maps]
+        ds = torch.empty((B * h * w, 64), dtype=torch.float32, device=kept[0].device)
+        wgrad.over_images(B, ds, lambda b, rows, rec: wgrad.maxpool3x3s2_backward_cl(kept[b], dp[b], h, w, out=rows(ds), record=rec))
+        x = frames[0].unsqueeze(0) if B == 1 else torch.stack(list(frames))      # (the sampler gives a batch one shape)
+        dW = wgrad.stem7x7_wgrad(x, ds, padded, mean, std, bound=stem_of(stem)._input_bound(x, mean, std))
+        ctx.state = None
+        return (None,) * 6 + (dW,)
+
+
+def stem_forward_train(model, images: Sequence[torch.Tensor], tap=None) -> list:
+    """The stem and its max-pool with a backward pass (FREEZE_AT = 0): per image the (t (h * w, 64), h, w) res2 starts from, B frames of one
+    shape.  The maps carry a grad_fn that reaches the stem's (folded) filter: K30's pool backward per image into one stacked dS, then one
+    weight gradient over the batch's stacked frames.  The stem computes no input gradient."""
+    images = list(images)
+    if not images:
+        raise hip.PodError("stem_forward_train: at least one frame")
+    padded = _require_frame(model, images[0])
+    for im in images[1:]:
+        if _require_frame(model, im) != padded or tuple(im.shape) != tuple(images[0].shape) or im.dtype != images[0].dtype:
+            raise hip.PodError("stem_forward_train: a batch holds frames of one shape and type, got {} {} and {} {}".format(
+                tuple(images[0].shape), images[0].dtype, tuple(im.shape), im.dtype))
+    stem = _conv_of(model.bottom_up.stem)
+    if not stem.weight.requires_grad:
+        raise hip.PodError("stem_forward_train: the stem's filter does not require a gradient (FoldedMasters sets it)")
+    with torch.cuda.device(images[0].device):
+        outs = _StemTrain.apply(stem, images, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), tuple(padded),
+                                tap if tap is not None else getattr(model.bottom_up, "train_tap", None), stem.weight)
+    h, w = (int(padded[0]) - 1) // 2 + 1, (int(padded[1]) - 1) // 2 + 1
+    return [(t, (h - 1) // 2 + 1, (w - 1) // 2 + 1) for t in outs]
 
 
 def centred(layout, conv, d: torch.Tensor, n: int, residual=None) -> torch.Tensor:
@@ -189,9 +275,15 @@ class _BlocksTrain(torch.autograd.Function):
             if block.shortcut is None:
                 d, gated = centred(transposed1x1, c1, da, n1, residual=dz), False
                 continue
-            # the half-resolution dA W1 + dZ Ws, expanded per image behind the gate of the block below, with what its output already carries
+            # dA W1 + dZ Ws: one GEMM with the other's result as residual
             half = centred(transposed1x1, c1, da, n1, residual=centred(transposed1x1, sc, dz, n1))
             below = from_above(i - 1) if i else None
+            if stride == 1:                                 # (res2's first block) nothing to expand: the gate of the block below, if there is one
+                if below is not None:
+                    half.add_(torch.cat(below))
+                d, gated = half, False
+                continue
+            # at half resolution: expanded per image behind the gate of the block below, with what its output already carries
             d, gated = torch.empty((B * h * w, c1.in_channels), dtype=torch.float32, device=dev), True
             wgrad.over_images(B, d, lambda b, rows, rec: wgrad.subsample2_scatter_cl(
                 rows(half), h, w, gate=saved[b][i]["x"] if i else None, add=None if below is None else below[b], out=rows(d), record=rec))
@@ -230,14 +322,18 @@ def blocks_forward_train(blocks: Sequence, maps: Sequence[Tuple[torch.Tensor, in
     return [[(flat[len(taps) * b + k], hw[i][0], hw[i][1]) for k, i in enumerate(taps)] for b in range(len(maps))]
 
 
-def resnet_forward_train(bottom_up, maps: Sequence[Tuple[torch.Tensor, int, int]]) -> List[list]:
-    """maps: per image the (t, h, w) of res2_maps, B images of one padded size.  Returns per image [(c3, h, w), (c4, h, w), (c5, h, w)], what
-    ResNet50.forward_cl returns; the maps carry a grad_fn that reaches the (folded) filter of every conv of res3 - res5.  A dict
+def resnet_forward_train(bottom_up, maps: Sequence[Tuple[torch.Tensor, int, int]], freeze_at: int = 2) -> List[list]:
+    """maps: per image the (t, h, w) of res2_maps -- below freeze_at = 2 of pool_maps (1) or stem_forward_train (0): res2 then runs in the
+    chain --, B images of one padded size.  Returns per image [(c3, h, w), (c4, h, w), (c5, h, w)], what ResNet50.forward_cl returns; the
+    maps carry a grad_fn that reaches the (folded) filter of every conv of the chain and, where they require it, the maps.  A dict
     `bottom_up.train_tap`, if there is one, receives the saved activations and every gate's output (tests)."""
-    blocks = trainable_blocks(bottom_up)
-    if [len(getattr(bottom_up, name)) > 0 and getattr(bottom_up, name)[0].shortcut is not None for name in STAGES] != [True] * 3 or len(_taps(blocks)) != 3:
-        raise hip.PodError("resnet_forward_train: res3, res4 and res5 each open with a conv-shortcut block and continue with identity blocks")
-    return blocks_forward_train(blocks, maps, tap=getattr(bottom_up, "train_tap", None))
+    blocks = trainable_blocks(bottom_up, freeze_at)
+    stages = (("res2",) if int(freeze_at) < 2 else ()) + STAGES
+    if [len(getattr(bottom_up, name)) > 0 and getattr(bottom_up, name)[0].shortcut is not None for name in stages] != [True] * len(stages) \
+            or len(_taps(blocks)) != len(stages):
+        raise hip.PodError("resnet_forward_train: every trained stage opens with a conv-shortcut block and continues with identity blocks")
+    outs = blocks_forward_train(blocks, maps, tap=getattr(bottom_up, "train_tap", None))
+    return [per_image[-3:] for per_image in outs]
 
 
 class FoldedMasters:
@@ -247,7 +343,8 @@ class FoldedMasters:
     W.grad = s dW', `refold` rewrites conv.weight = W s in place after the optimiser's step (the version bump rebuilds the derived filters),
     bit-equal to what fold_frozen_bn makes of a checkpoint that holds W.  The folded bias never changes."""
 
-    def __init__(self, folded_convs: Sequence[nn.Conv2d], pairs: Sequence[Tuple[nn.Conv2d, nn.Module]]):
+    def __init__(self, folded_convs: Sequence[nn.Conv2d], pairs: Sequence[Tuple[nn.Conv2d, nn.Module]], freeze_at: int = 2):
+        self.freeze_at = int(freeze_at)          # which convs these are: trainable_convs(., freeze_at) / unfolded_pairs(., freeze_at)
         if len(folded_convs) != len(pairs):
             raise hip.PodError("FoldedMasters: {} folded convs against {} (conv, FrozenBN) pairs".format(len(folded_convs), len(pairs)))
         self.convs, self.params, self.scales = list(folded_convs), [], []

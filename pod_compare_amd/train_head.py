@@ -22,7 +22,11 @@ per image under no_grad (resnet_train.res2_maps); res3 - res5 run with a backwar
 for the 1x1 weight gradients and the stride-2 scatter, K22 for the 3x3 ones), fed by the gradient the FPN's backward hands below its
 laterals and p6.  The device model computes with FrozenBN folded, W' = W s; the optimiser holds the unfolded W (W.grad = s dW'), so
 momentum and weight decay act on what the reference's act on, and conv.weight is refolded from W after every step.  A checkpoint carries
-W.  Only FREEZE_AT = 2 is supported.
+W.  MODEL.BACKBONE.FREEZE_AT is honoured as detectron2 honours it: 2 (the default) is the above; 1 trains res2 too -- the stem and its
+max-pool run under no_grad (resnet_train.pool_maps) and res2's three blocks join the chain --; 0 trains the stem as well, nothing runs
+under no_grad: the stem and the pool get a backward pass (resnet_train.stem_forward_train, K30: the pool's backward with the stem's ReLU
+gate per image, one 7x7 weight gradient over the batch's stacked frames).  3, 4 and 5 are refused, and so is a value other than 2
+without --train-backbone.  A checkpoint's `trained` list names res2 and the stem when they moved, so --resume across freeze points is refused.
 
 --fused-step: the optimiser's step is ONE launch of this project's own (K25, pod_compare_amd/sgd_step.py) in place of collect_grads + torch's
 SGD + refold: the trainer owns the momentum buffers, the kernel scales a folded filter's gradient by s, steps the master and rewrites the
@@ -81,7 +85,7 @@ from .config import setup_config
 from .data_parallel import GradBucket, broadcast_tensors, gather_objects, rank_slice
 from .fpn_train import backbone_maps, fpn_convs, fpn_forward_train
 from .head_train import conv_params, head_convs
-from .resnet_train import FoldedMasters, res2_maps, resnet_forward_train, trainable_convs, unfolded_pairs
+from .resnet_train import FREEZE_POINTS, FoldedMasters, pool_maps, res2_maps, resnet_forward_train, stem_forward_train, trainable_convs, unfolded_pairs
 from .probabilistic_inference import build_model
 from .sgd_step import LR_SCHEDULERS, WARMUP_METHODS, FusedSGD, SgdEntry, SolverSettings
 
@@ -179,15 +183,25 @@ def hflip_boxes(boxes: torch.Tensor, width) -> torch.Tensor:
     return out
 
 
+def trained_parts(train_fpn: bool, train_backbone: bool, freeze_at: int = 2) -> List[str]:
+    """What a run trains, as a checkpoint's `pod_trainer` names it (--resume compares the lists): at the default freeze point what it
+    always was; "res2" and "stem" follow where MODEL.BACKBONE.FREEZE_AT lets them move."""
+    parts = ["head"] + (["fpn"] if train_fpn or train_backbone else []) + (["backbone"] if train_backbone else [])
+    if train_backbone:
+        parts += (["res2"] if freeze_at < 2 else []) + (["stem"] if freeze_at < 1 else [])
+    return parts
+
+
 class HeadTrainer:
     """The step function of train_head: optimiser, schedule and the iteration count around model.head.forward_train + model.losses."""
 
     def __init__(self, model, base_lr: float = 0.001, momentum: float = 0.9, weight_decay: float = 1e-4, steps: Sequence[int] = (60000, 80000),
                  gamma: float = 0.1, warmup_iters: int = 1000, warmup_factor: float = 1e-3, iteration: int = 0, train_fpn: bool = False,
                  train_backbone: bool = False, shadow=None, fused_step: bool = False, data_parallel=None, solver: Optional[SolverSettings] = None,
-                 guard_nonfinite: bool = False, max_iter: int = 0):
+                 guard_nonfinite: bool = False, max_iter: int = 0, freeze_at: int = 2):
         """train_backbone: res3 - res5 train too (and the FPN: it lies between them and the head); `shadow`, the same model unfolded, gives
-        the master weights and FrozenBN scales (resnet_train.FoldedMasters).  fused_step: the optimiser's step is pod_sgd_step (K25) on
+        the master weights and FrozenBN scales (resnet_train.FoldedMasters).  freeze_at (with train_backbone): MODEL.BACKBONE.FREEZE_AT --
+        2: the stem and res2 stay frozen; 1: res2 trains too; 0: and the stem.  fused_step: the optimiser's step is pod_sgd_step (K25) on
         momentum buffers the trainer owns (`self.fused`), not torch's SGD; `self.opt` is the torch.optim.SGD either way (unused when fused).
         data_parallel: (rank, world, process group or None = the default one) -- this trainer is one rank of `world`: its gradients go
         through a bucket (`self.bucket`, data_parallel.GradBucket: K26, one all-reduce) and the fused step reads the rank mean from it.
@@ -204,6 +218,9 @@ class HeadTrainer:
         if data_parallel is not None and not fused_step:
             raise ValueError("data_parallel needs fused_step: the averaged gradients are stepped from the bucket by pod_sgd_step")
         self.model, self.train_backbone = model, bool(train_backbone)
+        self.freeze_at = int(freeze_at)
+        if self.freeze_at not in FREEZE_POINTS or (self.freeze_at != 2 and not self.train_backbone):
+            raise ValueError("freeze_at = {}: 0, 1 or 2, and other than 2 only with train_backbone".format(freeze_at))
         self.train_fpn = bool(train_fpn) or self.train_backbone
         self.params = conv_params(head_convs(model.head))
         if self.train_fpn:
@@ -216,7 +233,7 @@ class HeadTrainer:
         if self.train_backbone:
             if shadow is None:
                 raise ValueError("train_backbone needs `shadow`, the unfolded model: the optimiser holds its conv weights, not the folded ones")
-            self.masters = FoldedMasters(trainable_convs(model.bottom_up), unfolded_pairs(shadow.bottom_up))
+            self.masters = FoldedMasters(trainable_convs(model.bottom_up, self.freeze_at), unfolded_pairs(shadow.bottom_up, self.freeze_at), self.freeze_at)
             self.params += self.masters.params
         self.schedule = dict(base_lr=float(base_lr), steps=tuple(int(s) for s in steps), gamma=float(gamma), warmup_iters=int(warmup_iters),
                              warmup_factor=float(warmup_factor))
@@ -264,7 +281,7 @@ class HeadTrainer:
         return self._lr
 
     def trained(self) -> List[str]:
-        return ["head"] + (["fpn"] if self.train_fpn else []) + (["backbone"] if self.train_backbone else [])
+        return trained_parts(self.train_fpn, self.train_backbone, self.freeze_at)
 
     def param_names(self) -> List[str]:
         """detectron2's name of the weight each of self.params is (a master weight: of the conv it is the unfolded filter of)."""
@@ -304,11 +321,16 @@ class HeadTrainer:
         """The frozen backbone + FPN per image -> (per-level (B, 256, H, W) features, padded (h, w)).  train_fpn: only the backbone is
         frozen; the FPN runs on the batch's c3 - c5 with grad (fpn_train.fpn_forward_train)."""
         per_image, padded = [], None
-        if self.train_backbone:
+        if self.train_backbone and self.freeze_at == 2:
             # the stem and res2 frozen, per image; res3 - res5 and the FPN on the batch with grad
             res2 = [res2_maps(self.model, im) for im in images]
             padded = _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
             return fpn_forward_train(self.model.fpn, resnet_forward_train(self.model.bottom_up, res2)), padded
+        if self.train_backbone:
+            # FREEZE_AT 1: the stem and its pool frozen, per image; 0: they run with grad on the batch.  res2 - res5 and the FPN on the batch with grad
+            maps = [pool_maps(self.model, im) for im in images] if self.freeze_at == 1 else stem_forward_train(self.model, images)
+            padded = _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
+            return fpn_forward_train(self.model.fpn, resnet_forward_train(self.model.bottom_up, maps, self.freeze_at)), padded
         if self.train_fpn:
             for im in images:
                 maps, pad = backbone_maps(self.model, im)
@@ -446,7 +468,7 @@ def save_checkpoint(model, shadow, out_dir: str, name: str, iteration: int, trai
     if train_backbone:
         if masters is None:
             raise ValueError("save_checkpoint(train_backbone=True) needs the trainer's master weights (HeadTrainer.masters)")
-        masters.copy_to(unfolded_pairs(shadow.bottom_up))
+        masters.copy_to(unfolded_pairs(shadow.bottom_up, masters.freeze_at))
     with torch.no_grad():
         for dst, src in pairs:
             dst.weight.copy_(src.weight.detach().cpu())
@@ -597,7 +619,8 @@ def arg_parser():
     ap.add_argument("--loader-workers", type=int, default=-1, help="host threads of the loader; -1 = the config's value")
     ap.add_argument("--train-fpn", action="store_true", help="train the FPN's eight convolutions together with the head (the ResNet stays frozen)")
     ap.add_argument("--train-backbone", action="store_true", help="train res3 - res5 of the ResNet too, as detectron2 does at MODEL.BACKBONE.FREEZE_AT = 2 "
-                                                                  "(implies --train-fpn; the stem and res2 stay frozen)")
+                                                                  "(implies --train-fpn; the stem and res2 stay frozen unless the config's "
+                                                                  "MODEL.BACKBONE.FREEZE_AT says 1: res2 trains too, or 0: and the stem)")
     ap.add_argument("--fused-step", action="store_true", help="the optimiser's step as one launch of the project's own kernel (K25) in place of "
                                                               "torch.optim.SGD and the refold passes around it")
     ap.add_argument("--guard-nonfinite", action="store_true", help="stop at the first non-finite gradient or loss as detectron2's trainer does, without a "
@@ -662,15 +685,19 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     cfg.MODEL.DEVICE = args.device
     cov = covariance_overrides(cfg, args)
     freeze_at = cfg.MODEL.BACKBONE.get("FREEZE_AT", 2)
-    if int(freeze_at) != 2:
-        raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: the stem and res2 are frozen and res3 - res5 train (detectron2's "
-                         "default, FREEZE_AT = 2), or with neither --train-backbone nor --train-fpn only the head does".format(freeze_at))
+    if int(freeze_at) not in FREEZE_POINTS:
+        raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} is not supported: with --train-backbone 2 (detectron2's default: the stem and res2 are "
+                         "frozen and res3 - res5 train), 1 (res2 trains too) or 0 (and the stem); without it only 2".format(freeze_at))
+    freeze_at = int(freeze_at)
+    if freeze_at != 2 and not args.train_backbone:
+        raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} needs --train-backbone: without it the ResNet stays frozen, which is what FREEZE_AT = 2 "
+                         "(or no key) says".format(freeze_at))
     solver = solver_settings(cfg, guard_nonfinite=args.guard_nonfinite)      # (SystemExit for a key this trainer does not run, before a model is built)
     train_fpn = args.train_fpn or args.train_backbone
     # --resume: the file last_checkpoint names, if there is one (none: the run starts as without the flag, as detectron2's resume_or_load)
     resume_from = checkpoint.resolve_checkpoint(cfg.OUTPUT_DIR, "") if args.resume else ""
     resume_state = read_trainer_state(resume_from) if resume_from else None
-    trains = ["head"] + (["fpn"] if train_fpn else []) + (["backbone"] if args.train_backbone else [])
+    trains = trained_parts(train_fpn, args.train_backbone, freeze_at)
     if resume_state is not None and list(resume_state.get("trained", [])) != trains:          # (before a model is built; restore_trainer checks the rest)
         raise SystemExit("--resume: {} comes from a run that trained {}, this one trains {}: give the same --train-fpn / --train-backbone".format(
             resume_from, " + ".join(resume_state.get("trained", [])) or "nothing", " + ".join(trains)))
@@ -711,7 +738,7 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     trainer = HeadTrainer(model, base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, steps=s.STEPS, gamma=s.GAMMA,
                           warmup_iters=s.WARMUP_ITERS, warmup_factor=s.WARMUP_FACTOR, train_fpn=train_fpn, train_backbone=args.train_backbone,
                           shadow=shadow if args.train_backbone else None, fused_step=args.fused_step,
-                          data_parallel=(rank, world, group) if args.data_parallel else None, solver=solver, max_iter=max_iter)
+                          data_parallel=(rank, world, group) if args.data_parallel else None, solver=solver, max_iter=max_iter, freeze_at=freeze_at)
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
     sampler = FrameSampler(batch, random_flip=args.random_flip, seed=args.random_seed)
@@ -801,7 +828,7 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     if world > 1:
         import torch.distributed as dist
         dist.barrier(group)               # no rank leaves before the final checkpoint is on disk
-    what = ", the FPN and res3 - res5" if args.train_backbone else " and the FPN" if train_fpn else ""
+    what = ", the FPN and " + ("res3", "res2", "the stem, res2")[2 - freeze_at] + " - res5" if args.train_backbone else " and the FPN" if train_fpn else ""
     if rank == 0:
         print("trained the head%s for %d iterations; wrote %s" % (what, trainer.iteration, written[-1]))
     return {"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line,

@@ -2,13 +2,15 @@
 ReLU + dropout gate of the head's backward pass (probabilistic_retinanet.py:403-484 under train_net.py's loop) -- and of K23
 (csrc/k23_fpn_backward.hip): the weight gradient without taps and the two gathers of the FPN's backward pass -- and of K24
 (csrc/k24_resnet_backward.hip): the 1x1 weight gradient at the backbone's widths and strides and the scatter that undoes a stride-2 pixel
-selection.  GPU only: there is no CPU path."""
+selection -- and of K30 (csrc/k30_stem_backward.hip): the stem's 7x7 weight gradient and the max-pool's backward.  GPU only: there is no CPU path."""
 import ctypes
 from typing import Optional, Sequence, Tuple
 
 import torch
 
-from . import amax, hip
+from . import amax, conv1x1, hip
+
+_STEM_BOUNDS: dict = {}     # conv1x1.normalised_input_bound's constants per (mean, std), for callers without a Stem7x7 of their own
 
 
 def _level_array(levels: Sequence[Tuple[int, int]]):
@@ -89,10 +91,10 @@ def conv1x1_wgrad(x: torch.Tensor, dy: torch.Tensor, bias: bool = True):
                     pixels, x.shape[1], dy.shape[1]))
 
 
-def _map_gather(name: str, src: torch.Tensor, h: int, w: int, C: int, rule: str, gate, add, out, record) -> torch.Tensor:
-    """The call behind col2im3x3s2_cl and subsample2_scatter_cl: entry `name` gathers the ho * wo rows of src, which hold C channels each
-    (0: they cannot; `rule` names what they should be), into dx (h * w, C).  record: the caller's (one over a batch's images, which the
-    caller attaches: over_images), None = dx's own."""
+def _map_gather(name: str, src: torch.Tensor, h: int, w: int, C: int, rule: str, gate, add, out, record, call=None) -> torch.Tensor:
+    """The call behind col2im3x3s2_cl, subsample2_scatter_cl and maxpool3x3s2_backward_cl: entry `name` gathers the ho * wo rows of src, which
+    hold C channels each (0: they cannot; `rule` names what they should be), into dx (h * w, C).  record: the caller's (one over a batch's
+    images, which the caller attaches: over_images), None = dx's own.  call(lib, dx, record): an entry with arguments of its own."""
     h, w = int(h), int(w)
     rows = ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1)
     if h < 1 or w < 1 or C < 1 or C % 4 or int(src.shape[0]) != rows:
@@ -104,8 +106,11 @@ def _map_gather(name: str, src: torch.Tensor, h: int, w: int, C: int, rule: str,
             if tuple(t.shape) != (h * w, C) or t.device != src.device:
                 raise hip.PodError("{}: {} must be ({}, {}) on {}, got {} on {}".format(name, what, h * w, C, src.device, tuple(t.shape), t.device))
     with torch.cuda.device(src.device):
-        hip.check(getattr(hip.load(), name)(src.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), h, w, C, (amax.produced(dx) if record is None else record).data_ptr(),
-                                            hip.current_stream()), name)
+        rec = amax.produced(dx) if record is None else record
+        if call is not None:
+            hip.check(call(hip.load(), dx, rec), name)
+        else:
+            hip.check(getattr(hip.load(), name)(src.data_ptr(), hip.ptr(gate), hip.ptr(add), dx.data_ptr(), h, w, C, rec.data_ptr(), hip.current_stream()), name)
     return dx
 
 
@@ -179,3 +184,52 @@ def subsample2_scatter_cl(d_small: torch.Tensor, h: int, w: int, gate: Optional[
     the pixels with even coordinates, zero elsewhere, + add).  out may be `add`."""
     _cl("pod_subsample2_scatter_cl", "d_small", d_small)
     return _map_gather("pod_subsample2_scatter_cl", d_small, h, w, int(d_small.shape[1]), "({}, C) selected rows", gate, add, out, record)
+
+
+def stem7x7_wgrad(x: torch.Tensor, ds: torch.Tensor, padded_hw: Optional[tuple] = None, mean: Optional[torch.Tensor] = None,
+                  std: Optional[torch.Tensor] = None, bound: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of the stem's folded 7x7 / stride-2 / pad-3 filter (K30, pod_stem7x7_wgrad).  x (images, 3, hi, wi) or (3, hi, wi),
+    contiguous uint8 or fp32 on the GPU: the frames as conv1x1.Stem7x7 takes them, normalised on load with mean / std (3 floats each; None:
+    already normalised) and zero outside (hi, wi) up to padded_hw; ds (images * ho * wo, 64) channels-last, ho = (h - 1) // 2 + 1 of the
+    padded extent.  Returns dW (64, 3, 7, 7) fp32.  bound: the record that bounds the normalised input (Stem7x7._input_bound: the forward's
+    in_amax; None: formed here by the same rule); ds's record is its producer's, else computed now."""
+    name = "pod_stem7x7_wgrad"
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.uint8, torch.float32) and x.is_contiguous() and x.dim() in (3, 4) and int(x.shape[-3]) == 3):
+        raise hip.PodError("{}: the frames must be a contiguous uint8 / fp32 (images, 3, h, w) tensor on the GPU, got {} {} on {}".format(
+            name, getattr(x, "dtype", None), tuple(getattr(x, "shape", ())), getattr(x, "device", None)))
+    _cl(name, "ds", ds)
+    images, hi, wi = (1 if x.dim() == 3 else int(x.shape[0])), int(x.shape[-2]), int(x.shape[-1])
+    h, w = (hi, wi) if padded_hw is None else (int(padded_hw[0]), int(padded_hw[1]))
+    if (mean is None) != (std is None) or any(t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 3 and t.is_contiguous()) for t in (mean, std)):
+        raise hip.PodError("{}: mean and std come together, 3 contiguous fp32 values each on the GPU".format(name))
+    if mean is None and x.dtype != torch.float32:
+        raise hip.PodError("{}: a uint8 frame is normalised on load: mean and std required".format(name))
+    if bound is None:
+        bound = conv1x1.normalised_input_bound(x, mean, std, _STEM_BOUNDS)
+    lib = hip.load()
+    n = int(lib.pod_stem7x7_wgrad_partials(images, hi, wi, h, w))
+    if n <= 0:
+        raise hip.PodError("{}: images >= 1 and 1 <= frame extent <= padded extent <= 16384 required (what pod_stem7x7_split accepts), got images={} "
+                           "frame {} x {} padded {} x {}".format(name, images, hi, wi, h, w))
+    rows = images * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1)
+    if tuple(ds.shape) != (rows, 64) or ds.device != x.device:
+        raise hip.PodError("{}: {} frames padded to {} x {} pair with a ({}, 64) ds on {}, got {} on {}".format(name, images, h, w, rows, x.device, tuple(ds.shape), ds.device))
+    partials = torch.empty(n, dtype=torch.float32, device=x.device)
+    dW = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        hip.check(lib.pod_stem7x7_wgrad(x.data_ptr(), 1 if x.dtype == torch.uint8 else 0, images, hi, wi, hip.ptr(mean), hip.ptr(std), ds.data_ptr(), h, w,
+                                        bound.data_ptr(), amax.of(ds).data_ptr(), dW.data_ptr(), partials.data_ptr(), hip.current_stream()), name)
+    return dW
+
+
+def maxpool3x3s2_backward_cl(s: torch.Tensor, dp: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
+                             record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of conv1x1.maxpool3x3s2_cl and of the ReLU in front of it for one (h, w) image (K30): s (h * w, C), the stem's stored
+    post-ReLU output; dp (hq * wq, C), hq = (h - 1) // 2 + 1 -> ds (h * w, C) = (s > 0) * the sum of dp over the windows whose arg-max the
+    pixel is (torch's: the first maximum in row-major order wins)."""
+    _cl("pod_maxpool3x3s2_backward_cl", "s", s)
+    _cl("pod_maxpool3x3s2_backward_cl", "dp", dp)
+    if dp.device != s.device or int(dp.shape[1]) != int(s.shape[1]):
+        raise hip.PodError("pod_maxpool3x3s2_backward_cl: s {} on {} against dp {} on {}".format(tuple(s.shape), s.device, tuple(dp.shape), dp.device))
+    return _map_gather("pod_maxpool3x3s2_backward_cl", dp, h, w, int(dp.shape[1]), "({}, C) pooled rows", s, None, out, record, call=lambda lib, dx, rec: lib.pod_maxpool3x3s2_backward_cl(
+        s.data_ptr(), dp.data_ptr(), dx.data_ptr(), int(h), int(w), int(dp.shape[1]), rec.data_ptr(), hip.current_stream()))
