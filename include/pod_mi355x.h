@@ -1038,6 +1038,34 @@ int pod_stem7x7_wgrad(const void* x, int32_t x_is_u8, int32_t images, int32_t H_
                       int32_t H, int32_t W, const float* x_amax, const float* ds_amax, float* dW, float* partials, pod_stream_t stream);
 int pod_maxpool3x3s2_backward_cl(const float* s, const float* dP, float* dS, int32_t H, int32_t W, int32_t C, float* ds_amax, pod_stream_t stream);
 
+/* ---- K31  a training batch in one launch (csrc/k31_train_batch.hip) -------------------------------------------------------------
+ * Serves: what detectron2's DatasetMapper(is_train=True) does to the decoded frames of a batch behind build_detection_train_loader(cfg)
+ * (train_net.py's loop): ResizeShortestEdge at the frame's own drawn size with PIL's bilinear filter, then RandomFlip(horizontal), the
+ * RGB -> BGR flip and the HWC -> CHW transpose -- K20's work for every frame of the batch, in ONE launch, to the byte (the two kernels
+ * share one copy of the arithmetic, csrc/pod_resize_u8.h).  Two new symbols, one new structure and one constant under POD_ABI_VERSION 18,
+ * as for K20 - K30: no entry or structure that existed changed, so the number stands.
+ *
+ * PodTrainFrame: pod_resize_frame_u8's arguments for one frame (src .. flip_channels, each as documented there), `hflip` != 0: output
+ *   column x holds the RESIZED frame's column out_w - 1 - x (resize first, then flip), and `first_tile`: the index of the frame's first
+ *   workgroup -- 0 for frame 0, and for frame i + 1 frame i's plus ceil(out_w / 64) * ceil(out_h / 4) of frame i.
+ * pod_train_batch_tiles (host only): the launch's workgroup count, the sum of the frames' tiles, from out_h / out_w alone; -1 for a NULL
+ *   table, n_frames outside 1 .. POD_TRAIN_BATCH_MAX_FRAMES or a size outside 1 .. POD_RESIZE_MAX_SIDE.
+ * pod_train_batch_u8: frames HOST (pinned: the copy is then asynchronous; the caller keeps the table unchanged until it has run, an event
+ *   after the entry's return), frames_dev dev, room for n_frames records.  One copy of the table and one launch on `stream`; every frame
+ *   writes its own contiguous planar (3, out_h, out_w) uint8 tensor at `dst`, and no byte outside it.  POD_E_INVALID before anything is
+ *   enqueued for a NULL table, n_frames out of range, a frame pod_resize_frame_u8 would refuse, a first_tile sequence or n_tiles other
+ *   than the sizes give, more than 2^31 - 1 tiles, two outputs that overlap, or an output that overlaps any frame's source. */
+#define POD_TRAIN_BATCH_MAX_FRAMES 64
+typedef struct PodTrainFrame {
+    const uint8_t* src;  int32_t in_h;  int32_t in_w;  int64_t row_stride;
+    const int32_t* xbounds;  const int32_t* xcoeffs;  int32_t xk;  int32_t reserved0;
+    const int32_t* ybounds;  const int32_t* ycoeffs;  int32_t yk;  int32_t reserved1;
+    uint8_t* dst;  int32_t out_h;  int32_t out_w;  int32_t flip_channels;  int32_t hflip;
+    int64_t first_tile;
+} PodTrainFrame;
+int64_t pod_train_batch_tiles(const PodTrainFrame* frames, int32_t n_frames);
+int pod_train_batch_u8(const PodTrainFrame* frames, PodTrainFrame* frames_dev, int32_t n_frames, int64_t n_tiles, pod_stream_t stream);
+
 /* (test support -- the dumps of the in-kernel Philox draws, of the generator itself and of the f16 split -- is declared in
  * include/pod_mi355x_test.h: the library exports those entry points for tests/ and tools/, they are not part of the drop-in boundary.) */
 

@@ -143,6 +143,11 @@ class CocoImages:
         return self.images[i]["id"]
 
     def __getitem__(self, i: int) -> dict:
+        return self.entry(i)
+
+    def entry(self, i: int, size=None) -> dict:
+        """Entry i; size: the (nh, nw) the host path resizes to in place of ResizeShortestEdge(min_size, max_size) -- a training loader's
+        drawn size (train_head --train-loader)."""
         import numpy as np
         from PIL import Image
         from . import anchors
@@ -153,7 +158,7 @@ class CocoImages:
             if self.device_resize:
                 return {"frame": torch.as_tensor(np.array(im)), "height": int(rec.get("height", h)), "width": int(rec.get("width", w)),
                         "image_id": rec["id"], "file_name": rec["file_name"]}
-            nh, nw = anchors.resize_shortest_edge(h, w, self.min_size, self.max_size)
+            nh, nw = anchors.resize_shortest_edge(h, w, self.min_size, self.max_size) if size is None else (int(size[0]), int(size[1]))
             if (nh, nw) != (h, w):
                 im = im.resize((nw, nh), Image.BILINEAR)
             arr = np.asarray(im)[:, :, ::-1]                       # RGB -> BGR

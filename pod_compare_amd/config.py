@@ -100,11 +100,13 @@ def get_cfg() -> CfgNode:
         "OUTPUT_DIR": "./output",
         "SEED": 0,
         "DATASETS": {"TRAIN": (), "TEST": ()},
-        "DATALOADER": {"NUM_WORKERS": 4},
+        # (ASPECT_RATIO_GROUPING, FILTER_EMPTY_ANNOTATIONS and INPUT.*_TRAIN / RANDOM_FLIP: detectron2's defaults, read by train_head --train-loader)
+        "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True},
         # (BASE_LR .. CHECKPOINT_PERIOD: detectron2's defaults, read by train_head)
         "SOLVER": {"IMS_PER_BATCH": 1, "STEPS": (60000, 80000), "BASE_LR": 0.001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001, "WARMUP_ITERS": 1000,
                    "WARMUP_FACTOR": 1.0 / 1000, "GAMMA": 0.1, "MAX_ITER": 40000, "CHECKPOINT_PERIOD": 5000},
-        "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR"},
+        "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR", "MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333,
+                  "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal"},
         "MODEL": {
             "META_ARCHITECTURE": "ProbabilisticRetinaNet",
             "DEVICE": "cuda",

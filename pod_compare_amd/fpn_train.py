@@ -158,11 +158,11 @@ def fpn_forward_train(fpn, feats: Sequence[Sequence[Tuple[torch.Tensor, int, int
         return list(_FpnTrain.apply(fpn, feats, len(maps), *maps, *conv_params(fpn_convs(fpn))))
 
 
-def backbone_maps(model, image: torch.Tensor):
+def backbone_maps(model, image: torch.Tensor, padded=None):
     """The frozen backbone of one frame, channels-last: ([(c3, h, w), (c4, h, w), (c5, h, w)], padded (h, w)) -- the part of
-    ProbabilisticRetinaNet._trunk_eager ahead of the FPN (`_backbone_cl`)."""
+    ProbabilisticRetinaNet._trunk_eager ahead of the FPN (`_backbone_cl`).  padded: the batch's common padded size (None: the frame's own)."""
     with torch.no_grad():
-        maps = model._backbone_cl(image) if image.is_cuda else None
+        maps = model._backbone_cl(image, padded) if image.is_cuda else None
     if maps is None:
         raise hip.PodError("training the FPN needs the channels-last HIP backbone (a frame on the model's GPU, FrozenBN folded, the split kernels selected)")
     return maps

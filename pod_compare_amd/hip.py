@@ -30,6 +30,7 @@ POD_VIS_COLOUR_ENTROPY, POD_VIS_COLOUR_FIXED, POD_VIS_COLOUR_PALETTE, POD_VIS_CO
 POD_VIS_COV_BY_RANK, POD_VIS_COV_OWN = 0, 1
 POD_VIS_LABEL_BOX, POD_VIS_LABEL_GLYPH = 3, 4
 POD_RESIZE_MAX_SIDE = 32768
+POD_TRAIN_BATCH_MAX_FRAMES = 64
 POD_SGD_CHUNK = 4096
 POD_REG_LOSS_MOMENTS, POD_REG_LOSS_ENERGY, POD_MAX_REG_SAMPLES = 1, 2, 4096
 POD_FULL_COV_NLL, POD_FULL_COV_MOMENTS, POD_FULL_COV_ENERGY = 1, 2, 3
@@ -52,13 +53,14 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_sgd_chunk_map", "pod_sgd_step", "pod_grad_bucket_layout", "pod_grad_pack",
            "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss",
            "pod_sgd_solver_workspace_bytes", "pod_sgd_step_solver", "pod_sgd_solver_reset",
-           "pod_stem7x7_wgrad_partials", "pod_stem7x7_wgrad", "pod_maxpool3x3s2_backward_cl")
+           "pod_stem7x7_wgrad_partials", "pod_stem7x7_wgrad", "pod_maxpool3x3s2_backward_cl",
+           "pod_train_batch_tiles", "pod_train_batch_u8")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
                  "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes",
-                 "pod_stem7x7_wgrad_partials")
+                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -147,6 +149,14 @@ class PodSgdSolver(Structure):
 class PodSgdSolverStatus(Structure):
     """include/pod_mi355x.h: PodSgdSolverStatus (K29, the first 32 bytes of the solver's workspace)."""
     _fields_ = [("bad_steps", c_int64), ("first_bad_iteration", c_int64), ("last_norm", c_double), ("poisoned", c_int32), ("reserved", c_int32)]
+
+
+class PodTrainFrame(Structure):
+    """include/pod_mi355x.h: PodTrainFrame (K31, one frame of pod_train_batch_u8's table)."""
+    _fields_ = [("src", c_void_p), ("in_h", c_int32), ("in_w", c_int32), ("row_stride", c_int64),
+                ("xbounds", c_void_p), ("xcoeffs", c_void_p), ("xk", c_int32), ("reserved0", c_int32),
+                ("ybounds", c_void_p), ("ycoeffs", c_void_p), ("yk", c_int32), ("reserved1", c_int32),
+                ("dst", c_void_p), ("out_h", c_int32), ("out_w", c_int32), ("flip_channels", c_int32), ("hflip", c_int32), ("first_tile", c_int64)]
 
 
 class PodError(RuntimeError):
@@ -290,6 +300,9 @@ def load() -> ctypes.CDLL:
     lib.pod_stem7x7_wgrad_partials.restype = c_int64
     lib.pod_stem7x7_wgrad.argtypes = [P, c_int32, c_int32, c_int32, c_int32, P, P, P, c_int32, c_int32, P, P, P, P, P]
     lib.pod_maxpool3x3s2_backward_cl.argtypes = [P, P, P, c_int32, c_int32, c_int32, P, P]
+    lib.pod_train_batch_tiles.argtypes = [POINTER(PodTrainFrame), c_int32]
+    lib.pod_train_batch_tiles.restype = c_int64
+    lib.pod_train_batch_u8.argtypes = [POINTER(PodTrainFrame), P, c_int32, c_int64, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

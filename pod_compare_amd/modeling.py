@@ -1055,21 +1055,30 @@ class ProbabilisticRetinaNet(_TracksStorage):
             self._cl_ok = self.bottom_up.cl_eligible() and self.fpn.cl_eligible()       # (cached once true: folding is one-way)
         return self._cl_ok
 
-    def _backbone_cl(self, image: torch.Tensor):
-        """Frame -> ([(c3, h, w), (c4, h, w), (c5, h, w)] channels-last, padded (h, w)) when the channels-last HIP backbone takes it, else None."""
+    def _backbone_cl(self, image: torch.Tensor, padded: Optional[Tuple[int, int]] = None):
+        """Frame -> ([(c3, h, w), (c4, h, w), (c5, h, w)] channels-last, padded (h, w)) when the channels-last HIP backbone takes it, else None.
+        padded: the size the frame is run against (a training batch's common ImageList size, a multiple of 32 that holds the frame: the
+        stem reads everything outside the frame as zero after normalisation); None: the frame's own anchors.padded_size.  Only the HIP
+        stem pads on load: with `padded` anything else is an error."""
+        if padded is not None:
+            padded = _check_padded(image, padded)
         if (image.is_cuda and image.device == self.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
                 and image.dtype in (torch.uint8, torch.float32) and self._cl_backbone(self.pixel_mean) and self.bottom_up.hip_stem_ok()):
             # the frame as the loader hands it over: pod_stem7x7_split normalises ((x - mean) / std, PR:96) and pads on load
-            padded = _anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
+            if padded is None:
+                padded = _anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
             return self.bottom_up.forward_cl(None, frame=(image, self.pixel_mean.reshape(3), self.pixel_std.reshape(3), padded)), padded
+        if padded is not None:
+            raise hip.PodError("a frame is run against a common padded size only by the channels-last HIP backbone (a (3, h, w) uint8 / fp32 frame "
+                               "on the model's GPU, FrozenBN folded, the split kernels and the HIP stem selected)")
         x = self.preprocess_image(image)
         if self._cl_backbone(x):
             return self.bottom_up.forward_cl(x), tuple(x.shape[-2:])      # channels-last trunk on pod_conv1x1_split + pod_wino_conv3x3[_split]
         return None
 
-    def _trunk_eager(self, image: torch.Tensor):
-        """Frame -> (the five FPN maps, padded (h, w)): everything ahead of the head."""
-        cl = self._backbone_cl(image)
+    def _trunk_eager(self, image: torch.Tensor, padded: Optional[Tuple[int, int]] = None):
+        """Frame -> (the five FPN maps, padded (h, w)): everything ahead of the head.  padded: as _backbone_cl's."""
+        cl = self._backbone_cl(image, padded)
         if cl is not None:
             return self.fpn.forward_cl(cl[0]), cl[1]
         x = self.preprocess_image(image)                                 # the NCHW path (CPU tensors, the tests' reference; normalised a second time here)
@@ -1085,6 +1094,15 @@ class ProbabilisticRetinaNet(_TracksStorage):
     def _forward_eager(self, image: torch.Tensor, n: int, mc_dropout: bool, skip_unused_last_run: bool) -> HeadOutputs:
         feats, padded = self._trunk_eager(image)
         return self._head_eager(feats, padded, image.shape[-2:], n, mc_dropout, skip_unused_last_run)
+
+
+def _check_padded(image: torch.Tensor, padded) -> Tuple[int, int]:
+    """A common padded size for `image` (3, h, w): two multiples of the FPN's divisibility that hold the frame."""
+    ph, pw = int(padded[0]), int(padded[1])
+    d = _anchors.SIZE_DIVISIBILITY
+    if len(padded) != 2 or ph % d or pw % d or ph < int(image.shape[-2]) or pw < int(image.shape[-1]):
+        raise ValueError("padded = {} does not hold a frame of {} x {} in multiples of {}".format(tuple(padded), int(image.shape[-2]), int(image.shape[-1]), d))
+    return ph, pw
 
 
 def resize_test_image(image: torch.Tensor, min_size: int = 800, max_size: int = 1333) -> torch.Tensor:

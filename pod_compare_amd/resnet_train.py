@@ -26,7 +26,7 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import nn
 
-from . import conv1x1, hip, modeling, wgrad, wino
+from . import amax, conv1x1, hip, modeling, wgrad, wino
 from .conv_forms import stem_of
 from .fpn_train import _stacked
 from .head_train import backward_gemm, conv_params, flat_grads, flipped3x3, patch_matrix, transposed1x1
@@ -99,20 +99,23 @@ def _require(blocks) -> None:
                            "of conv1's stride, 1 or 2)")
 
 
-def _require_frame(model, image) -> Tuple[int, int]:
-    """The padded (h, w) of a frame the channels-last HIP backbone takes, as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size)."""
+def _require_frame(model, image, padded=None) -> Tuple[int, int]:
+    """The padded (h, w) of a frame the channels-last HIP backbone takes, as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size;
+    padded: a batch's common padded size instead, checked to hold the frame)."""
     ok = (torch.is_tensor(image) and image.is_cuda and image.device == model.device and image.dim() == 3 and image.shape[0] == 3 and image.is_contiguous()
           and image.dtype in (torch.uint8, torch.float32) and model._cl_backbone(model.pixel_mean) and model.bottom_up.hip_stem_ok())
     if not ok:
         raise hip.PodError("training the backbone needs the channels-last HIP backbone (a (3, h, w) uint8 / fp32 frame on the model's GPU, FrozenBN "
                            "folded, the split kernels and the HIP stem selected)")
+    if padded is not None:
+        return modeling._check_padded(image, padded)
     return modeling._anchors.padded_size(int(image.shape[1]), int(image.shape[2]))
 
 
-def res2_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+def res2_maps(model, image: torch.Tensor, padded=None) -> Tuple[torch.Tensor, int, int]:
     """The frozen stem, max-pool and res2 of one frame under no_grad, channels-last: (t (h * w, 256), h, w) -- what detectron2's FREEZE_AT = 2
-    leaves untrained.  The frame is padded as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size)."""
-    padded = _require_frame(model, image)
+    leaves untrained.  The frame is padded as ProbabilisticRetinaNet._backbone_cl pads it (anchors.padded_size; padded: to a batch's common size)."""
+    padded = _require_frame(model, image, padded)
     with torch.no_grad():
         return model.bottom_up.forward_cl(None, frame=(image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded), stop_after_res2=True)
 
@@ -123,10 +126,10 @@ def _stem_pool(stem: nn.Conv2d, image: torch.Tensor, mean: torch.Tensor, std: to
     return (s, h, w), conv1x1.maxpool3x3s2_cl(s, h, w)
 
 
-def pool_maps(model, image: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+def pool_maps(model, image: torch.Tensor, padded=None) -> Tuple[torch.Tensor, int, int]:
     """The frozen stem and max-pool of one frame under no_grad, channels-last: (t (h * w, 64), h, w) -- what detectron2's FREEZE_AT = 1 leaves
-    untrained, res2's input."""
-    padded = _require_frame(model, image)
+    untrained, res2's input.  padded: a batch's common padded size (None: the frame's own)."""
+    padded = _require_frame(model, image, padded)
     with torch.no_grad():
         return _stem_pool(_conv_of(model.bottom_up.stem), image, model.pixel_mean.reshape(3), model.pixel_std.reshape(3), padded)[1]
 
@@ -152,22 +155,31 @@ class _StemTrain(torch.autograd.Function):
         dp = [torch.zeros(((h - 1) // 2 + 1) * ((w - 1) // 2 + 1), 64, dtype=torch.float32, device=kept[0].device) if g is None else g.contiguous() for g in g_maps]
         ds = torch.empty((B * h * w, 64), dtype=torch.float32, device=kept[0].device)
         wgrad.over_images(B, ds, lambda b, rows, rec: wgrad.maxpool3x3s2_backward_cl(kept[b], dp[b], h, w, out=rows(ds), record=rec))
-        x = frames[0].unsqueeze(0) if B == 1 else torch.stack(list(frames))      # (the sampler gives a batch one shape)
-        dW = wgrad.stem7x7_wgrad(x, ds, padded, mean, std, bound=stem_of(stem)._input_bound(x, mean, std))
+        if all(tuple(f.shape) == tuple(frames[0].shape) for f in frames):
+            x = frames[0].unsqueeze(0) if B == 1 else torch.stack(list(frames))      # one shape: one weight gradient over the stacked frames
+            dW = wgrad.stem7x7_wgrad(x, ds, padded, mean, std, bound=stem_of(stem)._input_bound(x, mean, std))
+        else:
+            # frames of several sizes against one padded size: a weight gradient per image on its rows of dS, added in image order
+            dW, rows, rec = None, h * w, amax.of(ds)              # (the batch's record bounds every image's rows of dS)
+            for b, f in enumerate(frames):
+                g = wgrad.stem7x7_wgrad(f, amax.attach(ds[b * rows:(b + 1) * rows], rec), padded, mean, std, bound=stem_of(stem)._input_bound(f, mean, std))
+                dW = g if dW is None else dW.add_(g)
         ctx.state = None
         return (None,) * 6 + (dW,)
 
 
-def stem_forward_train(model, images: Sequence[torch.Tensor], tap=None) -> list:
+def stem_forward_train(model, images: Sequence[torch.Tensor], tap=None, padded=None) -> list:
     """The stem and its max-pool with a backward pass (FREEZE_AT = 0): per image the (t (h * w, 64), h, w) res2 starts from, B frames of one
-    shape.  The maps carry a grad_fn that reaches the stem's (folded) filter: K30's pool backward per image into one stacked dS, then one
+    shape -- or, with `padded`, the batch's common padded size, of any shapes it holds (the weight gradient is then K30 once per image,
+    the results added in image order; a batch of one shape makes the launches it makes without `padded`).  The maps carry a grad_fn that reaches the stem's (folded) filter: K30's pool backward per image into one stacked dS, then one
     weight gradient over the batch's stacked frames.  The stem computes no input gradient."""
     images = list(images)
     if not images:
         raise hip.PodError("stem_forward_train: at least one frame")
-    padded = _require_frame(model, images[0])
+    common = padded is not None
+    padded = _require_frame(model, images[0], padded)
     for im in images[1:]:
-        if _require_frame(model, im) != padded or tuple(im.shape) != tuple(images[0].shape) or im.dtype != images[0].dtype:
+        if _require_frame(model, im, padded if common else None) != padded or im.dtype != images[0].dtype or (not common and tuple(im.shape) != tuple(images[0].shape)):
             raise hip.PodError("stem_forward_train: a batch holds frames of one shape and type, got {} {} and {} {}".format(
                 tuple(images[0].shape), images[0].dtype, tuple(im.shape), im.dtype))
     stem = _conv_of(model.bottom_up.stem)

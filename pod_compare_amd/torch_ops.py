@@ -19,6 +19,9 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
     conv1x1_filter_split / conv1x1_split, stem7x7_filter_split / stem7x7_split, maxpool3x3s2_cl, im2col3x3s2_cl
                  the channels-last trunk (round 4): the backbone's / FPN's 1x1 convolutions with bias / residual / ReLU in the store, the
                  7x7 stem taking the frame as loaded (normalisation + padding on load) and its max-pool
+    train_batch_u8
+                 a training batch's network inputs in one launch (K31): decoded (h, w, 3) uint8 frames -> per frame the (3, nh, nw) uint8
+                 tensor PIL's bilinear resize at sizes[2 i], sizes[2 i + 1], the flip where hflips[i], BGR and the transpose give
 """
 from typing import List, Tuple
 
@@ -43,6 +46,7 @@ _LIB.define("stem7x7_filter_split(Tensor weight) -> Tensor")
 _LIB.define("stem7x7_split(Tensor frame, Tensor Ws, Tensor? bias, Tensor? mean, Tensor? std, int padded_h, int padded_w, bool relu=True) -> Tensor")
 _LIB.define("maxpool3x3s2_cl(Tensor x, int h, int w) -> Tensor")
 _LIB.define("im2col3x3s2_cl(Tensor x, int h, int w, bool relu=False) -> Tensor")
+_LIB.define("train_batch_u8(Tensor[] frames, int[] sizes, bool[] hflips, bool bgr=True) -> Tensor[]")
 
 _PATHS = {}            # key -> [HotPath, anchor identity, the anchor tensors]; insertion order = LRU order
 _MAX_PATHS = 16
@@ -286,7 +290,17 @@ def _im2col3x3s2_cl(x, h, w, relu=False) -> torch.Tensor:
     return y
 
 
+def _train_batch_u8(frames, sizes, hflips, bgr=True) -> List[torch.Tensor]:
+    from . import train_batch
+    torch._check(len(frames) >= 1 and len(sizes) == 2 * len(frames) and len(hflips) == len(frames), lambda: "train_batch_u8: (nh, nw) and a flip per frame")
+    for f in frames:
+        torch._check(f.is_cuda and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3, lambda: "frames: CUDA uint8 (h, w, 3)")
+    pairs = [(int(sizes[2 * i]), int(sizes[2 * i + 1])) for i in range(len(frames))]
+    return train_batch.train_batch_u8(list(frames), pairs, [bool(v) for v in hflips], bgr=bool(bgr))
+
+
 _IMPL = torch.library.Library("pod_mi355x", "IMPL")
+_IMPL.impl("train_batch_u8", _train_batch_u8, "CUDA")
 _IMPL.impl("im2col3x3s2_cl", _im2col3x3s2_cl, "CUDA")
 _IMPL.impl("conv1x1_filter_split", _conv1x1_filter_split, "CUDA")
 _IMPL.impl("conv1x1_split", _conv1x1_split, "CUDA")

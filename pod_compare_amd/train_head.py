@@ -3,9 +3,11 @@
     python -m pod_compare_amd.train_head --coco-json <gt.json> --image-root <dir> --data-dir <checkpoints root> \
         --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn | --train-backbone]
         [--fused-step] [--guard-nonfinite] [--random-flip] [--resume] [--data-parallel [--backend nccl|gloo] [--share-gpu]]
+        [--train-loader [--no-shuffle] [--batch-on-gpu]]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
-shape together; a shape's frames wait until a batch of them is complete), the frozen backbone + FPN per image under no_grad through the
+shape together; a shape's frames wait until a batch of them is complete -- with --train-loader, below, frames of one aspect-ratio
+group and any sizes), the frozen backbone + FPN per image under no_grad through the
 existing forward, head.forward_train on the stacked features (pod_compare_amd/head_train.py), model.losses (K21; `current_step`
 advanced every iteration as PR:146 does), backward() through the head's HIP backward (K22), torch.optim.SGD (momentum, weight decay)
 under detectron2's WarmupMultiStepLR; the solver settings are SOLVER.*.  Checkpoints carry detectron2's names
@@ -63,8 +65,22 @@ all-reduce sums it over the ranks and K25 steps from the bucket.  Each rank keep
 losses) and writes checkpoints, whose `pod_trainer` then carries `world` and `ranks`, every rank's loss state -- --resume continues at
 the same world size only.  SOLVER.IMS_PER_BATCH must be a multiple of W.
 
-Still NOT the reference's full trainer: the all-reduce does not overlap the backward pass, and a data-parallel rank reads its frames
-without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies); under settings that
+--train-loader [--no-shuffle] [--batch-on-gpu]: the first line of train_net.py's loop, build_detection_train_loader(cfg), as a data plan
+that is a pure function of the json, the config and --random-seed (pod_compare_amd/train_loader.py).  Frames without a usable annotation
+are dropped (DATALOADER.FILTER_EMPTY_ANNOTATIONS); every pass is a fresh seeded permutation (TrainingSampler; --no-shuffle: file order);
+per frame the short edge is drawn from INPUT.MIN_SIZE_TRAIN under MIN_SIZE_TRAIN_SAMPLING (`choice`, `range`), capped by MAX_SIZE_TRAIN,
+then the flip under INPUT.RANDOM_FLIP (`horizontal`, `none`; --random-flip forces it on) -- the TEST keys are not read; batches are
+grouped by aspect ratio only (DATALOADER.ASPECT_RATIO_GROUPING: w > h and the rest), so a batch holds frames of several sizes: each is run
+against the batch's common padded size, anchors.padded_size of the largest height and width (ImageList.from_tensors; the stem reads
+zero outside the frame after normalisation), its ground truth scaled and mirrored against its OWN size.  The frames a rank will need are
+known ahead, so they are read on DATALOADER.NUM_WORKERS threads in plan order -- for a data-parallel rank too, which still takes its
+slice of the one-rank run's global batches.  --batch-on-gpu: the threads only decode, and ONE launch (K31, pod_compare_amd/train_batch.py)
+resizes, mirrors, flips to BGR and transposes the rank's frames; the bytes are the host path's.  The checkpoint's sampler state is then
+the plan's (kind `train_loader`: the permutation generator at the start of the pass, the draw generator, the position, the waiting
+entries with their draws); --resume across the two kinds of data order is refused.  Without the flag nothing of this is imported.
+
+Still NOT the reference's full trainer: the all-reduce does not overlap the backward pass, and without --train-loader a data-parallel
+rank reads its frames without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies); under settings that
 compute a gradient norm, or the guard, the solver's 32-byte status is read with it and before a checkpoint.
 """
 import argparse
@@ -317,23 +333,26 @@ class HeadTrainer:
                 else:
                     self.opt.state[p]["momentum_buffer"] = state[name].to(device=p.device, dtype=p.dtype).clone()
 
-    def features(self, images: Sequence[torch.Tensor]):
+    def features(self, images: Sequence[torch.Tensor], padded=None):
         """The frozen backbone + FPN per image -> (per-level (B, 256, H, W) features, padded (h, w)).  train_fpn: only the backbone is
-        frozen; the FPN runs on the batch's c3 - c5 with grad (fpn_train.fpn_forward_train)."""
-        per_image, padded = [], None
+        frozen; the FPN runs on the batch's c3 - c5 with grad (fpn_train.fpn_forward_train).  padded: the batch's common padded size
+        (--train-loader: anchors.padded_size of the largest height and width, detectron2's ImageList.from_tensors) -- every frame is run
+        against it, whatever its own size; None: the frames are of one padded size, their own, and anything else raises."""
+        per_image, common = [], None if padded is None else tuple(int(v) for v in padded)
         if self.train_backbone and self.freeze_at == 2:
             # the stem and res2 frozen, per image; res3 - res5 and the FPN on the batch with grad
-            res2 = [res2_maps(self.model, im) for im in images]
-            padded = _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
+            res2 = [res2_maps(self.model, im, common) for im in images]
+            padded = common if common is not None else _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
             return fpn_forward_train(self.model.fpn, resnet_forward_train(self.model.bottom_up, res2)), padded
         if self.train_backbone:
             # FREEZE_AT 1: the stem and its pool frozen, per image; 0: they run with grad on the batch.  res2 - res5 and the FPN on the batch with grad
-            maps = [pool_maps(self.model, im) for im in images] if self.freeze_at == 1 else stem_forward_train(self.model, images)
-            padded = _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
+            maps = [pool_maps(self.model, im, common) for im in images] if self.freeze_at == 1 else stem_forward_train(self.model, images, padded=common)
+            padded = common if common is not None else _padded_size(int(images[0].shape[-2]), int(images[0].shape[-1]))
             return fpn_forward_train(self.model.fpn, resnet_forward_train(self.model.bottom_up, maps, self.freeze_at)), padded
+        padded = None
         if self.train_fpn:
             for im in images:
-                maps, pad = backbone_maps(self.model, im)
+                maps, pad = backbone_maps(self.model, im, common)
                 if padded is not None and tuple(pad) != tuple(padded):
                     raise ValueError("a batch holds frames of one padded size, got {} and {}".format(padded, pad))
                 padded = tuple(pad)
@@ -341,7 +360,7 @@ class HeadTrainer:
             return fpn_forward_train(self.model.fpn, per_image), padded
         with torch.no_grad():
             for im in images:
-                feats, pad = self.model._trunk_eager(im)
+                feats, pad = self.model._trunk_eager(im, common)
                 if padded is not None and tuple(pad) != tuple(padded):
                     raise ValueError("a batch holds frames of one padded size, got {} and {}".format(padded, pad))
                 padded = tuple(pad)
@@ -533,6 +552,20 @@ class FrameSampler:
         return [[int(i), int(f)] for i, f in state["pending"]]
 
 
+SAMPLER_KINDS = ("frame_sampler", "train_loader")       # FrameSampler's state carries no `kind`; train_loader.TrainPlan's names itself
+
+
+def check_sampler_kind(state: Optional[dict], train_loader: bool, path: str) -> None:
+    """--resume: SystemExit naming the file and both kinds unless the checkpoint's data order is of the kind this run continues."""
+    if state is None:
+        return
+    wrote = (state.get("sampler") or {}).get("kind", SAMPLER_KINDS[0])
+    runs = SAMPLER_KINDS[1 if train_loader else 0]
+    if wrote != runs:
+        raise SystemExit("--resume: the data order in {} is of kind `{}`, this run's is `{}`: resume it {} --train-loader".format(
+            path, wrote, runs, "with" if wrote == SAMPLER_KINDS[1] else "without"))
+
+
 def loss_state_of(trainer: HeadTrainer) -> dict:
     """The loss state of this trainer's model as a checkpoint holds it (a rank's own under data parallelism)."""
     ls = trainer.model.loss_state
@@ -592,7 +625,9 @@ def restore_trainer(trainer: HeadTrainer, state: dict, path: str) -> None:
 def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0],
                                  epilog="A step takes SOLVER.IMS_PER_BATCH frames of ONE resized shape: the sampler batches frames of equal shape "
-                                        "together, in data-set order; frames of a shape wait until a batch of them is complete.  Only the head "
+                                        "together, in data-set order; frames of a shape wait until a batch of them is complete -- unless "
+                                        "--train-loader is given: then a batch holds frames of one aspect-ratio group, of any sizes, in "
+                                        "detectron2's shuffled order at INPUT.MIN_SIZE_TRAIN, padded to one size.  Only the head "
                                         "trains, and with --train-fpn the FPN; the ResNet stays frozen unless --train-backbone is given.")
     here = os.path.dirname(os.path.abspath(__file__))
     ap.add_argument("--config-file", default=os.path.join(here, "configs/BDD-Detection/retinanet/retinanet_R_50_FPN_1x_reg_cls_var_dropout.yaml"))
@@ -629,6 +664,14 @@ def arg_parser():
                                                                    "FloatingPointError before anything is written; implies --fused-step")
     ap.add_argument("--random-flip", action="store_true", help="detectron2's RandomFlip: every frame is mirrored with probability 0.5 (drawn in "
                                                                "data order from --random-seed), its boxes with it")
+    ap.add_argument("--train-loader", action="store_true", help="detectron2's training loader (pod_compare_amd/train_loader.py): frames without usable "
+                                                                "annotations dropped (DATALOADER.FILTER_EMPTY_ANNOTATIONS), a seeded shuffle per pass, "
+                                                                "INPUT.MIN_SIZE_TRAIN / MAX_SIZE_TRAIN / MIN_SIZE_TRAIN_SAMPLING and RANDOM_FLIP drawn per "
+                                                                "frame, batches grouped by aspect ratio only (DATALOADER.ASPECT_RATIO_GROUPING) and padded "
+                                                                "to one size, read ahead on the loader threads -- for a data-parallel rank too")
+    ap.add_argument("--no-shuffle", action="store_true", help="--train-loader: keep the json's file order")
+    ap.add_argument("--batch-on-gpu", action="store_true", help="--train-loader: the loader threads only decode; ONE launch (K31) resizes, mirrors, "
+                                                                "flips to BGR and transposes the batch's frames; bit-identical to the host path")
     ap.add_argument("--resume", action="store_true", help="continue the run OUTPUT_DIR/last_checkpoint stopped in: its weights and its trainer state "
                                                           "(iteration, loss state, momentum, data position); refused if the file carries none")
     ap.add_argument("--data-parallel", action="store_true", help="one rank of a data-parallel run (RANK / WORLD_SIZE / LOCAL_RANK, as torch.distributed.run "
@@ -669,6 +712,14 @@ def main(argv=None):
             dist.destroy_process_group()
 
 
+def _ground_truth(path: str) -> dict:
+    with open(path, "r") as f:
+        gt = json.load(f)
+    if "annotations" not in gt:
+        raise SystemExit("--coco-json needs `annotations`: the head is trained against ground truth")
+    return gt
+
+
 def _run(args, rank: int, world: int, group, bind: bool = False):
     """main behind its arguments and process group: rank `rank` of `world` (1: the one-GPU run).  bind: this process was started as a rank
     and is bound to its GPU's NUMA node, as apply_net binds its ranks (a caller that brought its own process group keeps its affinity)."""
@@ -703,6 +754,19 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
             resume_from, " + ".join(resume_state.get("trained", [])) or "nothing", " + ".join(trains)))
     if resume_state is not None:
         check_world(resume_state, world, resume_from)
+    check_sampler_kind(resume_state, args.train_loader, resume_from)
+    if (args.no_shuffle or args.batch_on_gpu) and not args.train_loader:
+        raise SystemExit("--no-shuffle and --batch-on-gpu belong to --train-loader")
+    plan, gt = None, None
+    if args.train_loader:         # the whole data order from the config and the json alone: SystemExit for a key the loader does not run or a
+        from . import train_loader                    # record without height / width, before a model is built
+        plan_cfg = train_loader.plan_settings(cfg, random_flip=args.random_flip, shuffle=not args.no_shuffle, seed=args.random_seed)
+        gt = _ground_truth(args.coco_json)
+        planned = train_loader.planned_indices(gt["images"], gt["annotations"], evaluation_category_map(args.train_dataset, args.test_dataset),
+                                               plan_cfg.filter_empty)
+        if len(planned) < len(gt["images"]):
+            say("Removed {} images with no usable annotations. {} images left.".format(len(gt["images"]) - len(planned), len(planned)), flush=True)
+        plan = train_loader.TrainPlan(train_loader.frame_sizes(gt["images"], args.coco_json), planned, plan_cfg)
     first, last = rank_slice(max(1, int(cfg.SOLVER.IMS_PER_BATCH)), rank, world)           # this rank's frames of every global batch
     dev = torch.device(args.device)
     torch.cuda.set_device(dev)
@@ -710,15 +774,13 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         from . import hostbind
         b = hostbind.bind_rank_to_gpu_numa(dev.index or 0)
         say("rank %d: %s pci %s numa node %s -> %s" % (rank, dev, b["pci"], b["numa_node"], b["cpus"] if b["bound"] else "not bound (%s)" % b.get("why_not", "off")))
-    with open(args.coco_json, "r") as f:
-        gt = json.load(f)
-    if "annotations" not in gt:
-        raise SystemExit("--coco-json needs `annotations`: the head is trained against ground truth")
+    if gt is None:
+        gt = _ground_truth(args.coco_json)
     by_image: Dict[object, List[dict]] = {}
     for a in gt["annotations"]:
         by_image.setdefault(a["image_id"], []).append(a)
     cat_map = evaluation_category_map(args.train_dataset, args.test_dataset)
-    dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, device_resize=args.batch_on_gpu)
     # the model twice from one seed: on the device with FrozenBN folded (what runs), and unfolded on the CPU (what a checkpoint describes)
     load = not args.random_init or bool(resume_from)       # (a resumed run's weights are the checkpoint's, whatever the first run started from)
     torch.manual_seed(args.random_seed)
@@ -742,8 +804,8 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     batch, period = max(1, int(s.IMS_PER_BATCH)), int(s.CHECKPOINT_PERIOD)
     workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
     sampler = FrameSampler(batch, random_flip=args.random_flip, seed=args.random_seed)
-    saved = dict(train_fpn=train_fpn, train_backbone=args.train_backbone, masters=trainer.masters, trainer=trainer, sampler=sampler,
-                 random_seed=args.random_seed)
+    saved = dict(train_fpn=train_fpn, train_backbone=args.train_backbone, masters=trainer.masters, trainer=trainer,
+                 sampler=sampler if plan is None else plan, random_seed=args.random_seed)
 
     def frame(d: dict, flipped: bool):
         """One loader entry on the device with its ground truth in network-input pixels, mirrored if the draw said so."""
@@ -780,7 +842,14 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         if rank == 0:
             written.append(save_checkpoint(model, shadow, cfg.OUTPUT_DIR, name, it, ranks=ranks, **saved))
 
-    if resume_state is not None:
+    if resume_state is not None and plan is not None:
+        restore_trainer(trainer, resume_state, resume_from)
+        try:
+            plan.load_state(resume_state["sampler"])
+        except (ValueError, KeyError) as e:
+            raise SystemExit("--resume: {}: {}".format(resume_from, e))
+        say("resumed %s at iteration %d" % (resume_from, trainer.iteration), flush=True)
+    elif resume_state is not None:
         restore_trainer(trainer, resume_state, resume_from)
         for index, flipped in sampler.load_state(resume_state["sampler"]):       # the frames that waited in the buckets, in arrival order
             if not 0 <= index < len(dataset) or file_frame(index, bool(flipped)) is not None:
@@ -792,6 +861,25 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         folded = [c.weight for c in trainer.masters.convs] if trainer.masters is not None else []
         broadcast_tensors(trainer.params + folded + trainer.fused.buffers, group)
     written, last_line, stalled = [], None, 0
+    extra = {}
+
+    def after_step(res):
+        """The log line and the periodic checkpoint behind a step."""
+        nonlocal last_line
+        it = trainer.iteration
+        if args.log_period > 0 and (it % args.log_period == 0 or it == max_iter):
+            norm = trainer.grad_norm(trainer.check_finite())                      # (FloatingPointError after a bad step, under --guard-nonfinite)
+            shown = trainer.mean_losses() if args.data_parallel else res          # (the rank means, from the bucket's tail)
+            last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(shown["loss_cls"]), float(shown["loss_box_reg"]),
+                                                                              trainer.lr)
+            if norm is not None:
+                last_line += "  grad_norm %.6g" % norm
+            say(last_line, flush=True)
+        if period > 0 and it % period == 0 and it < max_iter:
+            write("model_%07d" % (it - 1), it)
+
+    if plan is not None:
+        extra = _train_on_plan(args, plan, dataset, trainer, by_image, cat_map, dev, workers, first, last, max_iter, after_step)
     while trainer.iteration < max_iter:
         progressed = False
         indices = range(sampler.next_index, len(dataset))
@@ -806,17 +894,8 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
             feats, padded = trainer.features(images)
             res = trainer.step(feats, padded, tuple(images[0].shape[-2:]), gb, gc)
             progressed = True
+            after_step(res)
             it = trainer.iteration
-            if args.log_period > 0 and (it % args.log_period == 0 or it == max_iter):
-                norm = trainer.grad_norm(trainer.check_finite())                      # (FloatingPointError after a bad step, under --guard-nonfinite)
-                shown = trainer.mean_losses() if args.data_parallel else res          # (the rank means, from the bucket's tail)
-                last_line = "iter %d  loss_cls %.6f  loss_box_reg %.6f  lr %.6g" % (it, float(shown["loss_cls"]), float(shown["loss_box_reg"]),
-                                                                                  trainer.lr)
-                if norm is not None:
-                    last_line += "  grad_norm %.6g" % norm
-                say(last_line, flush=True)
-            if period > 0 and it % period == 0 and it < max_iter:
-                write("model_%07d" % (it - 1), it)
             if it >= max_iter:
                 break
         else:
@@ -831,8 +910,52 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
     what = ", the FPN and " + ("res3", "res2", "the stem, res2")[2 - freeze_at] + " - res5" if args.train_backbone else " and the FPN" if train_fpn else ""
     if rank == 0:
         print("trained the head%s for %d iterations; wrote %s" % (what, trainer.iteration, written[-1]))
-    return {"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line,
-            "trainer": trainer}
+    return dict({"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line,
+                 "trainer": trainer}, **extra)
+
+
+def _train_on_plan(args, plan, dataset, trainer, by_image, cat_map, dev, workers, first, last, max_iter, after_step) -> dict:
+    """--train-loader's loop: the plan's global batches, this rank's entries [first, last) of each, read ahead pass by pass on `workers`
+    threads (a batch that completes across a pass boundary belongs to the pass it completes in; the waiting entries carry over inside the
+    plan).  The plan moves batch by batch, so a checkpoint's state is the position behind the last trained batch.  A frame's ground truth
+    is scaled by (nw / w, nh / h) and mirrored against the frame's OWN resized width; the batch's frames are run against one padded size,
+    anchors.padded_size of their largest height and width (detectron2's ImageList.from_tensors), which is also the `image_hw` handed
+    to forward_train (informational).  Returns what main's result gains: the plan, the batches trained and the loader wait in seconds."""
+    import time
+    from . import train_loader
+    frames = train_loader.PlannedFrames(dataset)
+    trained, wait = [], 0.0
+    while trainer.iteration < max_iter:
+        ahead = plan.until_pass_end(limit=max_iter - trainer.iteration)
+        stream = iter(Prefetched(frames, [e for b in ahead for e in b[first:last]], workers=workers))
+        try:
+            for _ in ahead:
+                mine = plan.next_batch()[first:last]
+                t0 = time.perf_counter()
+                loaded = [next(stream)[1] for _ in mine]
+                wait += time.perf_counter() - t0
+                if args.batch_on_gpu:           # K31: the decoded frames -> the network inputs, one launch
+                    from . import train_batch
+                    images = train_batch.train_batch_u8([d["frame"].to(dev, non_blocking=True) for d in loaded], [e.size for e in mine],
+                                                        [e.flipped for e in mine])
+                else:                           # resized by the loader threads at the drawn size; mirrored here
+                    images = [d["image"].to(dev, non_blocking=True) for d in loaded]
+                    images = [im.flip(-1) if e.flipped else im for im, e in zip(images, mine)]
+                gb, gc = [], []
+                for d, e in zip(loaded, mine):
+                    boxes, classes = image_ground_truth(by_image.get(d["image_id"], []), cat_map, e.size[1] / float(d["width"]), e.size[0] / float(d["height"]))
+                    gb.append(hflip_boxes(boxes, float(e.size[1])) if e.flipped else boxes)
+                    gc.append(classes)
+                padded = train_loader.batch_padded_size(mine)
+                feats, padded = trainer.features(images, padded=padded)
+                res = trainer.step(feats, padded, tuple(padded), gb, gc)
+                trained.append(mine)
+                after_step(res)
+                if trainer.iteration >= max_iter:
+                    break
+        finally:
+            stream.close()
+    return {"plan": plan, "trained": trained, "loader_wait": wait}
 
 
 if __name__ == "__main__":
