@@ -1137,6 +1137,54 @@ int pod_run_image_part(const PodConfig* cfg, const PodLevel* levels, const PodWo
                   int32_t box_merge_mode, int32_t cls_merge_mode, int32_t image_h, int32_t image_w,
                   int32_t out_h, int32_t out_w, const PodDetections* out, int32_t parts, pod_stream_t stream);
 
+/* ---- K32  retinanet_inference (csrc/k32_retinanet_inference.hip) ----------------------------------------------------------------
+ * Replaces: what the reference model runs in EVAL mode (PR:156-166: `self.inference(...)`, then `detector_postprocess`), i.e. detectron2's
+ * RetinaNet.inference_single_image (modeling/meta_arch/retinanet.py of the v0.1 line the reference was written against) and
+ * detector_postprocess (modeling/postprocessing.py) -- the routine `Trainer.test` / `--eval-only` of train_net.py:67-76 evaluates, NOT the
+ * probabilistic post-processing of PI.  It differs from pod_run_image's path: a level ranks its FLATTENED (anchor, class) scores, so one
+ * anchor may yield several detections of different classes; means only are decoded, no covariance.
+ * Input: the eval-mode head output as PodLevel planes, cfg->n_runs == 1; cls_var / reg_var / eps_cls are ignored.
+ *
+ * Ordering contract (DESIGN.md "K32"): the flat index of an entry inside its level is f = (cell * A + a) * K + k -- the order of
+ * permute_to_N_HWA_K(...).flatten() -- an entry is a candidate iff sigmoid(logit) > cfg->score_thresh (fp32), candidates rank by DESCENDING
+ * LOGIT (-0.0 == 0.0), ties to the lower f; a level keeps its first min(cfg->topk, candidates) ranked candidates.  The key of a candidate:
+ *     key = (order_bits(logit) << 32) | (0xFFFFFFFF - f),   order_bits = float bits with the sign bit flipped (negative: all bits flipped)
+ * -- K1's key convention with the logit in place of the score (sigmoid is monotone), so pod_level_topk's select and sort rank it unchanged.
+ *
+ * pod_retinanet_score : ONE streaming read of cls (4 * R * K bytes); appends the keys of level l to cand_keys + anchor_base_l * K, count
+ *                       in cand_count[l].  cand_keys : dev uint64[R_total * K];  cand_count : dev int32[2 * n_levels], zero on entry (as K1).
+ * pod_retinanet_topk  : pod_level_topk (K2's shared radix select and bitonic sort) on those lists; arguments and outputs as pod_level_topk.
+ * pod_retinanet_decode: one thread per row of the level-concatenated selection: anchor = f / K, class = f % K, Box2BoxTransform.apply_deltas
+ *                       (cfg->box_weights, dw / dh clamped at log(1000 / 16)), score = sigmoid of the key's logit.  cand_flat / cand_level /
+ *                       scores / classes : n_levels * topk entries, boxes (n_levels * topk, 4), 16-byte aligned.  cand_count is consumed (zeroed).
+ * pod_nms_cluster     : batched_nms + [:max_detections], unchanged, on (boxes, scores, classes).
+ * pod_retinanet_postprocess: rows keep[0 : n_keep) scaled by (scale_x, scale_y) (fp32 roundings of out / image size), clipped to
+ *                       [0, out_w] x [0, out_h], rows that are empty afterwards (Boxes.nonempty, threshold 0) dropped, compacted in keep order
+ *                       into det_boxes (max_detections, 4) / det_scores / det_classes; n_det dev int32.  Rows >= n_det are not written.
+ * pod_retinanet_infer_image: the five launches enqueued on `stream`; graph-capturable, reads nothing back; the only atomics are the
+ *                       list-append tickets of the scoring pass and K2's.  `workspace`: dev, 16-byte aligned,
+ *                       pod_retinanet_infer_workspace(cfg, levels, NULL) bytes, ZEROED ONCE after allocation (counters, NMS scratch) and
+ *                       then owned by this entry point; `layout` (may be NULL) receives the byte offsets of its parts.
+ * Limits (POD_E_INVALID otherwise): n_runs == 1, K <= POD_MAX_CLASSES - 1, topk <= POD_MAX_TOPK, n_levels * topk <= POD_MAX_CANDIDATES,
+ * max_detections <= POD_MAX_DETECTIONS, A * K * H * W < 2^31 per level. */
+typedef struct PodRetinaNetLayout {   /* byte offsets into the workspace; the arrays as the stage entry points document them */
+    int64_t cand_keys, cand_count, sel_keys, sel_count, cat_keys, cat_level, n_total, cand_flat, cand_level, boxes, scores, classes,
+        keep, n_keep, nms_scratch, total;
+} PodRetinaNetLayout;
+int64_t pod_retinanet_infer_workspace(const PodConfig* cfg, const PodLevel* levels, PodRetinaNetLayout* layout);
+int pod_retinanet_score(const PodConfig* cfg, const PodLevel* levels, uint64_t* cand_keys, int32_t* cand_count, pod_stream_t stream);
+int pod_retinanet_topk(const PodConfig* cfg, const PodLevel* levels, uint64_t* cand_keys, int32_t* cand_count, uint64_t* sel_keys,
+                       int32_t* sel_count, uint64_t* cat_keys, int32_t* cat_level, int32_t* n_total, pod_stream_t stream);
+int pod_retinanet_decode(const PodConfig* cfg, const PodLevel* levels, const float* anchors, const uint64_t* cat_keys,
+                         const int32_t* cat_level, const int32_t* n_total, int32_t* cand_count, int32_t* cand_flat, int32_t* cand_level,
+                         float* boxes, float* scores, int32_t* classes, pod_stream_t stream);
+int pod_retinanet_postprocess(const PodConfig* cfg, const int32_t* keep, const int32_t* n_keep, const float* boxes, const float* scores,
+                              const int32_t* classes, float scale_x, float scale_y, float out_h, float out_w, float* det_boxes,
+                              float* det_scores, int32_t* det_classes, int32_t* n_det, pod_stream_t stream);
+int pod_retinanet_infer_image(const PodConfig* cfg, const PodLevel* levels, const float* anchors, void* workspace, int32_t image_h,
+                              int32_t image_w, int32_t out_h, int32_t out_w, float* det_boxes, float* det_scores, int32_t* det_classes,
+                              int32_t* n_det, pod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,7 +126,8 @@ def get_cfg() -> CfgNode:
                                        "CLS_VAR_LOSS": {"NAME": "none", "NUM_SAMPLES": 3},
                                        "BBOX_COV_LOSS": {"NAME": "none", "COVARIANCE_TYPE": "diagonal", "NUM_SAMPLES": 1000}},
         },
-        "TEST": {"DETECTIONS_PER_IMAGE": 100},
+        # (EVAL_PERIOD, EXPECTED_RESULTS: detectron2's defaults, read by train_head's evaluation -- pod_compare_amd/train_eval.py)
+        "TEST": {"DETECTIONS_PER_IMAGE": 100, "EVAL_PERIOD": 0, "EXPECTED_RESULTS": []},
         # core/setup.py:109-133
         "PROBABILISTIC_INFERENCE": {"INFERENCE_MODE": "standard_nms", "AFFINITY_THRESHOLD": 0.7,
                                     "MC_DROPOUT": {"ENABLE": False, "NUM_RUNS": 1},

@@ -54,13 +54,15 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_reg_score_partials", "pod_reg_score_loss", "pod_full_cov_partials", "pod_full_cov_loss",
            "pod_sgd_solver_workspace_bytes", "pod_sgd_step_solver", "pod_sgd_solver_reset",
            "pod_stem7x7_wgrad_partials", "pod_stem7x7_wgrad", "pod_maxpool3x3s2_backward_cl",
-           "pod_train_batch_tiles", "pod_train_batch_u8")
+           "pod_train_batch_tiles", "pod_train_batch_u8",
+           "pod_retinanet_infer_workspace", "pod_retinanet_score", "pod_retinanet_topk", "pod_retinanet_decode", "pod_retinanet_postprocess",
+           "pod_retinanet_infer_image")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
                  "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes",
-                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles")
+                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles", "pod_retinanet_infer_workspace")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -157,6 +159,12 @@ class PodTrainFrame(Structure):
                 ("xbounds", c_void_p), ("xcoeffs", c_void_p), ("xk", c_int32), ("reserved0", c_int32),
                 ("ybounds", c_void_p), ("ycoeffs", c_void_p), ("yk", c_int32), ("reserved1", c_int32),
                 ("dst", c_void_p), ("out_h", c_int32), ("out_w", c_int32), ("flip_channels", c_int32), ("hflip", c_int32), ("first_tile", c_int64)]
+
+
+class PodRetinaNetLayout(Structure):
+    """include/pod_mi355x.h: PodRetinaNetLayout (K32, byte offsets into pod_retinanet_infer_image's workspace)."""
+    _fields_ = [(n, c_int64) for n in ("cand_keys", "cand_count", "sel_keys", "sel_count", "cat_keys", "cat_level", "n_total", "cand_flat", "cand_level",
+                                       "boxes", "scores", "classes", "keep", "n_keep", "nms_scratch", "total")]
 
 
 class PodError(RuntimeError):
@@ -303,6 +311,13 @@ def load() -> ctypes.CDLL:
     lib.pod_train_batch_tiles.argtypes = [POINTER(PodTrainFrame), c_int32]
     lib.pod_train_batch_tiles.restype = c_int64
     lib.pod_train_batch_u8.argtypes = [POINTER(PodTrainFrame), P, c_int32, c_int64, P]
+    lib.pod_retinanet_infer_workspace.argtypes = [POINTER(PodConfig), POINTER(PodLevel), POINTER(PodRetinaNetLayout)]
+    lib.pod_retinanet_infer_workspace.restype = c_int64
+    lib.pod_retinanet_score.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, P]
+    lib.pod_retinanet_topk.argtypes = lib.pod_level_topk.argtypes
+    lib.pod_retinanet_decode.argtypes = [POINTER(PodConfig), POINTER(PodLevel)] + [P] * 11
+    lib.pod_retinanet_postprocess.argtypes = [POINTER(PodConfig)] + [P] * 5 + [c_float] * 4 + [P] * 5
+    lib.pod_retinanet_infer_image.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, c_int32, c_int32, c_int32, c_int32, P, P, P, P, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -22,6 +22,9 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
     train_batch_u8
                  a training batch's network inputs in one launch (K31): decoded (h, w, 3) uint8 frames -> per frame the (3, nh, nw) uint8
                  tensor PIL's bilinear resize at sizes[2 i], sizes[2 i + 1], the flip where hflips[i], BGR and the transpose give
+    retinanet_inference
+                 detectron2's RetinaNet.inference + detector_postprocess for one image (K32; what the reference model runs in eval mode,
+                 PR:156-166): the eval-mode head output, per level (1, A*K, H, W) / (1, A*4, H, W) -> boxes, scores, classes
 """
 from typing import List, Tuple
 
@@ -47,6 +50,9 @@ _LIB.define("stem7x7_split(Tensor frame, Tensor Ws, Tensor? bias, Tensor? mean, 
 _LIB.define("maxpool3x3s2_cl(Tensor x, int h, int w) -> Tensor")
 _LIB.define("im2col3x3s2_cl(Tensor x, int h, int w, bool relu=False) -> Tensor")
 _LIB.define("train_batch_u8(Tensor[] frames, int[] sizes, bool[] hflips, bool bgr=True) -> Tensor[]")
+_LIB.define("retinanet_inference(Tensor[] box_cls, Tensor[] box_delta, Tensor[] anchors, int[] image_size, int[] out_size, int num_classes=7, "
+            "int topk_candidates=1000, float score_thresh=0.05, float nms_thresh=0.5, int max_detections=100, "
+            "float[] box_weights=[1.0, 1.0, 1.0, 1.0]) -> (Tensor, Tensor, Tensor)")
 
 _PATHS = {}            # key -> [HotPath, anchor identity, the anchor tensors]; insertion order = LRU order
 _MAX_PATHS = 16
@@ -299,7 +305,42 @@ def _train_batch_u8(frames, sizes, hflips, bgr=True) -> List[torch.Tensor]:
     return train_batch.train_batch_u8(list(frames), pairs, [bool(v) for v in hflips], bgr=bool(bgr))
 
 
+def _retinanet_inference(box_cls, box_delta, anchors, image_size, out_size, num_classes=7, topk_candidates=1000, score_thresh=0.05,
+                         nms_thresh=0.5, max_detections=100, box_weights=(1.0, 1.0, 1.0, 1.0)) -> Tuple[torch.Tensor, ...]:
+    from . import retinanet_inference as ri
+    torch._check(len(box_cls) >= 1, lambda: "box_cls: at least one FPN level")
+    _check_dense("box_cls", box_cls, box_cls)
+    _check_dense("box_delta", box_delta, box_cls)
+    torch._check(box_cls[0].shape[0] == 1, lambda: "retinanet_inference takes one run (the eval-mode head output)")
+    torch._check(len(anchors) == len(box_cls) and len(image_size) == 2 and len(out_size) == 2 and len(box_weights) == 4,
+                 lambda: "anchors per level; (h, w) sizes; four box weights")
+    K = int(num_classes)
+    torch._check(box_cls[0].shape[1] % K == 0, lambda: "box_cls channels {} are not A * num_classes".format(box_cls[0].shape[1]))
+    A = box_cls[0].shape[1] // K
+    dev = box_cls[0].device
+    shapes = tuple(tuple(t.shape[2:]) for t in box_cls)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    key = ("retinanet_inference", shapes, A, K, str(dev), stream, topk_candidates, score_thresh, nms_thresh, max_detections, tuple(box_weights))
+    akey = tuple((a.data_ptr(), a._version, tuple(a.shape)) for a in anchors)
+    entry = _PATHS.pop(key, None)
+    with torch.cuda.device(dev):
+        if entry is None:      # one workspace per (geometry, stream); the anchors are handled as predict handles them
+            p = ri.InferenceParams(num_classes=K, num_anchors=A, topk_candidates=topk_candidates, score_thresh=score_thresh, nms_thresh=nms_thresh,
+                                   max_detections=max_detections, box_weights=tuple(float(v) for v in box_weights))
+            entry = [ri.RetinaNetInference(shapes, anchors, p, device=dev), akey, list(anchors)]
+        elif entry[1] != akey:
+            entry[0].set_anchors(anchors)
+            entry[1], entry[2] = akey, list(anchors)
+        _PATHS[key] = entry
+        while len(_PATHS) > _MAX_PATHS:
+            _PATHS.pop(next(iter(_PATHS)))
+        det = entry[0].infer_image((list(box_cls), list(box_delta)), tuple(image_size), tuple(out_size))
+    boxes, scores, classes, _ = det.trimmed()      # the one host sync of an image (exact-size tensors, like the reference's Instances)
+    return boxes, scores, classes
+
+
 _IMPL = torch.library.Library("pod_mi355x", "IMPL")
+_IMPL.impl("retinanet_inference", _retinanet_inference, "CUDA")
 _IMPL.impl("train_batch_u8", _train_batch_u8, "CUDA")
 _IMPL.impl("im2col3x3s2_cl", _im2col3x3s2_cl, "CUDA")
 _IMPL.impl("conv1x1_filter_split", _conv1x1_filter_split, "CUDA")

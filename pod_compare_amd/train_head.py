@@ -4,6 +4,7 @@
         --config-file <model.yaml> [--weights <checkpoint>] [--max-iter N] [--log-period N] [--train-fpn | --train-backbone]
         [--fused-step] [--guard-nonfinite] [--random-flip] [--resume] [--data-parallel [--backend nccl|gloo] [--share-gpu]]
         [--train-loader [--no-shuffle] [--batch-on-gpu]]
+        [--val-coco-json <val.json> --val-image-root <dir> [--eval-only]]
 
 The head's part of train_net.py's loop: per step SOLVER.IMS_PER_BATCH frames of ONE resized shape (the sampler batches frames of equal
 shape together; a shape's frames wait until a batch of them is complete -- with --train-loader, below, frames of one aspect-ratio
@@ -78,6 +79,19 @@ slice of the one-rank run's global batches.  --batch-on-gpu: the threads only de
 resizes, mirrors, flips to BGR and transposes the rank's frames; the bytes are the host path's.  The checkpoint's sampler state is then
 the plan's (kind `train_loader`: the permutation generator at the start of the pass, the draw generator, the position, the waiting
 entries with their draws); --resume across the two kinds of data order is refused.  Without the flag nothing of this is imported.
+
+--val-coco-json / --val-image-root: the other two places train_net.py customises DefaultTrainer in, the test loader and the evaluator
+(pod_compare_amd/train_eval.py).  The validation set -- not the training json -- is evaluated after every iteration `it` with
+(it + 1) % TEST.EVAL_PERIOD == 0 (detectron2's EvalHook; 0, the default: never) and always after the last iteration: every image in file
+order at INPUT.MIN_SIZE_TEST / MAX_SIZE_TEST, the trainer's own model object in eval mode (dropout the identity, the filters the step just
+refolded), detectron2's RetinaNet.inference + detector_postprocess on the device (K32, pod_compare_amd/retinanet_inference.py: what the
+reference model runs in eval mode, PR:156-166), OUTPUT_DIR/inference/coco_instances_results.json as COCOEvaluator writes it, bbox AP from
+the K17 kernels, detectron2's `copypaste:` lines and, on a log step, an AP line behind the loss line.  After the last evaluation
+TEST.EXPECTED_RESULTS is checked as detectron2's verify_results checks it.  Evaluation touches nothing a run's determinism rests on: the
+checkpoints of a run with evaluation are those of the run without, to the bit.  TEST.EVAL_PERIOD > 0 without --val-coco-json is refused
+before a model is built.  --eval-only: load MODEL.WEIGHTS (--weights), or OUTPUT_DIR/last_checkpoint with --resume, evaluate once, print
+and return the results; no optimiser is built and --coco-json is not read.  Under --data-parallel every rank evaluates its share of the
+images (apply_net.shard_indices), the records are gathered, rank 0 writes and scores; the file's bytes do not depend on the world size.
 
 Still NOT the reference's full trainer: the all-reduce does not overlap the backward pass, and without --train-loader a data-parallel
 rank reads its frames without read-ahead.  The loss line is the only host read-back, on log steps only (and a checkpoint's copies); under settings that
@@ -674,6 +688,11 @@ def arg_parser():
                                                                 "flips to BGR and transposes the batch's frames; bit-identical to the host path")
     ap.add_argument("--resume", action="store_true", help="continue the run OUTPUT_DIR/last_checkpoint stopped in: its weights and its trainer state "
                                                           "(iteration, loss state, momentum, data position); refused if the file carries none")
+    ap.add_argument("--val-coco-json", default="", help="COCO-format validation set (not the training json): evaluated every TEST.EVAL_PERIOD "
+                                                        "iterations and after the last one, as detectron2's EvalHook does (train_eval.py, K32)")
+    ap.add_argument("--val-image-root", default="", help="directory of the files named in --val-coco-json")
+    ap.add_argument("--eval-only", action="store_true", help="train_net.py's flag: load MODEL.WEIGHTS (or OUTPUT_DIR/last_checkpoint with --resume), "
+                                                             "evaluate --val-coco-json once, print and return the results; builds no optimiser")
     ap.add_argument("--data-parallel", action="store_true", help="one rank of a data-parallel run (RANK / WORLD_SIZE / LOCAL_RANK, as torch.distributed.run "
                                                                  "sets them): the rank takes its share of every batch of SOLVER.IMS_PER_BATCH frames, the "
                                                                  "gradients are averaged over the ranks through one bucket (K26) and one all-reduce; implies "
@@ -744,6 +763,9 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         raise SystemExit("MODEL.BACKBONE.FREEZE_AT = {} needs --train-backbone: without it the ResNet stays frozen, which is what FREEZE_AT = 2 "
                          "(or no key) says".format(freeze_at))
     solver = solver_settings(cfg, guard_nonfinite=args.guard_nonfinite)      # (SystemExit for a key this trainer does not run, before a model is built)
+    eval_period = evaluation_period(cfg, args)                               # (and for an evaluation that has no validation set)
+    if args.eval_only:
+        return _eval_only(args, cfg, rank, world, group, say)
     train_fpn = args.train_fpn or args.train_backbone
     # --resume: the file last_checkpoint names, if there is one (none: the run starts as without the flag, as detectron2's resume_or_load)
     resume_from = checkpoint.resolve_checkpoint(cfg.OUTPUT_DIR, "") if args.resume else ""
@@ -861,7 +883,16 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         folded = [c.weight for c in trainer.masters.convs] if trainer.masters is not None else []
         broadcast_tensors(trainer.params + folded + trainer.fused.buffers, group)
     written, last_line, stalled = [], None, 0
-    extra = {}
+    extra, evaluations = {}, []
+
+    def evaluate(it: int):
+        """Trainer.test on the validation set with the model as it stands after iteration `it`; every rank takes part, rank 0 reports."""
+        from . import train_eval
+        res = train_eval.evaluate_model(model, cfg, args.val_coco_json, args.val_image_root, cfg.OUTPUT_DIR, args.train_dataset, args.test_dataset,
+                                        workers=workers, rank=rank, world=world, group=group, say=say)
+        say(train_eval.ap_line(it, res), flush=True)
+        evaluations.append((it, res))
+        return res
 
     def after_step(res):
         """The log line and the periodic checkpoint behind a step."""
@@ -875,6 +906,8 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
             if norm is not None:
                 last_line += "  grad_norm %.6g" % norm
             say(last_line, flush=True)
+        if eval_period > 0 and it % eval_period == 0 and it != max_iter:          # EvalHook.after_step; the last iteration's follows the loop
+            evaluate(it)
         if period > 0 and it % period == 0 and it < max_iter:
             write("model_%07d" % (it - 1), it)
 
@@ -903,6 +936,12 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         stalled = 0 if progressed else stalled + 1      # (an incomplete batch carries over into the next pass over the data set)
         if stalled >= batch:
             raise SystemExit("no batch of {} frames of one resized shape can be formed from {} frames".format(batch, len(dataset)))
+    if args.val_coco_json:                 # EvalHook.after_train, then DefaultTrainer.train's verify_results
+        from . import train_eval
+        extra["eval_results"] = evaluate(trainer.iteration)
+        extra["evaluations"] = evaluations
+        if rank == 0:
+            train_eval.verify_results(cfg, extra["eval_results"], say)
     write("model_final", trainer.iteration)
     if world > 1:
         import torch.distributed as dist
@@ -912,6 +951,44 @@ def _run(args, rank: int, world: int, group, bind: bool = False):
         print("trained the head%s for %d iterations; wrote %s" % (what, trainer.iteration, written[-1]))
     return dict({"iterations": trainer.iteration, "checkpoints": written, "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": last_line,
                  "trainer": trainer}, **extra)
+
+
+def evaluation_period(cfg, args) -> int:
+    """TEST.EVAL_PERIOD, checked against the flags before a model is built: SystemExit naming the key or the flag for an evaluation that
+    has no validation set to run on."""
+    period = cfg.TEST.get("EVAL_PERIOD", 0)
+    if isinstance(period, bool) or not isinstance(period, int) or period < 0:
+        raise SystemExit("TEST.EVAL_PERIOD = {!r} is not supported: a non-negative number of iterations (0: no periodic evaluation)".format(period))
+    if period > 0 and not args.val_coco_json:
+        raise SystemExit("TEST.EVAL_PERIOD = {} needs --val-coco-json and --val-image-root: the validation set is not the training json".format(period))
+    if args.eval_only and not args.val_coco_json:
+        raise SystemExit("--eval-only needs --val-coco-json and --val-image-root: the set to evaluate")
+    if args.val_coco_json and not args.val_image_root:
+        raise SystemExit("--val-coco-json needs --val-image-root: the directory of the files it names")
+    return int(period)
+
+
+def _eval_only(args, cfg, rank: int, world: int, group, say) -> dict:
+    """train_net.py:67-76: build the model, resume_or_load(MODEL.WEIGHTS, resume=--resume), Trainer.test, verify_results.  No optimiser,
+    no loss state, no training json."""
+    from . import train_eval
+    dev = torch.device(args.device)
+    torch.cuda.set_device(dev)
+    found = checkpoint.resolve_checkpoint(cfg.OUTPUT_DIR, "") if args.resume else ""
+    torch.manual_seed(args.random_seed)
+    # (--random-init evaluates the seeded initialisation unless a checkpoint is named: --weights, or last_checkpoint under --resume)
+    model = build_model(cfg, save_dir="" if args.resume else None, load_weights=not args.random_init or bool(found) or args.weights is not None)
+    say("evaluating %s" % (model.loaded_from or "the seeded random initialisation"), flush=True)
+    workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
+    res = train_eval.evaluate_model(model, cfg, args.val_coco_json, args.val_image_root, cfg.OUTPUT_DIR, args.train_dataset, args.test_dataset,
+                                    workers=workers, rank=rank, world=world, group=group, say=say)
+    say(train_eval.ap_line(0, res), flush=True)
+    if rank == 0:
+        train_eval.verify_results(cfg, res, say)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier(group)
+    return {"iterations": 0, "checkpoints": [], "output_dir": cfg.OUTPUT_DIR, "model": model, "last_line": None, "eval_results": res}
 
 
 def _train_on_plan(args, plan, dataset, trainer, by_image, cat_map, dev, workers, first, last, max_iter, after_step) -> dict:
