@@ -82,8 +82,17 @@ class Golden:
 
 # What the parity bar actually uses: every assert_close call records the worst absolute error and the worst error in units of its
 # bound, per (test, quantity); tests/conftest.py writes them out at the end of a GPU session (gpurun_out/parity_errors.{json,md};
-# the committed copy is profiles/r04_parity_errors.md).
+# the fp64 referee's rows in parity_errors_fp64.json beside them).  What the bar itself rests on -- how far the fp32 reference and the HIP path each are from an fp64 evaluation of the same
+# arithmetic -- is measured by tests/fp64_referee and committed as profiles/fp64_referee.md.
 PARITY_LOG = {}
+REFEREE_LOG = {}      # (test, quantity) -> figures of fp64_referee's acceptance rule (e_hip, e_ref, their ratios)
+
+
+def record_referee(what, fig):
+    """One row of the fp64 referee's rule (tests/fp64_referee/f64_ref.py: within_rule): the HIP side's and the fp32 oracle's normalised
+    errors against fp64 over the same entries (tests/fp64_referee/gpu_common.py: hold also feeds both sides to _record)."""
+    test = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" (")[0]
+    REFEREE_LOG[(test, what)] = dict(fig)
 
 
 def _record(what, err, bound, b):
@@ -105,9 +114,9 @@ def _record(what, err, bound, b):
 
 def assert_close(a, b, what="", rtol=RTOL, atol=ATOL, matrix_scale=False):
     """|a - b| <= max(atol, rtol |b|) element-wise.  With the defaults that is `north_star`'s "within 1e-4 on box means / covariances"
-    read RELATIVE TO max(1, |ref|): the quantities are fp32 moments of 1000 samples of coordinates up to ~1 300 px (and covariances up
-    to ~1e4 px^2) -- an absolute 1e-4 on a 1 300-px coordinate is below the spacing of fp32 numbers there (1.2e-4), so no fp32
-    computation, the reference's own on another BLAS included, could meet it.  How much of the bar is used: profiles/r04_parity_errors.md."""
+    read RELATIVE TO max(1, |ref|).  What that bar is worth is measured, not argued: profiles/fp64_referee.md holds the error of the
+    fp32 reference itself, and of the HIP path, against an fp64 evaluation of the same arithmetic (tests/fp64_referee).  Box means: the
+    reference is within 0.22 of this bar on every fixture.  Covariances: see `matrix_scale`."""
     a = torch.as_tensor(a).double()
     b = torch.as_tensor(b).double()
     assert a.shape == b.shape, "{}: shape {} vs {}".format(what, tuple(a.shape), tuple(b.shape))
@@ -116,11 +125,11 @@ def assert_close(a, b, what="", rtol=RTOL, atol=ATOL, matrix_scale=False):
     err = (a - b).abs()
     bound = torch.clamp(rtol * b.abs(), min=atol)      # defaults: 1e-4 * max(1, |b|), the bar DESIGN.md and smoke() state
     if matrix_scale and b.dim() >= 2:
-        # COVARIANCE MATRICES (round 6, found by the full-size index tests): an entry is (a difference of) sums of 1000 fp32 products of the
-        # size of the matrix's variances, so its rounding noise scales with the LARGEST entry of its matrix, not with itself -- a p7 anchor's
-        # box has variances of ~1 500 px^2 and correlations near 0: an off-diagonal entry of 0.3 carries 2e-4 of summation-order noise (1e-7
-        # of the variances; the reference's own sgemm on another BLAS differs by as much).  Bound = rtol * max(1, max |ref matrix|); the
-        # element-wise fraction is still recorded (parity_errors.md: `cov ... elementwise`).
+        # COVARIANCE MATRICES at full size: per MATRIX, rtol * max(1, max |ref matrix|).  Measured (profiles/fp64_referee.md, CPU section):
+        # against fp64 the fp32 reference ITSELF is up to 7.3x over the element-wise bar on the full-size candidate covariances (an
+        # off-diagonal entry near 0 of a matrix whose variances are ~1e3 px^2) and never above 0.6 of the per-matrix bar; the HIP path is
+        # held to no more than 2x the reference's own distance from fp64 by tests/fp64_referee.  The element-wise fraction is still
+        # recorded (parity_errors.md: `cov ... elementwise`).
         _record(what + " (elementwise reading)", err, bound, b)
         scale = b.abs().amax(dim=(-2, -1), keepdim=True).clamp(min=1.0)
         bound = torch.maximum(bound, (rtol * scale).expand_as(bound))
@@ -150,3 +159,17 @@ def write_parity_report(directory):
         f.write("| quantity | tests | elements | worst abs. error | worst error / max(1, abs ref) | worst fraction of its bound | in |\n|---|---|---|---|---|---|---|\n")
         for k, q in sorted(by_q.items()):
             f.write("| %s | %d | %d | %.3e | %.3e | %.3f | `%s` |\n" % (k, q["tests"], q["n"], q["max_abs"], q["max_rel"], q["frac"], q["where"]))
+        if REFEREE_LOG:
+            f.write("\n" + referee_table())
+    if REFEREE_LOG:
+        with open(os.path.join(directory, "parity_errors_fp64.json"), "w") as f:
+            json.dump([dict(test=t, quantity=w, **r) for (t, w), r in sorted(REFEREE_LOG.items())], f, indent=1)
+
+
+def referee_table():
+    """The GPU section of profiles/fp64_referee.md: per (test, quantity) e_hip, e_ref (normalised errors against fp64) and their ratios."""
+    out = ["| test | quantity | entries | e_hip max | e_ref max | ratio | e_hip rms | e_ref rms | ratio | worst entry |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for (t, w), r in sorted(REFEREE_LOG.items()):
+        out.append("| `%s` | %s | %d | %.2e | %.2e | %.2f | %.2e | %.2e | %.2f | %d |" % (
+            t.split("::", 1)[-1], w, r["n"], r["hip_max"], r["ref_max"], r["ratio_max"], r["hip_rms"], r["ref_rms"], r["ratio_rms"], r["at"]))
+    return "\n".join(out) + "\n"

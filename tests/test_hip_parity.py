@@ -67,7 +67,7 @@ def test_hip_matches_reference_golden(path):
     assert_close(det.scores[:m].cpu(), g.t("scores"), "scores", rtol=2e-6, atol=1e-7)
     assert_close(det.probs[:m].cpu(), g.t("pred_cls_probs"), "probs", rtol=2e-6, atol=1e-7)
     assert_close(det.boxes[:m].cpu(), ref_boxes, "boxes")
-    assert_close(det.cov[:m].cpu(), g.t("pred_boxes_covariance"), "cov", matrix_scale="/full_" in path)
+    assert_close(det.cov[:m].cpu(), g.t("pred_boxes_covariance"), "cov")      # element-wise at full size too (profiles/fp64_referee.md)
 
 
 @pytest.mark.parametrize("path", PRE_NMS, ids=fixture_id)
@@ -94,7 +94,8 @@ def test_hip_indices_bit_exact(path):
     assert int(same.sum()) >= n - 16
     assert_close(hp.boxes[:n].cpu()[same], g.t("aw0_boxes")[same], "candidate boxes")
     if g.t("aw0_cov").numel():
-        # (full size: per MATRIX -- tests/helpers.py; the small frames keep the element-wise bar they have always met)
+        # (full size: per MATRIX -- against fp64 the fp32 reference itself is up to 7.3x over the element-wise bar on these candidate
+        # covariances, profiles/fp64_referee.md; the small frames keep the element-wise bar they have always met)
         assert_close(hp.cov[:n].cpu()[same], g.t("aw0_cov")[same], "candidate cov", matrix_scale="/full_" in path)
     nk = int(hp.n_keep.item())
     ref_keep = inv[g.t("nms_keep_0")[:100]]
