@@ -127,12 +127,16 @@ def test_sparse_tower_gives_the_dense_towers_detections(dropout, runs, cov):
     sp = m(frame, sparse_bbox=hook, **kw)
     for a, b in zip(sp.cls + sp.cls_var, dense.cls + dense.cls_var):
         # the cls side is the dense one (MIOpen's p6 / p7 kernels accumulate with atomics: two forwards agree to rounding, not bit for bit)
-        assert float((a - b).abs().max()) <= 2e-4 * max(1.0, float(b.abs().max()))
+        err = float((a - b).abs().max()) / max(1.0, float(b.abs().max()))
+        print("sparse vs dense, cls side: %.3e of scale" % err)
+        assert err <= 1e-4           # the project's bar (was 2e-4; measured: profiles/sparse_reference.md)
     got = hp.finish("bayes_od", cls, sp.delta, cls_var, sp.reg_var, (256, 384), (256, 384))
     assert int(hp.n_total.item()) == n and n > 20
     assert torch.equal(hp.cand_anchor_idx[:n], ref[2])
     for name, a, b in (("delta", hp.cand_delta[:n], ref[0]), ("reg_var", hp.cand_reg_var[:n], ref[1])):
-        assert float((a - b).abs().max()) <= 2e-4 * max(1.0, float(b.abs().max())), name
+        err = float((a - b).abs().max()) / max(1.0, float(b.abs().max()))
+        print("sparse vs dense, %s at the candidates: %.3e of scale" % (name, err))
+        assert err <= 1e-4, name     # the project's bar (was 2e-4; measured: profiles/sparse_reference.md)
     assert float((hp.boxes[:n] - ref[3]).abs().max()) <= 1e-4 * max(1.0, float(ref[3].abs().max()))
     k = got.count()
     assert k == want.count() and k > 0
