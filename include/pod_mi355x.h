@@ -1136,6 +1136,31 @@ int pod_run_image(const PodConfig* cfg, const PodLevel* levels, const PodWorkspa
 int pod_run_image_part(const PodConfig* cfg, const PodLevel* levels, const PodWorkspace* ws, int32_t mode,
                   int32_t box_merge_mode, int32_t cls_merge_mode, int32_t image_h, int32_t image_w,
                   int32_t out_h, int32_t out_w, const PodDetections* out, int32_t parts, pod_stream_t stream);
+/* FINISH is itself two parts, for several inference configs on one image: 4 CANDIDATES (gather + decode + NMS: what no mode changes; `out`
+ * may be NULL), 8 TAIL (the mode's fusion launch, none for standard NMS, + pod_finalize: reads the candidate arrays and the keep list
+ * CANDIDATES left and leaves them as they were; writes ws->m_* and `out`), 5 FRONT = SELECT + CANDIDATES.  2 = 4 then 8.  Values 1, 2 and 3
+ * are what they were. */
+#define POD_PART_SELECT 1
+#define POD_PART_FINISH 2
+#define POD_PART_CANDIDATES 4
+#define POD_PART_FRONT 5
+#define POD_PART_TAIL 8
+
+/* Several inference configs of one image on one front (the comparison pass, DESIGN.md "Comparison pass"): the front -- pod_merge_score_fused
+ * -> pod_level_topk -> pod_gather_decode -> pod_nms_cluster -- is enqueued ONCE, then per tail, in order, that mode's fusion launch and
+ * pod_finalize into the tail's own PodDetections.  tails[t].out holds what pod_run_image(mode, box_merge_mode, cls_merge_mode) on the same
+ * inputs and cfg->philox_seed writes, bit for bit.  ws->m_* is scratch the tails share: stream order serialises them.  Nothing synchronises
+ * or allocates; graph-capturable as pod_run_image is.  POD_E_INVALID, with nothing enqueued: n_tails < 1 or > POD_MAX_MODE_TAILS, an unknown
+ * mode, a POD_MODE_BAYES_OD tail without covariances (cfg->cov_dims == 0 and cfg->n_runs == 1) or with a merge mode pod_bayes_fuse refuses,
+ * a NULL output, and whatever pod_run_image refuses.  One new symbol, one new structure and six constants under POD_ABI_VERSION 18: no
+ * entry or structure that existed changed, so the number stands. */
+#define POD_MAX_MODE_TAILS 8
+typedef struct PodModeTail {
+    int32_t mode, box_merge_mode, cls_merge_mode, reserved;
+    PodDetections out;
+} PodModeTail;
+int pod_run_image_modes(const PodConfig* cfg, const PodLevel* levels, const PodWorkspace* ws, const PodModeTail* tails, int32_t n_tails,
+                        int32_t image_h, int32_t image_w, int32_t out_h, int32_t out_w, pod_stream_t stream);
 
 /* ---- K32  retinanet_inference (csrc/k32_retinanet_inference.hip) ----------------------------------------------------------------
  * Replaces: what the reference model runs in EVAL mode (PR:156-166: `self.inference(...)`, then `detector_postprocess`), i.e. detectron2's

@@ -337,14 +337,229 @@ def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train
     return {"ap": ap, "pm": pm, "ce": ce, "min_allowed_score": thr, "map_results": map_path}
 
 
+def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str) -> str:
+    """AN:44-48: `<OUTPUT_DIR>/inference/<test data set>/<name of the inference YAML>`, the directory the reference's apply_net writes a
+    config's coco_instances_results.json to and its evaluators read it from."""
+    return os.path.join(output_dir, "inference", test_dataset, os.path.split(inference_config)[-1][:-5])
+
+
+COMPARISON_COLUMNS = (      # (heading, evaluator, path into the dictionary evaluate_results returns for it, format)
+    ("AP", "ap", ("stats", 0), "%.3f"), ("AP50", "ap", ("stats", 1), "%.3f"), ("AP75", "ap", ("stats", 2), "%.3f"),
+    ("TP Cls NLL", "pm", ("average", "true_positives_cls_analysis", "ignorance_score_mean"), "%.4f"),
+    ("TP Reg NLL", "pm", ("average", "true_positives_reg_analysis", "ignorance_score_mean"), "%.4f"),
+    ("FP Cls NLL", "pm", ("average", "false_positives_cls_analysis", "ignorance_score_mean"), "%.4f"),
+    ("FP Reg Entropy", "pm", ("average", "false_positives_reg_analysis", "total_entropy_mean"), "%.4f"),
+    ("Cls MCE", "ce", ("cls_marginal_calibration_error",), "%.4f"), ("Reg ECE", "ce", ("reg_expected_calibration_error",), "%.4f"),
+    ("Reg MaxCE", "ce", ("reg_maximum_calibration_error",), "%.4f"), ("Cls MUE", "ce", ("cls_minimum_uncertainty_error",), "%.4f"),
+    ("Reg MUE", "ce", ("reg_minimum_uncertainty_error",), "%.4f"))
+
+
+def format_comparison_table(names: Sequence[str], results: Sequence[dict]) -> str:
+    """One row per inference config, in order, from the dictionaries `evaluate_results` returned: AP / AP50 / AP75 (COCO's first three
+    numbers), the four score columns of the PM table and the five of the CE table.  No number is computed here; one that an evaluator
+    left undefined (no true positives, say) prints as "-"."""
+    def cell(res, which, path, fmt):
+        v = res[which]
+        for k in path:
+            v = v[k]
+        return "-" if v is None else fmt % float(v)
+
+    rows = [("Inference Config",) + tuple(c[0] for c in COMPARISON_COLUMNS)]
+    rows += [(n,) + tuple(cell(r, *c[1:]) for c in COMPARISON_COLUMNS) for n, r in zip(names, results)]
+    w = [max(len(r[i]) for r in rows) for i in range(len(rows[0]))]
+    line = "+" + "+".join("-" * (x + 2) for x in w) + "+"
+    body = ["| " + r[0].ljust(w[0]) + " | " + " | ".join(r[i].center(w[i]) for i in range(1, len(r))) + " |" for r in rows]
+    return "\n".join([line, body[0], line] + body[1:] + [line])
+
+
+def _start_rank(args, world: int, rank: int, local_rank: int) -> None:
+    """This rank's process group, device and NUMA binding: the same for one inference config and for several."""
+    if world > 1:
+        if args.backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group(args.backend)
+    torch.cuda.set_device(local_rank)
+    if world > 1:                 # enqueue + loader threads of this rank on its GPU's NUMA node (hostbind.py; POD_BIND_NUMA=0: off)
+        from . import hostbind
+        b = hostbind.bind_rank_to_gpu_numa(local_rank)
+        print("rank %d: cuda:%d pci %s numa node %s -> %s" % (rank, local_rank, b["pci"], b["numa_node"], b["cpus"] if b["bound"] else "not bound (%s)" % b.get("why_not", "off")))
+
+
+def _network_input(args, cfg, d: Optional[dict], i: int, dev):
+    """Image i as the predictor takes it, enqueued on the current stream: (input_im, the synthetic frame or None).  d: the loader's entry
+    of a --coco-json run -- resized on the host exactly as detectron2's mapper does, or, with --resize-on-gpu, the decoded frame, which
+    goes up and comes out as the host path's bytes (K20), outside any captured graph.  image_id is the position in the list: the data
+    set's id is restored by _image_order."""
+    from . import modeling, resize, synthetic
+    if d is not None:
+        if args.resize_on_gpu:
+            image = resize.resize_frame_u8(d["frame"].to(dev, non_blocking=True), cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+        else:
+            image = d["image"].to(dev, non_blocking=True)
+        return [{"image": image, "height": d["height"], "width": d["width"], "image_id": i}], None
+    frame = synthetic.synthetic_frame(i, device=dev)
+    image = modeling.resize_test_image(frame, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    return [{"image": image, "height": frame.shape[1], "width": frame.shape[2], "image_id": i}], frame
+
+
+def _image_order(ids: List[int], all_cnt: list, all_rec: list, width: int, dataset):
+    """The flushed chunks of one config as (ids, counts, records) in image order, the ids the data set's own."""
+    order = sorted(range(len(ids)), key=lambda q: ids[q])
+    ids = [ids[q] for q in order]
+    cnt = torch.cat(all_cnt)[order] if all_cnt else torch.zeros((0,), dtype=torch.int32)
+    rec = torch.cat(all_rec)[order] if all_rec else torch.zeros((0, 128, width))
+    if dataset is not None:
+        ids = [dataset.image_id(i) for i in ids]
+    return ids, cnt, rec
+
+
+def _main_comparison(args, paths: List[str]):
+    """`main` for several --inference-config paths: the sharded loop with a `probabilistic_inference.build_comparison` in the predictor's
+    place -- one decode, one model evaluation per family of configs, one front per sub-family -- every config's files written where its own
+    run under the reference's directory layout writes them."""
+    from . import modeling
+    from .config import setup_config
+    from .probabilistic_inference import build_comparison
+    for flag, given in (("--output", args.output is not None), ("--vis-dir", bool(args.vis_dir)), ("--ensemble-per-gpu", args.ensemble_per_gpu)):
+        if given:
+            raise SystemExit("%s names one run's output: it cannot be combined with several --inference-config paths (every config writes "
+                             "coco_instances_results.json to <OUTPUT_DIR>/inference/<test data set>/<its name>/)" % flag)
+    if args.binary_output and os.path.dirname(args.binary_output):
+        raise SystemExit("--binary-output with several --inference-config paths is a file NAME, written into every config's directory")
+    names = [os.path.split(p)[-1][:-5] for p in paths]
+    if len(set(names)) != len(names):
+        raise SystemExit("--inference-config: two paths share the name %s, so they share an output directory" % sorted(n for n in names if names.count(n) > 1)[0])
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
+    evaluating = args.eval or args.eval_only
+    if evaluating and not has_ground_truth(args.coco_json):
+        raise SystemExit("--eval / --eval-only need ground truth: --coco-json with `annotations`")
+    cfgs = [setup_config(args.config_file, p, args.random_seed, data_dir=args.data_dir, is_testing=bool(args.data_dir)) for p in paths]
+    dirs = [inference_output_dir(cfgs[0].OUTPUT_DIR, args.test_dataset, p) for p in paths]
+    outputs = [os.path.join(d, "coco_instances_results.json") for d in dirs]
+    sidecars = [os.path.join(d, args.binary_output) if args.binary_output else "" for d in dirs]
+
+    def evaluate_all(device):
+        res = []
+        for name, out, side in zip(names, outputs, sidecars):
+            print("== %s" % name)
+            binary = args.eval_only and bool(side)        # as one config's --eval-only: the sidecar when it is named
+            res.append(evaluate_results(side if binary else out, args.coco_json, args.train_dataset, args.test_dataset, binary=binary,
+                                        min_allowed_score=args.min_allowed_score, map_results=args.map_results, device=device, seed=args.random_seed))
+        table = format_comparison_table(names, res)
+        with open(os.path.join(dirs[0], "comparison.txt"), "w") as f:
+            f.write(table + "\n")
+        print(table)
+        return res
+
+    if args.eval_only:
+        return evaluate_all("cuda:%d" % local_rank) if rank == 0 else None
+    _start_rank(args, world, rank, local_rank)
+    for cfg in cfgs:
+        if args.weights is not None:
+            cfg.MODEL.WEIGHTS = args.weights
+        if args.random_init:
+            cfg.MODEL.WEIGHTS, cfg.OUTPUT_DIR = "", ""
+        cfg.MODEL.DEVICE = "cuda:%d" % local_rank
+    cfg = cfgs[0]
+    K, dev = cfg.MODEL.RETINANET.NUM_CLASSES, cfg.MODEL.DEVICE
+    dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST,
+                         device_resize=args.resize_on_gpu) if args.coco_json else None
+    if dataset is not None:
+        args.num_images = len(dataset)
+    mine = shard_indices(args.num_images, rank, world)
+    torch.manual_seed(args.random_seed)
+    compare = build_comparison(cfgs)
+    compare.return_device = True
+    compare.sparse_bbox_tower = not args.dense_bbox and os.environ.get("POD_SPARSE_BBOX", "1") != "0"
+    for m in [compare.model] + list(compare.model_list):
+        if isinstance(m, modeling.ProbabilisticRetinaNet):
+            m.enable_graphs(not args.no_graphs)
+            m.graph_after_seen = 2
+    # the streams of the config that asks for the fewest: an MC-dropout config's masks are keyed by the forward number of a stream, so
+    # its files are those of its own run only on its own run's streams; the other configs' bytes do not depend on the stream count
+    own_streams = [2 if p.mc_dropout_enabled and p.num_mc_dropout_runs > 1 else 3 if p.inference_mode == "ensembles" and len(p.model_list) > 1 else 4
+                   for p in compare.predictors]
+    n_streams = args.streams if args.streams > 0 else min(own_streams)
+    streams = [torch.cuda.current_stream()] + [torch.cuda.Stream() for _ in range(n_streams - 1)]
+    width, F, N = record_width(K), max(1, args.flush_every), len(cfgs)
+    n_mine = len(shard_indices(args.num_images, 0, world))
+    all_ids: List[List[int]] = [[] for _ in range(N)]
+    all_cnt, all_rec = [[] for _ in range(N)], [[] for _ in range(N)]
+
+    def flush(chunk_ids, recs, cnts):
+        """One collective per config: this chunk's records of every rank, image order restored."""
+        for st in streams[1:]:
+            streams[0].wait_stream(st)
+        for k in range(N):
+            rec = torch.stack(recs[k]) if recs[k] else torch.zeros((0, 128, width), device=dev)
+            cnt = torch.stack(cnts[k]) if cnts[k] else torch.zeros((0,), dtype=torch.int32, device=dev)
+            ids, cnt, rec = gather_records(chunk_ids, cnt, rec, args.num_images, world, per_rank=F)
+            all_ids[k].extend(ids)
+            all_cnt[k].append(cnt.cpu())
+            all_rec[k].append(rec.cpu())
+
+    torch.cuda.synchronize()
+    t_loop = time.perf_counter()
+    chunk_ids, recs, cnts = [], [[] for _ in range(N)], [[] for _ in range(N)]
+    workers = args.loader_workers if args.loader_workers >= 0 else int(cfg.DATALOADER.NUM_WORKERS)
+    loaded = iter(Prefetched(dataset, mine, workers=workers)) if dataset is not None else None
+    with torch.no_grad():
+        for j in range(n_mine):
+            if j < len(mine):
+                i = mine[j]
+                if loaded is not None:
+                    _, d = next(loaded)
+                with torch.cuda.stream(streams[j % len(streams)]):
+                    input_im, _ = _network_input(args, cfg, d if dataset is not None else None, i, dev)
+                    dets = compare(input_im)
+                    chunk_ids.append(i)
+                    for k, det in enumerate(dets):
+                        recs[k].append(det.records)
+                        cnts[k].append(det.n_det)
+                if os.environ.get("POD_SYNC_EACH_IMAGE") == "1":
+                    torch.cuda.synchronize()
+            if (j + 1) % F == 0 or j + 1 == n_mine:
+                flush(chunk_ids, recs, cnts)
+                chunk_ids, recs, cnts = [], [[] for _ in range(N)], [[] for _ in range(N)]
+    torch.cuda.synchronize()
+    t_loop = time.perf_counter() - t_loop
+    if rank == 0:
+        cat_map = category_mapping(args.train_dataset, args.test_dataset)
+        for k in range(N):
+            ids, cnt, rec = _image_order(all_ids[k], all_cnt[k], all_rec[k], width, dataset)
+            os.makedirs(dirs[k], exist_ok=True)
+            with open(outputs[k], "w") as fp:
+                json.dump(results_json(ids, cnt, rec, K, cat_map), fp, indent=4, separators=(",", ": "))
+            if sidecars[k]:
+                from .inference_utils import write_binary_results
+                write_binary_results(sidecars[k], ids, cnt, rec, K)
+            print("wrote %s: %d images, %d detections" % (outputs[k], len(ids), int(cnt.sum())))
+        if t_loop > 0:
+            print("comparison loop: %d images x %d configs on %d rank(s) in %.2f s = %.1f images/s; per image %d model evaluation(s) and %d "
+                  "front(s) (%d stream(s) per GPU)" % (args.num_images, N, world, t_loop, args.num_images / t_loop,
+                                                        len(compare.families), sum(len(f.subfamilies) for f in compare.families), n_streams))
+    res = evaluate_all(dev) if rank == 0 and args.eval else None
+    if world > 1:
+        dist.destroy_process_group()
+    return res
+
+
 def main(argv=None):
-    from . import synthetic
     from .config import setup_config
     from .probabilistic_inference import build_predictor
     ap = argparse.ArgumentParser()
     here = os.path.dirname(os.path.abspath(__file__))
     ap.add_argument("--config-file", default=os.path.join(here, "configs/BDD-Detection/retinanet/retinanet_R_50_FPN_1x_reg_cls_var_dropout.yaml"))
-    ap.add_argument("--inference-config", default=os.path.join(here, "configs/Inference/bayes_od_mc_dropout.yaml"))
+    ap.add_argument("--inference-config", nargs="+", default=[os.path.join(here, "configs/Inference/bayes_od_mc_dropout.yaml")],
+                    help="one inference YAML, or several to compare on ONE pass over the data: the configs whose model evaluation is the same call "
+                         "share it, those that also share the candidate list share merge + score, top-k, decode and NMS, and every config writes "
+                         "coco_instances_results.json (with --binary-output NAME its sidecar, with --eval its mAP_res.txt) to <OUTPUT_DIR>/inference/"
+                         "<test data set>/<name of its YAML>/ -- the bytes of its own run; --eval ends with comparison.txt beside the first.  "
+                         "Configs that share an evaluation but not the candidate list (pre- and post-NMS ensembles together) get the bbox side "
+                         "evaluated on every cell: their files are those of their own runs under --dense-bbox.  --output, --vis-dir and "
+                         "--ensemble-per-gpu take one config")
     ap.add_argument("--num-images", type=int, default=8, help="synthetic 1280x720 frames (ignored with --coco-json)")
     ap.add_argument("--coco-json", default="", help="COCO-format json whose `images` are run (the reference's test data loader, AN:83-84)")
     ap.add_argument("--image-root", default="", help="directory of the files named in --coco-json")
@@ -399,6 +614,9 @@ def main(argv=None):
                     help="--vis-dir: reference = the ellipses as PV:70-86 pairs them (the box drawn k-th, by area, gets the k-th covariance of "
                          "the result order); box = every box with its own covariance")
     args = ap.parse_args(argv)
+    if len(args.inference_config) > 1:
+        return _main_comparison(args, list(args.inference_config))
+    args.inference_config = args.inference_config[0]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     evaluating = args.eval or args.eval_only
     if evaluating:
@@ -422,16 +640,7 @@ def main(argv=None):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.share_gpu:
         local_rank = 0
-    if world > 1:
-        if args.backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group(args.backend)
-    torch.cuda.set_device(local_rank)
-    if world > 1:                 # enqueue + loader threads of this rank on its GPU's NUMA node (hostbind.py; POD_BIND_NUMA=0: off)
-        from . import hostbind
-        b = hostbind.bind_rank_to_gpu_numa(local_rank)
-        print("rank %d: cuda:%d pci %s numa node %s -> %s" % (rank, local_rank, b["pci"], b["numa_node"], b["cpus"] if b["bound"] else "not bound (%s)" % b.get("why_not", "off")))
+    _start_rank(args, world, rank, local_rank)
     cfg = setup_config(args.config_file, args.inference_config, args.random_seed, data_dir=args.data_dir, is_testing=bool(args.data_dir))
     if args.weights is not None:
         cfg.MODEL.WEIGHTS = args.weights
@@ -439,7 +648,7 @@ def main(argv=None):
         cfg.MODEL.WEIGHTS, cfg.OUTPUT_DIR = "", ""
     cfg.MODEL.DEVICE = "cuda:%d" % local_rank
     K = cfg.MODEL.RETINANET.NUM_CLASSES
-    from . import modeling, resize
+    from . import modeling
     dataset = CocoImages(args.coco_json, args.image_root, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST,
                          device_resize=args.resize_on_gpu) if args.coco_json else None
     if dataset is not None:
@@ -508,17 +717,7 @@ def main(argv=None):
                     if loaded is not None:
                         _, d = next(loaded)                             # resized on the host exactly as detectron2's mapper does, a few entries ahead
                     with torch.cuda.stream(streams[j % len(streams)]):
-                        if dataset is not None:
-                            if args.resize_on_gpu:      # the decoded frame goes up; the host path's bytes come out (K20), outside any captured graph
-                                image = resize.resize_frame_u8(d["frame"].to(dev, non_blocking=True), cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
-                            else:
-                                image = d["image"].to(dev, non_blocking=True)
-                            input_im = [{"image": image, "height": d["height"], "width": d["width"],
-                                         "image_id": i}]                # position in the list: the dataset's id is restored below
-                        else:
-                            frame = synthetic.synthetic_frame(i, device=dev)
-                            image = modeling.resize_test_image(frame, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
-                            input_im = [{"image": image, "height": frame.shape[1], "width": frame.shape[2], "image_id": i}]
+                        input_im, frame = _network_input(args, cfg, d if dataset is not None else None, i, dev)
                         det = predictor(input_im)
                         if vis is not None:           # enqueued behind the detections on this stream; not part of any captured graph
                             if dataset is not None:
@@ -538,13 +737,7 @@ def main(argv=None):
             print("rank %d: wrote %d annotated frames to %s" % (rank, vis.count, args.vis_dir))
     torch.cuda.synchronize()
     t_loop = time.perf_counter() - t_loop
-    ids = all_ids
-    order = sorted(range(len(ids)), key=lambda q: ids[q])
-    ids = [ids[q] for q in order]
-    cnt = torch.cat(all_cnt)[order] if all_cnt else torch.zeros((0,), dtype=torch.int32)
-    rec = torch.cat(all_rec)[order] if all_rec else torch.zeros((0, 128, width))
-    if dataset is not None:
-        ids = [dataset.image_id(i) for i in ids]
+    ids, cnt, rec = _image_order(all_ids, all_cnt, all_rec, width, dataset)
     if rank == 0:
         with open(args.output, "w") as fp:
             json.dump(results_json(ids, cnt, rec, K, category_mapping(args.train_dataset, args.test_dataset)), fp, indent=4, separators=(",", ": "))

@@ -40,7 +40,7 @@ POD_SGD_CLIP_OFF, POD_SGD_CLIP_VALUE, POD_SGD_CLIP_NORM, POD_SGD_CLIP_FULL_MODEL
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
            "pod_decode_cov", "pod_nms_scratch_bytes", "pod_nms_cluster", "pod_bayes_fuse", "pod_anchor_stats_merge",
            "pod_ensemble_append", "pod_ensemble_merge",
-           "pod_finalize", "pod_reg_nll", "pod_relu_dropout", "pod_bias_act", "pod_bias_act_to_nchw", "pod_bias_act_to_nhwc", "pod_expand_dropout", "pod_match_groundtruth", "pod_run_image", "pod_run_image_part",
+           "pod_finalize", "pod_reg_nll", "pod_relu_dropout", "pod_bias_act", "pod_bias_act_to_nchw", "pod_bias_act_to_nhwc", "pod_expand_dropout", "pod_match_groundtruth", "pod_run_image", "pod_run_image_part", "pod_run_image_modes",
            "pod_absmax", "pod_wino_filter_transform", "pod_wino_conv3x3", "pod_wino_filter_split_bytes", "pod_wino_filter_transform_split", "pod_wino_conv3x3_split", "pod_sparse_reach", "pod_sparse_live_blocks", "pod_wino_reduce", "pod_conv1x1_filter_split_bytes", "pod_conv1x1_filter_split", "pod_conv1x1_split", "pod_reduce_partials", "pod_stem7x7_filter_split", "pod_stem7x7_split", "pod_maxpool3x3s2_cl", "pod_im2col3x3s2_cl",
            "pod_coco_eval_scratch_bytes", "pod_coco_eval_images", "pod_coco_accumulate_workspace_bytes", "pod_coco_accumulate",
            "pod_calib_keys", "pod_calib_reg_counts", "pod_calib_min_uncertainty_workspace_bytes", "pod_calib_min_uncertainty",
@@ -66,6 +66,8 @@ _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scra
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
+POD_PART_SELECT, POD_PART_FINISH, POD_PART_CANDIDATES, POD_PART_FRONT, POD_PART_TAIL = 1, 2, 4, 5, 8
+POD_MAX_MODE_TAILS = 8
 
 
 class PodLevel(Structure):
@@ -94,6 +96,11 @@ class PodWorkspace(Structure):
 class PodDetections(Structure):
     """include/pod_mi355x.h: PodDetections (pod_finalize's outputs)."""
     _fields_ = [(n, c_void_p) for n in ("boxes", "cov", "scores", "classes", "probs", "records", "n_det")]
+
+
+class PodModeTail(Structure):
+    """include/pod_mi355x.h: PodModeTail (one inference config of a pod_run_image_modes call)."""
+    _fields_ = [("mode", c_int32), ("box_merge_mode", c_int32), ("cls_merge_mode", c_int32), ("reserved", c_int32), ("out", PodDetections)]
 
 
 class PodConvSet(Structure):
@@ -246,6 +253,8 @@ def load() -> ctypes.CDLL:
                                   c_int32, c_int32, c_int32, c_int32, POINTER(PodDetections), P]
     lib.pod_run_image_part.argtypes = [POINTER(PodConfig), POINTER(PodLevel), POINTER(PodWorkspace), c_int32, c_int32, c_int32,
                                        c_int32, c_int32, c_int32, c_int32, POINTER(PodDetections), c_int32, P]
+    lib.pod_run_image_modes.argtypes = [POINTER(PodConfig), POINTER(PodLevel), POINTER(PodWorkspace), POINTER(PodModeTail), c_int32,
+                                        c_int32, c_int32, c_int32, c_int32, P]
     lib.pod_coco_eval_scratch_bytes.argtypes = [c_int32, c_int32]
     lib.pod_coco_eval_scratch_bytes.restype = c_size_t
     lib.pod_coco_eval_images.argtypes = [POINTER(PodCocoParams), P, c_int32] + [P] * 12 + [P]

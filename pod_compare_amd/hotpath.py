@@ -494,6 +494,60 @@ class HotPath:
         self._dirty = False
         return out
 
+    # -- several inference configs on one front (pod_run_image_modes; probabilistic_inference.build_comparison) --------------------------
+    def _mode_tails(self, tails, out_size):
+        """tails: (mode, box_merge_mode, cls_merge_mode) names per config -> (PodModeTail array, its DeviceDetections); refuses what the C
+        entry would, by name."""
+        tails = [(t,) if isinstance(t, str) else tuple(t) for t in tails]
+        if not 1 <= len(tails) <= hip.POD_MAX_MODE_TAILS:
+            raise hip.PodError("1 .. {} tails per front, got {}".format(hip.POD_MAX_MODE_TAILS, len(tails)))
+        arr, outs = (hip.PodModeTail * len(tails))(), []
+        for i, t in enumerate(tails):
+            mode, bm, cm = (t + ("bayesian_inference", "max_score")[len(t) - 1:])[:3]
+            if mode not in MODES:
+                raise ValueError("Invalid inference mode {}.".format(mode))   # PI:100-103
+            if mode == "bayes_od" and not self.has_covariance:
+                raise hip.PodError("bayes_od needs box covariances (a reg_var head or MC runs)")
+            out = self.new_detections(out_size)
+            arr[i].mode = self._MODE_ID[mode]
+            arr[i].box_merge_mode = {"bayesian_inference": 0, "covariance_intersection": 1}[bm]
+            arr[i].cls_merge_mode = {"max_score": 0, "bayesian_inference": 1}[cm]
+            arr[i].out = hip.PodDetections(out.ptr("boxes"), out.ptr("cov"), out.ptr("scores"), out.ptr("classes"), out.ptr("probs"),
+                                           out.ptr("records"), out.ptr("n_det"))
+            outs.append(out)
+        return arr, outs
+
+    def run_modes(self, tails, cls, delta, cls_var=None, reg_var=None, *, image_size, out_size,
+                  draw_id: Optional[int] = None) -> List[DeviceDetections]:
+        """pod_run_image_modes: K1 .. K4 of one image once, then per tail -- (mode, box_merge_mode, cls_merge_mode), or a mode name -- its
+        fusion launch and K7 into a DeviceDetections of its own.  Tail t's detections are `run_image(*tails[t])`'s at the same draw id, bit for
+        bit; one draw id is consumed."""
+        arr, outs = self._mode_tails(tails, out_size)
+        self._clean()
+        self._begin_draw(draw_id)
+        lv = self._levels(cls, delta, cls_var, reg_var, None)
+        self._lv_keepalive = (lv, None)
+        self._dirty = True       # a failure between K1 and K2 leaves counters / bitmap non-zero
+        hip.check(self.lib.pod_run_image_modes(self.cfg, lv, self.ws, arr, len(outs), int(image_size[0]), int(image_size[1]),
+                                               int(out_size[0]), int(out_size[1]), hip.current_stream()), "pod_run_image_modes")
+        self._dirty = False
+        return outs
+
+    def finish_modes(self, tails, cls, delta, cls_var, reg_var, image_size, out_size) -> List[DeviceDetections]:
+        """`finish` for several configs after one `select`: gather + decode + NMS once (parts = 4), then a tail per config (parts = 8)."""
+        arr, outs = self._mode_tails(tails, out_size)
+        lv = self._levels(cls, delta, cls_var, reg_var, None)
+        self._lv_keepalive = (lv, None)
+        size = (int(image_size[0]), int(image_size[1]), int(out_size[0]), int(out_size[1]))
+        st = hip.current_stream()
+        hip.check(self.lib.pod_run_image_part(self.cfg, lv, self.ws, hip.POD_MODE_STANDARD_NMS, 0, 0, *size, None, hip.POD_PART_CANDIDATES, st),
+                  "pod_run_image_part(candidates)")
+        self._dirty = False
+        for t in arr:
+            hip.check(self.lib.pod_run_image_part(self.cfg, lv, self.ws, t.mode, t.box_merge_mode, t.cls_merge_mode, *size, t.out,
+                                                  hip.POD_PART_TAIL, st), "pod_run_image_part(tail)")
+        return outs
+
     def run(self, mode: str, cls, delta, cls_var=None, reg_var=None, *, image_size, out_size,
             eps_fn: Optional[Callable] = None, box_merge_mode: str = "bayesian_inference",
             cls_merge_mode: str = "max_score", write_merged: bool = True, one_call: bool = True,

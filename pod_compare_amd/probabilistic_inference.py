@@ -84,6 +84,14 @@ def build_predictor(cfg, model=None, model_list=None):
     raise ValueError("Invalid meta-architecture {}.".format(cfg.MODEL.META_ARCHITECTURE))
 
 
+def build_comparison(cfgs, model=None, model_list=None):
+    """Several inference configs (merged configs that differ in PROBABILISTIC_INFERENCE only) on one pass: `comparison(input_im)` returns
+    one result per config, each bit-equal to `build_predictor(cfg)(input_im)`'s, for one model evaluation per family of configs and one
+    front of the post-processing chain per sub-family (pod_compare_amd/comparison.py)."""
+    from .comparison import Comparison
+    return Comparison(cfgs, model=model, model_list=model_list)
+
+
 class ProbabilisticPredictor(ABC):
     """PI:36-166."""
 
