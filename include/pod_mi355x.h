@@ -1210,6 +1210,33 @@ int pod_retinanet_infer_image(const PodConfig* cfg, const PodLevel* levels, cons
                               int32_t image_w, int32_t out_h, int32_t out_w, float* det_boxes, float* det_scores, int32_t* det_classes,
                               int32_t* n_det, pod_stream_t stream);
 
+/* ---- K33  the evaluation's bounded scoring rules: energy score and CRPS (csrc/k33_eval_scores.hip) ----------------------------
+ * Serves: compute_reg_scores (scoring_rules.py:45-81) when asked for more than the NLL.  The reference's scoring_rules.py defines the
+ * ignorance score and the MSE and NEITHER of these rules; the definitions are the ones below, in box space (no smooth-L1 term, no division
+ * by the coordinate count: this is not K27's training loss, which lives in delta space).  One new symbol and one new stream word under
+ * POD_ABI_VERSION 18, as for K20 - K32: no entry or structure that existed changed, so the number stands.
+ *
+ * Rows i < n: means (n, 4), covs (n, 4, 4), gt (n, 4), dev fp32, as pod_reg_nll takes them.  Sigma = cov + 1e-2 I, the sum formed in fp32 and
+ * then widened; L its Cholesky factor in fp64, the lower triangle read -- pod_reg_nll's factorisation, one copy shared by both kernels.
+ *   Energy score, M = num_samples, eps_s in R^4 for s = 0 .. M (M + 1 draws, iid N(0, 1), fp32):
+ *     u1_s = (mean - gt) + L eps_s;   u2_s = L (eps_s - eps_{s+1}), formed from the fp32 difference of the normals, widened, and never as a
+ *     difference of samples (K27's and K28's rule);   energy[i] = (1 / M) sum_{s < M} |u1_s|_2  -  (1 / (2 M)) sum_{s < M} |u2_s|_2.
+ *   CRPS, the marginal rule, closed form, no draws: sd_j = sqrt(Sigma_jj), z_j = (gt_j - mean_j) / sd_j,
+ *     crps[i] = (1 / 4) sum_j sd_j [z_j (2 Phi(z_j) - 1) + 2 phi(z_j) - 1 / sqrt(pi)],  Phi through erf.
+ *   Everything after the fp32 normals is fp64; each output rounds to fp32 once, at its store.  A row whose Sigma is not positive definite
+ *   gets NaN in both outputs and affects no other row (pod_reg_nll behaves so).
+ * One wavefront per row; a lane owns the sample pairs c = lane, lane + 64, ..., keeps two fp64 partial sums, a butterfly in a fixed order
+ * adds them.  No atomics: two launches give the same bits, and a row's result depends on that row's inputs, its index i, `seed` and M alone
+ * -- not on n, the grid or the other rows.
+ * Draws: eps_in NULL = in-kernel Philox4x32-10 normals on a stream word of their own (0x65767300, "evs"): samples 2c and 2c + 1 of row i are
+ *   components 0..3 and 4..7 of the call with counter (i, 0, c, stream word) and key `seed` (K27's map); or dev (num_samples + 1, n, 4) normals
+ *   to replay.  eps_out: NULL or a buffer of that shape receiving the normals used.  Both are a test and replay facility.
+ * energy / crps: dev float[n]; either may be NULL (not both) and is then not computed; with energy NULL num_samples is ignored.
+ * POD_E_INVALID before anything is enqueued: means, covs or gt NULL; energy and crps both NULL; n < 0; energy given and num_samples outside
+ *   [1, POD_MAX_REG_SAMPLES]; eps_in or eps_out given while energy is NULL, or off 16 bytes.  n == 0: POD_OK, nothing launched. */
+int pod_reg_scores(const float* means, const float* covs, const float* gt, int32_t n, int32_t num_samples, uint64_t seed,
+                   const float* eps_in, float* eps_out, float* energy, float* crps, pod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,12 +298,14 @@ def has_ground_truth(coco_json: str) -> bool:
 
 
 def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train", test_dataset: str = "bdd_val", binary: bool = False,
-                     min_allowed_score: Optional[float] = None, map_results: str = "", device: str = "cuda", seed: int = 0) -> dict:
+                     min_allowed_score: Optional[float] = None, map_results: str = "", device: str = "cuda", seed: int = 0,
+                     scoring_rules: Sequence[str] = ("nll",), energy_samples: int = 1000) -> dict:
     """AN:104-106: the offline chain on a result file, in this process on `device`.  1) AP on K17 (compute_average_precision, its
     default --cat-ids), mAP_res.txt written beside `results`; 2) PM; 3) CE with the calibration pass on the GPU (K18).  Prints the
     three tables the modules print.  The PM / CE threshold: `min_allowed_score`, else `map_results`' (PM:50-65 / CE:47-63), else --
     when the test set is the model's own (bdd_val for a BDD model) -- the threshold the AP step just wrote, else 0.0.  (The reference
-    reads the training family's file; its AN:104 has the AP call commented out.)  torch is seeded with `seed` before CE's randperm."""
+    reads the training family's file; its AN:104 has the AP call commented out.)  torch is seeded with `seed` before CE's randperm.
+    scoring_rules beside "nll" (energy, crps, brier) and energy_samples go to PM with `seed`: extra columns, nothing else changes."""
     from . import compute_average_precision as cap
     from . import compute_calibration_errors as cce
     from . import compute_probabilistic_metrics as cpm
@@ -328,13 +330,21 @@ def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train
     else:
         thr = 0.0
     cmap = evaluation_category_map(train_dataset, test_dataset)
-    pm = cpm.probabilistic_metrics(predicted, gt["annotations"], cat_mapping_dict=cmap, min_allowed_score=thr, device=device)
+    extra = {} if tuple(scoring_rules) == ("nll",) else {"scoring_rules": tuple(scoring_rules), "energy_samples": energy_samples, "seed": seed}
+    pm = cpm.probabilistic_metrics(predicted, gt["annotations"], cat_mapping_dict=cmap, min_allowed_score=thr, device=device, **extra)
     print(cpm.format_table(pm))
     torch.manual_seed(seed)
     ce = cce.calibration_errors_of_results(predicted, gt["annotations"], cmap, thr, device=device)
     print(cce.format_table(ce))
     print("Cls Marginal Calibration Error computed by: " + ce["cls_marginal_calibration_error_source"])
     return {"ap": ap, "pm": pm, "ce": ce, "min_allowed_score": thr, "map_results": map_path}
+
+
+def _scoring_rule_options(args) -> dict:
+    """--scoring-rules / --energy-samples as evaluate_results takes them; nothing when only the reference's rules are asked for."""
+    if tuple(args.scoring_rules) == ("nll",):
+        return {}
+    return {"scoring_rules": tuple(args.scoring_rules), "energy_samples": args.energy_samples}
 
 
 def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str) -> str:
@@ -352,20 +362,28 @@ COMPARISON_COLUMNS = (      # (heading, evaluator, path into the dictionary eval
     ("Cls MCE", "ce", ("cls_marginal_calibration_error",), "%.4f"), ("Reg ECE", "ce", ("reg_expected_calibration_error",), "%.4f"),
     ("Reg MaxCE", "ce", ("reg_maximum_calibration_error",), "%.4f"), ("Cls MUE", "ce", ("cls_minimum_uncertainty_error",), "%.4f"),
     ("Reg MUE", "ce", ("reg_minimum_uncertainty_error",), "%.4f"))
+EXTRA_COMPARISON_COLUMNS = (      # appended, in this order, when a result carries the key: --scoring-rules brier / energy / crps
+    ("TP Cls Brier", "pm", ("average", "true_positives_cls_analysis", "brier_score_mean"), "%.4f"),
+    ("FP Cls Brier", "pm", ("average", "false_positives_cls_analysis", "brier_score_mean"), "%.4f"),
+    ("TP Reg Energy", "pm", ("average", "true_positives_reg_analysis", "energy_score_mean"), "%.4f"),
+    ("TP Reg CRPS", "pm", ("average", "true_positives_reg_analysis", "crps_mean"), "%.4f"))
 
 
 def format_comparison_table(names: Sequence[str], results: Sequence[dict]) -> str:
     """One row per inference config, in order, from the dictionaries `evaluate_results` returned: AP / AP50 / AP75 (COCO's first three
     numbers), the four score columns of the PM table and the five of the CE table.  No number is computed here; one that an evaluator
-    left undefined (no true positives, say) prints as "-"."""
+    left undefined (no true positives, say) prints as "-".  The columns of the extra scoring rules follow when a result carries them."""
     def cell(res, which, path, fmt):
         v = res[which]
         for k in path:
-            v = v[k]
-        return "-" if v is None else fmt % float(v)
+            v = v.get(k) if isinstance(v, dict) else v[k]
+            if v is None:
+                return "-"
+        return fmt % float(v)
 
-    rows = [("Inference Config",) + tuple(c[0] for c in COMPARISON_COLUMNS)]
-    rows += [(n,) + tuple(cell(r, *c[1:]) for c in COMPARISON_COLUMNS) for n, r in zip(names, results)]
+    columns = COMPARISON_COLUMNS + tuple(c for c in EXTRA_COMPARISON_COLUMNS if any(c[2][2] in r[c[1]][c[2][0]][c[2][1]] for r in results))
+    rows = [("Inference Config",) + tuple(c[0] for c in columns)]
+    rows += [(n,) + tuple(cell(r, *c[1:]) for c in columns) for n, r in zip(names, results)]
     w = [max(len(r[i]) for r in rows) for i in range(len(rows[0]))]
     line = "+" + "+".join("-" * (x + 2) for x in w) + "+"
     body = ["| " + r[0].ljust(w[0]) + " | " + " | ".join(r[i].center(w[i]) for i in range(1, len(r))) + " |" for r in rows]
@@ -446,7 +464,7 @@ def _main_comparison(args, paths: List[str]):
             print("== %s" % name)
             binary = args.eval_only and bool(side)        # as one config's --eval-only: the sidecar when it is named
             res.append(evaluate_results(side if binary else out, args.coco_json, args.train_dataset, args.test_dataset, binary=binary,
-                                        min_allowed_score=args.min_allowed_score, map_results=args.map_results, device=device, seed=args.random_seed))
+                                        min_allowed_score=args.min_allowed_score, map_results=args.map_results, device=device, seed=args.random_seed, **_scoring_rule_options(args)))
         table = format_comparison_table(names, res)
         with open(os.path.join(dirs[0], "comparison.txt"), "w") as f:
             f.write(table + "\n")
@@ -606,6 +624,8 @@ def main(argv=None):
                                                              "that is given) as --eval does")
     ap.add_argument("--min-allowed-score", type=float, default=None, help="--eval: the detections' score threshold of PM and CE")
     ap.add_argument("--map-results", default="", help="--eval: take the PM / CE threshold from this mAP_res.txt (PM:50-65)")
+    from .compute_probabilistic_metrics import add_scoring_rule_arguments
+    add_scoring_rule_arguments(ap)          # --eval: --scoring-rules nll [energy] [crps] [brier], --energy-samples (draws keyed by --random-seed)
     ap.add_argument("--vis-dir", default="", help="also write every image of this rank annotated as visualize_inference draws it (PI:113-146): "
                                                    "the first --vis-max-boxes detections with their corner-covariance ellipses over the frame at "
                                                    "its original size, rendered on the GPU (K19) and encoded on host threads as <dir>/<file stem>.png")
@@ -633,7 +653,7 @@ def main(argv=None):
         local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
         return evaluate_results(args.binary_output if binary else (args.output or "coco_instances_results.json"), args.coco_json,
                                 args.train_dataset, args.test_dataset, binary=binary, min_allowed_score=args.min_allowed_score,
-                                map_results=args.map_results, device="cuda:%d" % local_rank, seed=args.random_seed)
+                                map_results=args.map_results, device="cuda:%d" % local_rank, seed=args.random_seed, **_scoring_rule_options(args))
     if args.output is None:
         args.output = "coco_instances_results.json"
     rank = int(os.environ.get("RANK", "0"))
@@ -755,7 +775,7 @@ def main(argv=None):
     res = None
     if rank == 0 and args.eval:
         res = evaluate_results(args.output, args.coco_json, args.train_dataset, args.test_dataset, min_allowed_score=args.min_allowed_score,
-                               map_results=args.map_results, device=dev, seed=args.random_seed)
+                               map_results=args.map_results, device=dev, seed=args.random_seed, **_scoring_rule_options(args))
     if world > 1:
         dist.destroy_process_group()
     return res

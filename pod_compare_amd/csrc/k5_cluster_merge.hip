@@ -17,6 +17,7 @@
 // combined with wavefront butterflies plus one LDS hop across the 4 waves.  K6's parts have names (cluster_prologue,
 // FOR_EACH_MEMBER, centre_fallback); K5 is written out (see there); the host checks and fills both through cluster_params.
 #include "pod_device.h"
+#include "pod_reg_sigma.h"
 
 namespace pod {
 
@@ -622,20 +623,9 @@ __global__ void __launch_bounds__(256) k_reg_nll(const float* means, const float
     if (i >= n) return;
     // -log N(gt; mean, cov + 1e-2 I) through a 4x4 Cholesky factor
     double a[4][4], L[4][4];
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) a[r][c] = (double)(covs[(size_t)i * 16 + r * 4 + c] + ((r == c) ? 1e-2f : 0.0f));
+    reg_sigma_factor(covs + (size_t)i * 16, a, L);
     double logdet = 0.0;
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c <= r; ++c) {
-            double s = a[r][c];
-            for (int k = 0; k < c; ++k) s -= L[r][k] * L[c][k];
-            if (r == c) {
-                L[r][r] = sqrt(s);
-                logdet += log(L[r][r]);
-            } else {
-                L[r][c] = s / L[c][c];
-            }
-        }
+    for (int r = 0; r < 4; ++r) logdet += log(L[r][r]);
     double y[4], maha = 0.0;
     for (int r = 0; r < 4; ++r) {
         double s = (double)gt[(size_t)i * 4 + r] - (double)means[(size_t)i * 4 + r];

@@ -141,6 +141,7 @@ struct f32x8n {
 // stream ids for the counter's 4th word
 constexpr uint32_t STREAM_CLS = 0x636c7300u;   // classification logit samples (PI:291-295)
 constexpr uint32_t STREAM_BOX = 0x626f7800u;   // box-delta samples (PI:351-356)
+constexpr uint32_t STREAM_EVAL_SCORE = 0x65767300u;   // box samples of the evaluation's energy score ("evs", k33_eval_scores.hip)
 
 __device__ __forceinline__ f32x8n philox_normals8(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t stream) {
     const u32x4 r = philox4x32_10(u32x4{c0, c1, c2, stream}, (uint32_t)seed, (uint32_t)(seed >> 32));

@@ -6,6 +6,11 @@ core/evaluation_tools/scoring_rules.py (SR) `compute_reg_scores`, `compute_reg_s
 row order (prediction-dict key order, then ground-truth order, true positive = highest max class probability).
 The reference re-concatenates its result tensors inside a Python loop over every ground-truth box (EU:222-360);
 here one kernel launch labels the whole data set and the partitions are gathered with index tensors on the device.
+
+Beside the reference's rules: `reg_proper_scores` (energy score and CRPS per row, kernel pod_reg_scores, K33) and `brier_rows` -- bounded
+proper scoring rules scoring_rules.py does not define.  A partition that carries their per-row tensors ("energy_score", "crps",
+"brier_score") gets their means under the mask from `compute_reg_scores` / `retinanet_compute_cls_scores`; one that does not gets what
+the reference returns.
 """
 import math
 from typing import Dict
@@ -69,17 +74,60 @@ def match_predictions_to_groundtruth(predicted_box_means: Dict, predicted_cls_pr
             "false_negatives": {"gt_box_means": gb[fn_g], "gt_cat_idxs": gc[fn_g]}}
 
 
+def reg_proper_scores(means: torch.Tensor, covs: torch.Tensor, gt: torch.Tensor, num_samples: int = 1000, seed: int = 0,
+                      energy: bool = True, crps: bool = True) -> Dict:
+    """Per-row energy score ("energy_score") and CRPS ("crps") of N(mean, cov + 1e-2 I) at the ground truth, fp32, from ONE launch of
+    pod_reg_scores (include/pod_mi355x.h, K33; the reference defines neither rule).  Row i draws under (seed, i) alone: a row's score
+    depends neither on the number of rows nor on the other rows."""
+    n = int(means.shape[0])
+    out = {}
+    if energy:
+        out["energy_score"] = torch.empty(n, dtype=torch.float32, device=means.device)
+    if crps:
+        out["crps"] = torch.empty(n, dtype=torch.float32, device=means.device)
+    if not out:
+        raise ValueError("reg_proper_scores: neither rule asked for")
+    if n == 0:
+        return out
+    f = lambda t: t.to(torch.float32).contiguous()
+    means, covs, gt = f(means), f(covs), f(gt)
+    with torch.cuda.device(means.device):
+        hip.check(hip.load().pod_reg_scores(hip.ptr(means), hip.ptr(covs), hip.ptr(gt), n, int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                            None, None, hip.ptr(out.get("energy_score")), hip.ptr(out.get("crps")), hip.current_stream()),
+                  "pod_reg_scores")
+    return out
+
+
+def brier_rows(p: torch.Tensor) -> torch.Tensor:
+    """Per-row Brier score of the binary vector [p, 1 - p] against [1, 0] -- the multilabel formulation retinanet_compute_cls_scores uses
+    for the ignorance score (SR:6-42): (1 - p)^2 + (1 - p)^2."""
+    q = 1.0 - p
+    return 2.0 * q * q
+
+
+def _row_score_means(input_matches: Dict, valid_idxs: torch.Tensor, names) -> Dict:
+    """Means of the per-row tensors `input_matches` carries, under the mask: fp32 rows, the mean taken in fp64; None on an empty mask."""
+    out = {}
+    for name in names:
+        if name in input_matches:
+            rows = input_matches[name][valid_idxs]
+            out[name + "_mean"] = float(rows.double().mean()) if rows.shape[0] else None
+    return out
+
+
 def compute_reg_scores(input_matches: Dict, valid_idxs: torch.Tensor) -> Dict:
-    """SR:45-81: ignorance (NLL of N(mean, cov + 1e-2 I) at the ground truth, kernel pod_reg_nll) and MSE."""
+    """SR:45-81: ignorance (NLL of N(mean, cov + 1e-2 I) at the ground truth, kernel pod_reg_nll) and MSE; and, where the partition carries
+    the per-row tensors "energy_score" / "crps" (reg_proper_scores on the WHOLE partition), their means under the mask."""
     means = input_matches["predicted_box_means"][valid_idxs].contiguous()
     covs = input_matches["predicted_box_covariances"][valid_idxs].contiguous()
     gt = input_matches["gt_box_means"][valid_idxs].contiguous()
+    extra = _row_score_means(input_matches, valid_idxs, ("energy_score", "crps"))
     if means.shape[0] == 0:
-        return {"ignorance_score_mean": None, "mean_squared_error": None}
+        return dict({"ignorance_score_mean": None, "mean_squared_error": None}, **extra)
     lib = hip.load()
     nll = torch.empty(means.shape[0], dtype=torch.float32, device=means.device)
     hip.check(lib.pod_reg_nll(hip.ptr(means), hip.ptr(covs), hip.ptr(gt), means.shape[0], hip.ptr(nll), hip.current_stream()), "pod_reg_nll")
-    return {"ignorance_score_mean": float(nll.mean()), "mean_squared_error": float(((means - gt) ** 2).mean())}
+    return dict({"ignorance_score_mean": float(nll.mean()), "mean_squared_error": float(((means - gt) ** 2).mean())}, **extra)
 
 
 def compute_reg_scores_fn(false_positives: Dict, valid_idxs: torch.Tensor) -> Dict:
@@ -96,9 +144,10 @@ def compute_reg_scores_fn(false_positives: Dict, valid_idxs: torch.Tensor) -> Di
 def retinanet_compute_cls_scores(input_matches: Dict, valid_idxs: torch.Tensor) -> Dict:
     """SR:6-42: mean of -log p(correct) in the multilabel formulation."""
     p = input_matches["predicted_score_of_gt_category"][valid_idxs]
+    extra = _row_score_means(input_matches, valid_idxs, ("brier_score",))          # where the partition carries brier_rows of its rows
     if p.shape[0] == 0:
-        return {"ignorance_score_mean": None}
-    return {"ignorance_score_mean": float((-torch.log(p)).mean())}
+        return dict({"ignorance_score_mean": None}, **extra)
+    return dict({"ignorance_score_mean": float((-torch.log(p)).mean())}, **extra)
 
 
 def eval_predictions_preprocess(predicted_instances, min_allowed_score: float = 0.0, is_odd: bool = False, device="cpu"):

@@ -56,7 +56,7 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_stem7x7_wgrad_partials", "pod_stem7x7_wgrad", "pod_maxpool3x3s2_backward_cl",
            "pod_train_batch_tiles", "pod_train_batch_u8",
            "pod_retinanet_infer_workspace", "pod_retinanet_score", "pod_retinanet_topk", "pod_retinanet_decode", "pod_retinanet_postprocess",
-           "pod_retinanet_infer_image")
+           "pod_retinanet_infer_image", "pod_reg_scores")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
@@ -327,6 +327,7 @@ def load() -> ctypes.CDLL:
     lib.pod_retinanet_decode.argtypes = [POINTER(PodConfig), POINTER(PodLevel)] + [P] * 11
     lib.pod_retinanet_postprocess.argtypes = [POINTER(PodConfig)] + [P] * 5 + [c_float] * 4 + [P] * 5
     lib.pod_retinanet_infer_image.argtypes = [POINTER(PodConfig), POINTER(PodLevel), P, P, c_int32, c_int32, c_int32, c_int32, P, P, P, P, P]
+    lib.pod_reg_scores.argtypes = [P, P, P, c_int32, c_int32, c_uint64, P, P, P, P, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -13,6 +13,7 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
                  dense head tensors (per level, NCHW planes `(n_runs, A*C, H, W)`, the conv head's own layout) -> detections
     nms_cluster  detectron2 batched_nms as called at PI:554-560 / IU:31-36 -> keep indices
     reg_nll      compute_reg_scores' per-row NLL, scoring_rules.py:68-74
+    reg_scores   the per-row energy score and CRPS of the same Gaussians (K33; rules the reference does not define) -> (energy, crps)
     wino_filter_transform / wino_conv3x3
                  the head's `Conv2d(C, K, 3, padding=1) [+ ReLU + Dropout]` (PR:403-484) for all MC runs and FPN levels in one
                  launch: channels-last activations in, channels-last (trunk) or NCHW planes (predictors) out
@@ -40,6 +41,7 @@ _LIB.define("predict(Tensor[] box_cls, Tensor[] box_delta, Tensor[] box_cls_var,
             "-> (Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.define("nms_cluster(Tensor boxes, Tensor scores, Tensor classes, float nms_thresh, int max_detections, int num_classes) -> Tensor")
 _LIB.define("reg_nll(Tensor means, Tensor covs, Tensor gt) -> Tensor")
+_LIB.define("reg_scores(Tensor means, Tensor covs, Tensor gt, int num_samples=1000, int seed=0) -> (Tensor, Tensor)")
 _LIB.define("wino_filter_transform(Tensor weight) -> Tensor")
 _LIB.define("wino_conv3x3(Tensor src, Tensor U, Tensor? bias, Tensor blocks, int K, int out_elements, bool planes=False, bool relu=False, "
             "float dropout_p=0.0, int seed=0, int offset=0) -> Tensor")
@@ -150,6 +152,22 @@ def _reg_nll(means, covs, gt) -> torch.Tensor:
         hip.check(hip.load().pod_reg_nll(hip.ptr(means.contiguous()), hip.ptr(covs.contiguous()), hip.ptr(gt.contiguous()), n, hip.ptr(out),
                                          hip.current_stream()), "pod_reg_nll")
     return out
+
+
+def _reg_scores(means, covs, gt, num_samples=1000, seed=0) -> Tuple[torch.Tensor, torch.Tensor]:
+    n = int(means.shape[0])
+    for name, t, shape in (("means", means, (n, 4)), ("covs", covs, (n, 4, 4)), ("gt", gt, (n, 4))):
+        torch._check(t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == means.device,
+                     lambda: "{}: CUDA fp32 {}".format(name, shape))
+    torch._check(1 <= num_samples <= hip.POD_MAX_REG_SAMPLES, lambda: "num_samples in [1, {}]".format(hip.POD_MAX_REG_SAMPLES))
+    energy = torch.empty(n, dtype=torch.float32, device=means.device)
+    crps = torch.empty(n, dtype=torch.float32, device=means.device)
+    if n:
+        with torch.cuda.device(means.device):
+            hip.check(hip.load().pod_reg_scores(hip.ptr(means.contiguous()), hip.ptr(covs.contiguous()), hip.ptr(gt.contiguous()), n, int(num_samples),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, None, None, hip.ptr(energy), hip.ptr(crps), hip.current_stream()),
+                      "pod_reg_scores")
+    return energy, crps
 
 
 def _wino_filter_transform(weight) -> torch.Tensor:
@@ -351,5 +369,6 @@ _IMPL.impl("maxpool3x3s2_cl", _maxpool3x3s2_cl, "CUDA")
 _IMPL.impl("predict", _predict, "CUDA")
 _IMPL.impl("nms_cluster", _nms_cluster, "CUDA")
 _IMPL.impl("reg_nll", _reg_nll, "CUDA")
+_IMPL.impl("reg_scores", _reg_scores, "CUDA")
 _IMPL.impl("wino_filter_transform", _wino_filter_transform, "CUDA")
 _IMPL.impl("wino_conv3x3", _wino_conv3x3, "CUDA")
