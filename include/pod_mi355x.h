@@ -1237,6 +1237,60 @@ int pod_retinanet_infer_image(const PodConfig* cfg, const PodLevel* levels, cons
 int pod_reg_scores(const float* means, const float* covs, const float* gt, int32_t n, int32_t num_samples, uint64_t seed,
                    const float* eps_in, float* eps_out, float* energy, float* crps, pod_stream_t stream);
 
+/* ---- K34  PDQ, the probability-based detection quality: pairwise quality and assignment (csrc/k34_pdq.hip) ---------------------
+ * Replaces: nothing the reference runs -- its README's line "For evaluating with PDQ, please use the official PDQ code" sends the user to a
+ * separate CPU tool.  PDQ (Hall et al., "Probabilistic Object Detection: Definition and Evaluation") is DEFINED here, every discretisation
+ * choice stated; numbers are comparable with that tool's only up to these choices.  Three new symbols under POD_ABI_VERSION 18, as for
+ * K20 - K33: no entry or structure that existed changed.
+ *
+ * Per image m < n_images: a frame (W, H) = frames[2 m], frames[2 m + 1]; detections j < D = det_off[m + 1] - det_off[m] (xyxy mean, 4x4
+ * covariance, a class probability row of K = num_classes); ground truths i < G = gt_off[m + 1] - gt_off[m] (xyxy box, contiguous class c_i).
+ *   Pixel (u, v), 0 <= u < W, 0 <= v < H, has the centre (u + 0.5, v + 0.5).  The ground-truth segment S_i: the pixels whose centre lies in
+ *   [x1, x2) x [y1, y2) (no masks); n_i = |S_i|.
+ *   Corner blocks: S_tl the (x1, y1) and S_br the (x2, y2) 2x2 block of cov + 1e-2 I, the sum formed in fp32 and then widened (K33's rule;
+ *   the lower triangle is read; cross-corner covariance is ignored, as PDQ's probabilistic box does).  sd = sqrt of the diagonal, rho
+ *   clamped to [-0.99, 0.99].  A detection is INVALID when a diagonal entry of a block is not positive or not finite, a mean is not finite
+ *   or a correlation is not finite: quality 0 against every ground truth, det_invalid[j] = 1, no effect on any other detection.
+ *   P(pixel in box) = A B,  A = Phi2((cx - mu_x1) / sd_x1, (cy - mu_y1) / sd_y1; rho_tl),  B = Phi2((mu_x2 - cx) / sd_x2, (mu_y2 - cy) / sd_y2; rho_br),
+ *   Phi2(h, k; rho) = Phi(h) Phi(k) + (1 / 2 pi) int_0^{asin rho} exp(-(h^2 + k^2 - 2 h k sin t) / (2 cos^2 t)) dt, fp64, Phi through erfc; the
+ *   integral by 20-point Gauss-Legendre on equal panels no wider than asin(0.99) / 4 (four at |rho| = 0.99, none at rho = 0).
+ *   The complement is never 1 - P:  Ac = Phi(-h) + Phi(-k) - Phi2(-h, -k; rho), Bc likewise, Q = Ac + A Bc.
+ *   The detection's segment T_j = {P >= p_min}.  small = 1e-14.
+ *     sum_fg(i, j) = sum_{x in S_i} log max(P'(x), small), P' = P on T_j and 0 elsewhere;   L_FG = -sum_fg / n_i
+ *     sum_bg(i, j) = sum_{x in T_j \ S_i} log max(Q(x), small);                              L_BG = -sum_bg / n_i
+ *     q_fg = exp(-L_FG), q_bg = exp(-L_BG), q_spatial = exp(-(L_FG + L_BG)), q_label = p_j[c_i] (0 for c_i outside [0, K)),
+ *     pPDQ = sqrt(q_spatial q_label).  n_i = 0, S_i and T_j disjoint, or the detection invalid: all five and both sums are 0 -- a pair
+ *     without overlap can never be a true positive, which is also what makes skipping the pixels outside the region of interest exact.
+ *   One workgroup per detection evaluates P and Q once per pixel of the region of interest (columns with cx < mu_x1 + z sd_x1 or
+ *   cx > mu_x2 - z sd_x2, z = Phi^-1(p_min), hold no pixel of T_j since P <= Phi of each single argument; rows likewise; one pixel wider,
+ *   clipped to the frame) and gives every ground truth of the image its sums from that pass: compensated fp64 sums in pixel order, no atomics.  A
+ *   pair's numbers depend on that detection, that ground truth, the frame and p_min alone -- not on the grid, the other images or pairs.
+ * pod_pdq_pairs: frames (n_images, 2), det_off, gt_off (n_images + 1, from 0) int32 and pair_off (n_images + 1, from 0) int64 are HOST
+ *   tables, pair_off[m + 1] - pair_off[m] = G D; the call copies them into `workspace` (dev, pod_pdq_workspace_bytes(n_images) bytes).
+ *   det_means (D_total, 4), det_covs (D_total, 4, 4), det_probs (D_total, K), gt_boxes (G_total, 4) dev fp32, gt_classes dev int32[G_total].
+ *   quality: dev double[5][n_pairs], n_pairs = pair_off[n_images], the planes pPDQ, q_spatial, q_label, q_fg, q_bg; pair (i, j) of image m at
+ *   pair_off[m] + i D + j.  sums: NULL or dev double[2][n_pairs] (sum_fg, sum_bg).  det_invalid: NULL or dev int32[D_total].
+ * pod_pdq_assign: per image the maximum-weight assignment on the G x D matrix of pPDQ (plane 0 of `quality`), padded with zeros to
+ *   n = max(G, D): shortest augmenting paths with potentials in fp64 on cost -pPDQ over the G real rows, one wavefront per image, ties to the
+ *   lowest column -- additions, subtractions and comparisons only.  A true positive is an assigned pair with pPDQ > 0; a pPDQ that is not
+ *   positive and finite counts as 0.
+ *   gt_match: dev int32[G_total], the detection (index inside its image) of a ground truth's true positive, else -1.  counts: dev
+ *   int32[n_images][3] = TP, FP = D - TP, FN = G - TP.  image_sums: dev double[n_images][5], the sums over the image's true positives of the
+ *   five planes, added in ground-truth order.  The data set's PDQ = sum pPDQ / (TP + FP + FN) (0 when that is 0) is the caller's, in image order.
+ * POD_E_INVALID before anything is enqueued: a needed pointer NULL (frames, the offsets; the packed arrays, quality and workspace where there
+ *   is something to read or write), n_images < 0, offsets not starting at 0, decreasing, or pair_off not the running sum of G D, a side
+ *   G or D above POD_PDQ_MAX_SIDE, num_classes outside [1, POD_MAX_CLASSES], a frame dimension below 1 or above POD_PDQ_MAX_FRAME, p_min
+ *   outside (0, 1), workspace / quality / sums / image_sums off 8 bytes.  No detection (pairs) / no image (assign): POD_OK, nothing launched. */
+#define POD_PDQ_MAX_SIDE   256     /* ground truths / detections of one image */
+#define POD_PDQ_MAX_FRAME  32768   /* frame width / height */
+size_t pod_pdq_workspace_bytes(int32_t n_images);
+int pod_pdq_pairs(const int32_t* frames, const int32_t* det_off, const int32_t* gt_off, const int64_t* pair_off, int32_t n_images,
+                  const float* det_means, const float* det_covs, const float* det_probs, int32_t num_classes, const float* gt_boxes,
+                  const int32_t* gt_classes, double p_min, void* workspace, double* quality, double* sums, int32_t* det_invalid,
+                  pod_stream_t stream);
+int pod_pdq_assign(const int32_t* det_off, const int32_t* gt_off, const int64_t* pair_off, int32_t n_images, const double* quality,
+                   void* workspace, int32_t* gt_match, int32_t* counts, double* image_sums, pod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

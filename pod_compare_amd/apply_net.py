@@ -299,13 +299,14 @@ def has_ground_truth(coco_json: str) -> bool:
 
 def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train", test_dataset: str = "bdd_val", binary: bool = False,
                      min_allowed_score: Optional[float] = None, map_results: str = "", device: str = "cuda", seed: int = 0,
-                     scoring_rules: Sequence[str] = ("nll",), energy_samples: int = 1000) -> dict:
+                     scoring_rules: Sequence[str] = ("nll",), energy_samples: int = 1000, pdq: bool = False, p_min: float = 0.0027) -> dict:
     """AN:104-106: the offline chain on a result file, in this process on `device`.  1) AP on K17 (compute_average_precision, its
     default --cat-ids), mAP_res.txt written beside `results`; 2) PM; 3) CE with the calibration pass on the GPU (K18).  Prints the
     three tables the modules print.  The PM / CE threshold: `min_allowed_score`, else `map_results`' (PM:50-65 / CE:47-63), else --
     when the test set is the model's own (bdd_val for a BDD model) -- the threshold the AP step just wrote, else 0.0.  (The reference
     reads the training family's file; its AN:104 has the AP call commented out.)  torch is seeded with `seed` before CE's randperm.
-    scoring_rules beside "nll" (energy, crps, brier) and energy_samples go to PM with `seed`: extra columns, nothing else changes."""
+    scoring_rules beside "nll" (energy, crps, brier) and energy_samples go to PM with `seed`: extra columns, nothing else changes.
+    pdq: also PDQ (compute_pdq, K34) on the same detections under the same threshold, its table printed and its dict under "pdq"."""
     from . import compute_average_precision as cap
     from . import compute_calibration_errors as cce
     from . import compute_probabilistic_metrics as cpm
@@ -337,14 +338,20 @@ def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train
     ce = cce.calibration_errors_of_results(predicted, gt["annotations"], cmap, thr, device=device)
     print(cce.format_table(ce))
     print("Cls Marginal Calibration Error computed by: " + ce["cls_marginal_calibration_error_source"])
-    return {"ap": ap, "pm": pm, "ce": ce, "min_allowed_score": thr, "map_results": map_path}
+    res = {"ap": ap, "pm": pm, "ce": ce, "min_allowed_score": thr, "map_results": map_path}
+    if pdq:
+        from . import compute_pdq
+        res["pdq"] = compute_pdq.pdq_of_results(predicted, gt, cmap, thr, p_min, device)
+        print(compute_pdq.format_table(res["pdq"]))
+    return res
 
 
 def _scoring_rule_options(args) -> dict:
-    """--scoring-rules / --energy-samples as evaluate_results takes them; nothing when only the reference's rules are asked for."""
-    if tuple(args.scoring_rules) == ("nll",):
-        return {}
-    return {"scoring_rules": tuple(args.scoring_rules), "energy_samples": args.energy_samples}
+    """--scoring-rules / --energy-samples and --pdq / --p-min as evaluate_results takes them; nothing when only the reference's rules are asked for."""
+    opts = {} if tuple(args.scoring_rules) == ("nll",) else {"scoring_rules": tuple(args.scoring_rules), "energy_samples": args.energy_samples}
+    if getattr(args, "pdq", False):
+        opts.update(pdq=True, p_min=args.p_min)
+    return opts
 
 
 def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str) -> str:
@@ -362,11 +369,12 @@ COMPARISON_COLUMNS = (      # (heading, evaluator, path into the dictionary eval
     ("Cls MCE", "ce", ("cls_marginal_calibration_error",), "%.4f"), ("Reg ECE", "ce", ("reg_expected_calibration_error",), "%.4f"),
     ("Reg MaxCE", "ce", ("reg_maximum_calibration_error",), "%.4f"), ("Cls MUE", "ce", ("cls_minimum_uncertainty_error",), "%.4f"),
     ("Reg MUE", "ce", ("reg_minimum_uncertainty_error",), "%.4f"))
-EXTRA_COMPARISON_COLUMNS = (      # appended, in this order, when a result carries the key: --scoring-rules brier / energy / crps
+EXTRA_COMPARISON_COLUMNS = (      # appended, in this order, when a result carries the key: --scoring-rules brier / energy / crps, --pdq
     ("TP Cls Brier", "pm", ("average", "true_positives_cls_analysis", "brier_score_mean"), "%.4f"),
     ("FP Cls Brier", "pm", ("average", "false_positives_cls_analysis", "brier_score_mean"), "%.4f"),
     ("TP Reg Energy", "pm", ("average", "true_positives_reg_analysis", "energy_score_mean"), "%.4f"),
-    ("TP Reg CRPS", "pm", ("average", "true_positives_reg_analysis", "crps_mean"), "%.4f"))
+    ("TP Reg CRPS", "pm", ("average", "true_positives_reg_analysis", "crps_mean"), "%.4f"),
+    ("PDQ", "pdq", ("PDQ",), "%.4f"))
 
 
 def format_comparison_table(names: Sequence[str], results: Sequence[dict]) -> str:
@@ -374,14 +382,24 @@ def format_comparison_table(names: Sequence[str], results: Sequence[dict]) -> st
     numbers), the four score columns of the PM table and the five of the CE table.  No number is computed here; one that an evaluator
     left undefined (no true positives, say) prints as "-".  The columns of the extra scoring rules follow when a result carries them."""
     def cell(res, which, path, fmt):
-        v = res[which]
+        v = res.get(which)
+        if v is None:
+            return "-"
         for k in path:
             v = v.get(k) if isinstance(v, dict) else v[k]
             if v is None:
                 return "-"
         return fmt % float(v)
 
-    columns = COMPARISON_COLUMNS + tuple(c for c in EXTRA_COMPARISON_COLUMNS if any(c[2][2] in r[c[1]][c[2][0]][c[2][1]] for r in results))
+    def carries(res, which, path):
+        v = res.get(which)
+        for k in path:
+            if not isinstance(v, dict) or k not in v:
+                return False
+            v = v[k]
+        return True
+
+    columns = COMPARISON_COLUMNS + tuple(c for c in EXTRA_COMPARISON_COLUMNS if any(carries(r, c[1], c[2]) for r in results))
     rows = [("Inference Config",) + tuple(c[0] for c in columns)]
     rows += [(n,) + tuple(cell(r, *c[1:]) for c in columns) for n, r in zip(names, results)]
     w = [max(len(r[i]) for r in rows) for i in range(len(rows[0]))]
@@ -626,6 +644,9 @@ def main(argv=None):
     ap.add_argument("--map-results", default="", help="--eval: take the PM / CE threshold from this mAP_res.txt (PM:50-65)")
     from .compute_probabilistic_metrics import add_scoring_rule_arguments
     add_scoring_rule_arguments(ap)          # --eval: --scoring-rules nll [energy] [crps] [brier], --energy-samples (draws keyed by --random-seed)
+    ap.add_argument("--pdq", action="store_true", help="--eval: also PDQ, the probability-based detection quality (compute_pdq, K34), under the PM / CE "
+                                                       "threshold: its table, its dict under \"pdq\" and a PDQ column in comparison.txt")
+    ap.add_argument("--p-min", type=float, default=0.0027, help="--pdq: a pixel belongs to a detection's segment when P(pixel in box) >= this")
     ap.add_argument("--vis-dir", default="", help="also write every image of this rank annotated as visualize_inference draws it (PI:113-146): "
                                                    "the first --vis-max-boxes detections with their corner-covariance ellipses over the frame at "
                                                    "its original size, rendered on the GPU (K19) and encoded on host threads as <dir>/<file stem>.png")

@@ -11,6 +11,9 @@ Beside the reference's rules: `reg_proper_scores` (energy score and CRPS per row
 proper scoring rules scoring_rules.py does not define.  A partition that carries their per-row tensors ("energy_score", "crps",
 "brier_score") gets their means under the mask from `compute_reg_scores` / `retinanet_compute_cls_scores`; one that does not gets what
 the reference returns.
+
+`pdq_scores` (with `pdq_pair_quality` and `pdq_assign` under it) is PDQ, the probability-based detection quality, on the kernels of K34
+(include/pod_mi355x.h has the definition): the metric the reference's README leaves to a separate CPU tool.
 """
 import math
 from typing import Dict
@@ -148,6 +151,116 @@ def retinanet_compute_cls_scores(input_matches: Dict, valid_idxs: torch.Tensor) 
     if p.shape[0] == 0:
         return dict({"ignorance_score_mean": None}, **extra)
     return dict({"ignorance_score_mean": float((-torch.log(p)).mean())}, **extra)
+
+
+PDQ_P_MIN = 0.0027
+PDQ_PLANES = ("pPDQ", "q_spatial", "q_label", "q_fg", "q_bg")
+
+
+class PdqTables:
+    """The host tables of a pod_pdq_* call -- frames (n, 2) = (W, H), detection, ground-truth and pair offsets -- as contiguous CPU tensors,
+    and the device workspace the calls copy them into."""
+
+    def __init__(self, frames, det_counts, gt_counts, device):
+        n = len(det_counts)
+        if len(gt_counts) != n or len(frames) != n:
+            raise ValueError("pdq: one frame, one detection count and one ground-truth count per image")
+        if any(c > hip.POD_PDQ_MAX_SIDE for c in list(det_counts) + list(gt_counts)):
+            raise hip.PodError("more than {} detections or ground truths in one image".format(hip.POD_PDQ_MAX_SIDE))
+        cum = lambda xs: torch.tensor([0] + list(xs), dtype=torch.int64).cumsum(0)
+        self.n_images = n
+        self.frames = torch.tensor([[int(w), int(h)] for w, h in frames], dtype=torch.int32).reshape(n, 2).contiguous()
+        self.det_off = cum(det_counts).to(torch.int32).contiguous()
+        self.gt_off = cum(gt_counts).to(torch.int32).contiguous()
+        self.pair_off = cum([d * g for d, g in zip(det_counts, gt_counts)]).contiguous()
+        self.n_det, self.n_gt, self.n_pairs = int(self.det_off[-1]), int(self.gt_off[-1]), int(self.pair_off[-1])
+        self.device = torch.device(device)
+        self.workspace = torch.empty(max(int(hip.load().pod_pdq_workspace_bytes(n)), 8), dtype=torch.uint8, device=self.device)
+
+    def pair_matrix(self, plane: torch.Tensor, m: int) -> torch.Tensor:
+        """Image m's (G, D) view of one plane of n_pairs values."""
+        G, D = int(self.gt_off[m + 1] - self.gt_off[m]), int(self.det_off[m + 1] - self.det_off[m])
+        return plane[int(self.pair_off[m]):int(self.pair_off[m + 1])].view(G, D)
+
+
+def pdq_pair_quality(tables: PdqTables, means: torch.Tensor, covs: torch.Tensor, probs: torch.Tensor, gt_boxes: torch.Tensor,
+                     gt_classes: torch.Tensor, p_min: float = PDQ_P_MIN, sums: bool = False):
+    """pod_pdq_pairs (K34): packed detections (D_total, 4) / (D_total, 4, 4) / (D_total, K) and ground truths (G_total, 4) / int (G_total,)
+    on the device -> (quality (5, n_pairs) fp64 in PDQ_PLANES' order, det_invalid (D_total,) int32[, sums (2, n_pairs) fp64])."""
+    dev = tables.device
+    f = lambda t, shape: t.to(dev, torch.float32).reshape(shape).contiguous()
+    K = int(probs.shape[1]) if probs.dim() == 2 and probs.shape[0] else 1
+    means, covs, probs, gt_boxes = f(means, (-1, 4)), f(covs, (-1, 4, 4)), f(probs, (-1, K)), f(gt_boxes, (-1, 4))
+    gt_classes = gt_classes.to(dev, torch.int32).reshape(-1).contiguous()
+    if means.shape[0] != tables.n_det or covs.shape[0] != tables.n_det or probs.shape[0] != tables.n_det or \
+            gt_boxes.shape[0] != tables.n_gt or gt_classes.shape[0] != tables.n_gt:
+        raise ValueError("pdq: the packed arrays do not have the tables' row counts")
+    quality = torch.zeros((5, tables.n_pairs), dtype=torch.float64, device=dev)
+    invalid = torch.zeros(tables.n_det, dtype=torch.int32, device=dev)
+    s = torch.zeros((2, tables.n_pairs), dtype=torch.float64, device=dev) if sums else None
+    P = hip.ptr
+    with torch.cuda.device(dev):
+        hip.check(hip.load().pod_pdq_pairs(tables.frames.data_ptr(), tables.det_off.data_ptr(), tables.gt_off.data_ptr(), tables.pair_off.data_ptr(),
+                                           tables.n_images, P(means), P(covs), P(probs), K, P(gt_boxes), P(gt_classes), float(p_min),
+                                           P(tables.workspace), P(quality), P(s), P(invalid), hip.current_stream()), "pod_pdq_pairs")
+    return (quality, invalid, s) if sums else (quality, invalid)
+
+
+def pdq_assign(tables: PdqTables, quality: torch.Tensor):
+    """pod_pdq_assign (K34): per image the maximum-weight assignment on plane 0 of `quality` -> (gt_match (G_total,) int32: the detection
+    inside its image or -1, counts (n_images, 3) int32 = TP, FP, FN, image_sums (n_images, 5) fp64 over the true positives)."""
+    dev = tables.device
+    quality = quality.to(dev, torch.float64).contiguous()
+    if tuple(quality.shape) != (5, tables.n_pairs):
+        raise ValueError("pdq: quality must be the (5, n_pairs) planes of the tables")
+    match = torch.full((tables.n_gt,), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros((tables.n_images, 3), dtype=torch.int32, device=dev)
+    image_sums = torch.zeros((tables.n_images, 5), dtype=torch.float64, device=dev)
+    P = hip.ptr
+    with torch.cuda.device(dev):
+        hip.check(hip.load().pod_pdq_assign(tables.det_off.data_ptr(), tables.gt_off.data_ptr(), tables.pair_off.data_ptr(), tables.n_images,
+                                            P(quality), P(tables.workspace), P(match), P(counts), P(image_sums), hip.current_stream()), "pod_pdq_assign")
+    return match, counts, image_sums
+
+
+def pdq_scores(pred: Dict, gt: Dict, frame_sizes: Dict, cat_mapping: Dict[int, int], p_min: float = PDQ_P_MIN, device="cuda") -> Dict:
+    """PDQ of a data set (include/pod_mi355x.h, K34).  pred: what `eval_predictions_preprocess` returns (already filtered by the minimum
+    allowed score); gt: what `eval_gt_preprocess` returns; frame_sizes: image id -> (width, height), in the order the images are added
+    up; cat_mapping: the ground truth's category id -> the model's contiguous class.  An image on one side only counts (its detections
+    are false positives, its ground truths false negatives); one without a frame size raises.  One launch scores every (ground truth,
+    detection) pair of the data set, one assigns every image; the totals are added on the host in image order, in fp64.
+    -> {"PDQ", "avg_pPDQ", "avg_spatial", "avg_label", "avg_fg", "avg_bg", "TP", "FP", "FN", "invalid_detections", "num_images", "p_min"}."""
+    dev = torch.device(device)
+    boxes, probs, covs = pred["predicted_boxes"], pred["predicted_cls_probs"], pred["predicted_covar_mats"]
+    gboxes, gcats = gt["gt_boxes"], gt["gt_cat_idxs"]
+    missing = [i for i in list(boxes) + list(gboxes) if i not in frame_sizes]
+    if missing:
+        raise ValueError("pdq: no frame size for image {!r}".format(missing[0]))
+    ids = [i for i in frame_sizes if i in boxes or i in gboxes]
+    nd = [int(boxes[i].shape[0]) if i in boxes else 0 for i in ids]
+    ng = [int(gboxes[i].shape[0]) if i in gboxes else 0 for i in ids]
+    tables = PdqTables([frame_sizes[i] for i in ids], nd, ng, dev)
+    K = next((int(probs[i].shape[1]) for i in ids if i in probs), 1)
+    cat = lambda ts, shape: torch.cat([t.to(dev, torch.float32).reshape(shape) for t in ts]) if ts else torch.zeros((0,) + tuple(shape[1:]), device=dev)
+    means = cat([boxes[i] for i in ids if i in boxes], (-1, 4))
+    cov = cat([covs[i] for i in ids if i in boxes], (-1, 4, 4))
+    prob = cat([probs[i] for i in ids if i in boxes], (-1, K))
+    gb = cat([gboxes[i] for i in ids if i in gboxes], (-1, 4))
+    gc = torch.tensor([cat_mapping[int(c)] for i in ids if i in gboxes for c in gcats[i].reshape(-1).tolist()], dtype=torch.int32, device=dev)
+    res = {"PDQ": 0.0, "avg_pPDQ": 0.0, "avg_spatial": 0.0, "avg_label": 0.0, "avg_fg": 0.0, "avg_bg": 0.0, "TP": 0, "FP": sum(nd), "FN": sum(ng),
+           "invalid_detections": 0, "num_images": len(ids), "p_min": float(p_min)}
+    if not ids:
+        return res
+    quality, invalid = pdq_pair_quality(tables, means, cov, prob, gb, gc, p_min)
+    _, counts, image_sums = pdq_assign(tables, quality)
+    tp, fp, fn = (int(v) for v in counts.sum(0).tolist())
+    totals = [0.0] * 5
+    for row in image_sums.cpu().tolist():          # image order, fp64
+        totals = [a + b for a, b in zip(totals, row)]
+    res.update({"TP": tp, "FP": fp, "FN": fn, "invalid_detections": int(invalid.sum()), "PDQ": totals[0] / (tp + fp + fn) if tp + fp + fn else 0.0})
+    if tp:
+        res.update({k: t / tp for k, t in zip(("avg_pPDQ", "avg_spatial", "avg_label", "avg_fg", "avg_bg"), totals)})
+    return res
 
 
 def eval_predictions_preprocess(predicted_instances, min_allowed_score: float = 0.0, is_odd: bool = False, device="cpu"):

@@ -14,6 +14,8 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
     nms_cluster  detectron2 batched_nms as called at PI:554-560 / IU:31-36 -> keep indices
     reg_nll      compute_reg_scores' per-row NLL, scoring_rules.py:68-74
     reg_scores   the per-row energy score and CRPS of the same Gaussians (K33; rules the reference does not define) -> (energy, crps)
+    pdq_pairs    PDQ's five per-pair quantities for a batch of images (K34; a metric the reference leaves to a separate CPU tool): host
+                 tables (frames, offsets: CPU int32) + packed CUDA detections and ground truths -> (quality (5, n_pairs) fp64, det_invalid)
     wino_filter_transform / wino_conv3x3
                  the head's `Conv2d(C, K, 3, padding=1) [+ ReLU + Dropout]` (PR:403-484) for all MC runs and FPN levels in one
                  launch: channels-last activations in, channels-last (trunk) or NCHW planes (predictors) out
@@ -42,6 +44,8 @@ _LIB.define("predict(Tensor[] box_cls, Tensor[] box_delta, Tensor[] box_cls_var,
 _LIB.define("nms_cluster(Tensor boxes, Tensor scores, Tensor classes, float nms_thresh, int max_detections, int num_classes) -> Tensor")
 _LIB.define("reg_nll(Tensor means, Tensor covs, Tensor gt) -> Tensor")
 _LIB.define("reg_scores(Tensor means, Tensor covs, Tensor gt, int num_samples=1000, int seed=0) -> (Tensor, Tensor)")
+_LIB.define("pdq_pairs(Tensor frames, Tensor det_off, Tensor gt_off, Tensor means, Tensor covs, Tensor probs, Tensor gt_boxes, Tensor gt_classes, "
+            "float p_min=0.0027) -> (Tensor, Tensor)")
 _LIB.define("wino_filter_transform(Tensor weight) -> Tensor")
 _LIB.define("wino_conv3x3(Tensor src, Tensor U, Tensor? bias, Tensor blocks, int K, int out_elements, bool planes=False, bool relu=False, "
             "float dropout_p=0.0, int seed=0, int offset=0) -> Tensor")
@@ -168,6 +172,31 @@ def _reg_scores(means, covs, gt, num_samples=1000, seed=0) -> Tuple[torch.Tensor
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, None, None, hip.ptr(energy), hip.ptr(crps), hip.current_stream()),
                       "pod_reg_scores")
     return energy, crps
+
+
+def _pdq_pairs(frames, det_off, gt_off, means, covs, probs, gt_boxes, gt_classes, p_min=0.0027) -> Tuple[torch.Tensor, torch.Tensor]:
+    """frames (n, 2) = (W, H), det_off, gt_off (n + 1, from 0): CPU integer tensors (the kernel's host tables); the packed arrays on one CUDA
+    device.  -> quality (5, n_pairs) fp64, pair (i, j) of image m at sum_{m' < m} G D + i D + j, and det_invalid (D_total,) int32."""
+    from . import evaluation_utils as ev
+    for name, t in (("frames", frames), ("det_off", det_off), ("gt_off", gt_off)):
+        torch._check(not t.is_cuda and not t.is_floating_point(), lambda: "{}: a CPU integer tensor (a host table)".format(name))
+    n = int(frames.shape[0])
+    torch._check(frames.dim() == 2 and frames.shape[1] == 2 and tuple(det_off.shape) == (n + 1,) and tuple(gt_off.shape) == (n + 1,),
+                 lambda: "frames (n, 2), det_off and gt_off (n + 1,)")
+    torch._check(n == 0 or (int(det_off[0]) == 0 and int(gt_off[0]) == 0), lambda: "offsets start at 0")
+    nd, ng = (det_off[1:] - det_off[:-1]).tolist(), (gt_off[1:] - gt_off[:-1]).tolist()
+    torch._check(all(0 <= c <= hip.POD_PDQ_MAX_SIDE for c in nd + ng), lambda: "0 .. {} detections / ground truths per image".format(hip.POD_PDQ_MAX_SIDE))
+    torch._check(0.0 < p_min < 1.0, lambda: "p_min in (0, 1)")
+    D, G = sum(nd), sum(ng)
+    K = int(probs.shape[1]) if probs.dim() == 2 else 0
+    torch._check(1 <= K <= hip.POD_MAX_CLASSES, lambda: "probs: (D, K), K in [1, {}]".format(hip.POD_MAX_CLASSES))
+    for name, t, shape in (("means", means, (D, 4)), ("covs", covs, (D, 4, 4)), ("probs", probs, (D, K)), ("gt_boxes", gt_boxes, (G, 4))):
+        torch._check(t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.device == means.device,
+                     lambda: "{}: CUDA fp32 {}".format(name, shape))
+    torch._check(gt_classes.is_cuda and not gt_classes.is_floating_point() and tuple(gt_classes.shape) == (G,) and gt_classes.device == means.device,
+                 lambda: "gt_classes: CUDA integer ({},)".format(G))
+    tables = ev.PdqTables(frames.tolist(), nd, ng, means.device)
+    return ev.pdq_pair_quality(tables, means, covs, probs, gt_boxes, gt_classes, float(p_min))
 
 
 def _wino_filter_transform(weight) -> torch.Tensor:
@@ -370,5 +399,6 @@ _IMPL.impl("predict", _predict, "CUDA")
 _IMPL.impl("nms_cluster", _nms_cluster, "CUDA")
 _IMPL.impl("reg_nll", _reg_nll, "CUDA")
 _IMPL.impl("reg_scores", _reg_scores, "CUDA")
+_IMPL.impl("pdq_pairs", _pdq_pairs, "CUDA")
 _IMPL.impl("wino_filter_transform", _wino_filter_transform, "CUDA")
 _IMPL.impl("wino_conv3x3", _wino_conv3x3, "CUDA")
