@@ -1291,6 +1291,59 @@ int pod_pdq_pairs(const int32_t* frames, const int32_t* det_off, const int32_t* 
 int pod_pdq_assign(const int32_t* det_off, const int32_t* gt_off, const int64_t* pair_off, int32_t n_images, const double* quality,
                    void* workspace, int32_t* gt_match, int32_t* counts, double* image_sums, pod_stream_t stream);
 
+/* ---- K35  synthetic corruptions of the decoded frame (csrc/k35_corrupt_u8.hip) ---------------------------------------------------
+ * Replaces: nothing in the reference: the test loader's frame, between decode and AN:83-84's resize.  The reference measures data-set
+ * shift with a second and a third data set; this is the controlled shift of Hendrycks and Dietterich's ImageNet-C, eight kinds, the
+ * constants of the five severities this project's own (pod_compare_amd/corruptions.py): parity with no package is claimed.
+ * Two new symbols and one new structure under POD_ABI_VERSION 18, as for K20 - K34: no entry or structure that existed changed.
+ *
+ * Input and output: uint8 (h, w, 3) RGB, rows `row_stride` bytes apart (>= 3 w), two buffers that do not overlap.  The output is a pure
+ * function of (frame bytes, kind, parameters, key).  Every kind ends in Q(v) = uint8(floor(min(max(v, 0), 1) * 255 + 0.5)): round to
+ * nearest, where the public implementations truncate -- a flat region stays flat under a filter whose taps sum to 1 +- an ulp.
+ *   GAUSSIAN_NOISE  fp32: xf = float(x) / 255, v = xf + sigma z             (sigma = (float)p0; the product first, then the sum)
+ *   SPECKLE_NOISE   fp32: v = xf + (xf * c) * z                             (c = (float)p0)
+ *     z of channel ch at pixel (x, y): Philox4x32-10 with counter (x, y, 0, 0x636f7200 "cor") and key `key` (low word, high word);
+ *     normal ch & 1 of output word ch >> 1 through box_muller16 (csrc/pod_device.h).
+ *   IMPULSE_NOISE   integers: counter (x, y, 1, 0x636f7200); byte ch becomes 255 / 0 (bit ch of word 3 set / clear) iff word ch <
+ *     impulse_threshold = min(floor(amount 2^32), 2^32 - 1), and passes unchanged otherwise.
+ *   BRIGHTNESS, SATURATE  fp64, every operation rounded on its own: r, g, b = x / 255.0; V = max, m = min, d = V - m; S = d / V (0 when
+ *     V = 0); h6 = 0 when d = 0, else (g - b) / d (+ 6 when negative) when V = r, else 2 + (b - r) / d when V = g, else 4 + (r - g) / d.
+ *     BRIGHTNESS: V <- min(V + p0, 1).  SATURATE: S <- min(max(S p0 + p1, 0), 1).  Back: i = floor(h6) (6 reads as 0), f = h6 - i,
+ *     p = V (1 - S), q = V (1 - f S), t = V (1 - (1 - f) S); (r, g, b) by sextant: (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q).
+ *   CONTRAST        fp64: mean_c = (integer sum of channel c) / (255.0 h w); v = (x / 255.0 - mean_c) p0 + mean_c.  The sums are 32-bit
+ *     integers per workgroup, added in 64 bits by a second launch: the bytes cannot depend on the grid.  No float atomics.
+ *   GAUSSIAN_BLUR   taps: dev float[2 radius + 1], radius <= 24.  Separable, along the rows, then down the columns; border clamped to the
+ *     edge.  fp32: acc = fmaf(tap, float(byte), acc) in ascending tap order, the intermediate kept in byte units in `scratch`; v = acc / 255.
+ *   DEFOCUS_BLUR    taps: dev float[(2 radius + 1)^2] row-major, radius <= 12: a dense correlation, the same stencil for the three
+ *     channels, reflect-101 borders repeated until the index is inside; fp32 as above, stencil rows then columns ascending.
+ * pod_corrupt_scratch_bytes: bytes of `scratch` (dev, 8-byte aligned) a call needs -- GAUSSIAN_BLUR 12 h w, CONTRAST 32 + 12 ceil(h w / 4096),
+ *   0 for the other kinds (scratch may then be NULL) and for a side outside [1, POD_RESIZE_MAX_SIDE].
+ * pod_corrupt_frame_u8: enqueues on `stream` (one launch; CONTRAST three, GAUSSIAN_BLUR two), never synchronises.  POD_E_INVALID and nothing
+ *   enqueued: src, dst or corruption NULL; a side < 1 or > POD_RESIZE_MAX_SIDE; a row stride < 3 w; kind outside [0, POD_CORRUPT_KINDS); a
+ *   filter's radius < 0 or above its cap, or its taps NULL; scratch NULL, off 8 bytes or smaller than pod_corrupt_scratch_bytes says; src,
+ *   dst and the needed scratch overlapping one another. */
+#define POD_CORRUPT_GAUSSIAN_NOISE 0
+#define POD_CORRUPT_SPECKLE_NOISE  1
+#define POD_CORRUPT_IMPULSE_NOISE  2
+#define POD_CORRUPT_GAUSSIAN_BLUR  3
+#define POD_CORRUPT_DEFOCUS_BLUR   4
+#define POD_CORRUPT_BRIGHTNESS     5
+#define POD_CORRUPT_CONTRAST       6
+#define POD_CORRUPT_SATURATE       7
+#define POD_CORRUPT_KINDS          8      /* the rest of ImageNet-C would continue here */
+typedef struct PodCorruption {
+    int32_t kind;                 /* POD_CORRUPT_* */
+    int32_t radius;               /* the filters: taps reach -radius .. radius */
+    double p0, p1;                /* the kind's parameters (above); unused ones ignored */
+    const float* taps;            /* dev; the filters */
+    uint32_t impulse_threshold;   /* IMPULSE_NOISE */
+    uint32_t reserved;
+    uint64_t key;                 /* the noises: Philox key */
+} PodCorruption;
+size_t pod_corrupt_scratch_bytes(int32_t kind, int32_t h, int32_t w);
+int pod_corrupt_frame_u8(const uint8_t* src, int32_t h, int32_t w, int64_t src_row_stride, uint8_t* dst, int64_t dst_row_stride,
+                         const PodCorruption* corruption, void* scratch, size_t scratch_bytes, pod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -354,10 +354,33 @@ def _scoring_rule_options(args) -> dict:
     return opts
 
 
-def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str) -> str:
+def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str, suffix: str = "") -> str:
     """AN:44-48: `<OUTPUT_DIR>/inference/<test data set>/<name of the inference YAML>`, the directory the reference's apply_net writes a
-    config's coco_instances_results.json to and its evaluators read it from."""
-    return os.path.join(output_dir, "inference", test_dataset, os.path.split(inference_config)[-1][:-5])
+    config's coco_instances_results.json to and its evaluators read it from.  suffix: a corrupted run's `<NAME>_<N>`, which makes the
+    data set's component `<test data set>_<NAME>_<N>` -- a corrupted data set is another data set."""
+    return os.path.join(output_dir, "inference", test_dataset + ("_" + suffix if suffix else ""), os.path.split(inference_config)[-1][:-5])
+
+
+def _check_corruption(args) -> None:
+    """--corruption NAME --severity N (K35, corruptions.py): refused by name before a model is built or a rank is started where the run has
+    no decoded frame on the device to corrupt, or draws / re-reads frames another way.  Implies --resize-on-gpu."""
+    if args.corruption is None and args.severity is None:
+        return
+    if args.corruption is None or args.severity is None:
+        raise SystemExit("--corruption and --severity are needed together")
+    from . import corruptions
+    try:
+        corruptions.parameters(args.corruption, args.severity)
+    except ValueError as e:
+        raise SystemExit("--corruption / --severity: %s" % e)
+    if not args.coco_json:
+        raise SystemExit("--corruption corrupts decoded files: it needs --coco-json (synthetic frames are not supported)")
+    for flag, given in (("--ensemble-per-gpu", args.ensemble_per_gpu), ("--vis-dir", bool(args.vis_dir)), ("--eval-only", args.eval_only)):
+        if given:
+            raise SystemExit("--corruption cannot be combined with %s" % flag)
+    args.resize_on_gpu = True
+    if int(os.environ.get("RANK", "0")) == 0:
+        print("corrupted on the GPU: %s, severity %d" % (args.corruption, args.severity))
 
 
 COMPARISON_COLUMNS = (      # (heading, evaluator, path into the dictionary evaluate_results returns for it, format)
@@ -425,12 +448,17 @@ def _start_rank(args, world: int, rank: int, local_rank: int) -> None:
 def _network_input(args, cfg, d: Optional[dict], i: int, dev):
     """Image i as the predictor takes it, enqueued on the current stream: (input_im, the synthetic frame or None).  d: the loader's entry
     of a --coco-json run -- resized on the host exactly as detectron2's mapper does, or, with --resize-on-gpu, the decoded frame, which
-    goes up and comes out as the host path's bytes (K20), outside any captured graph.  image_id is the position in the list: the data
+    goes up and comes out as the host path's bytes (K20), outside any captured graph; with --corruption it is corrupted at its own size
+    on the way (K35).  image_id is the position in the list: the data
     set's id is restored by _image_order."""
     from . import modeling, resize, synthetic
     if d is not None:
         if args.resize_on_gpu:
-            image = resize.resize_frame_u8(d["frame"].to(dev, non_blocking=True), cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+            frame = d["frame"].to(dev, non_blocking=True)
+            if getattr(args, "corruption", None):       # K35, on this image's stream; the key names the image, not its place on a rank
+                from . import corruptions
+                frame = corruptions.corrupt_frame_u8(frame, args.corruption, args.severity, corruptions.corruption_key(args.random_seed, i))
+            image = resize.resize_frame_u8(frame, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
         else:
             image = d["image"].to(dev, non_blocking=True)
         return [{"image": image, "height": d["height"], "width": d["width"], "image_id": i}], None
@@ -472,7 +500,8 @@ def _main_comparison(args, paths: List[str]):
     if evaluating and not has_ground_truth(args.coco_json):
         raise SystemExit("--eval / --eval-only need ground truth: --coco-json with `annotations`")
     cfgs = [setup_config(args.config_file, p, args.random_seed, data_dir=args.data_dir, is_testing=bool(args.data_dir)) for p in paths]
-    dirs = [inference_output_dir(cfgs[0].OUTPUT_DIR, args.test_dataset, p) for p in paths]
+    suffix = "%s_%d" % (args.corruption, args.severity) if args.corruption else ""
+    dirs = [inference_output_dir(cfgs[0].OUTPUT_DIR, args.test_dataset, p, suffix) for p in paths]
     outputs = [os.path.join(d, "coco_instances_results.json") for d in dirs]
     sidecars = [os.path.join(d, args.binary_output) if args.binary_output else "" for d in dirs]
 
@@ -654,7 +683,14 @@ def main(argv=None):
     ap.add_argument("--vis-ellipse-pairing", choices=("reference", "box"), default="reference",
                     help="--vis-dir: reference = the ellipses as PV:70-86 pairs them (the box drawn k-th, by area, gets the k-th covariance of "
                          "the result order); box = every box with its own covariance")
+    ap.add_argument("--corruption", default=None,
+                    help="--coco-json: corrupt every decoded frame on the GPU before the resize (K35, corruptions.py): gaussian_noise, speckle_noise, "
+                         "impulse_noise, gaussian_blur, defocus_blur, brightness, contrast or saturate, after ImageNet-C.  Needs --severity; implies "
+                         "--resize-on-gpu.  The noise of image i is keyed by (--random-seed, i): the bytes do not depend on ranks or streams.  With "
+                         "several --inference-config paths the directories are <test data set>_<NAME>_<N>")
+    ap.add_argument("--severity", type=int, default=None, help="--corruption: 1 (mild) to 5")
     args = ap.parse_args(argv)
+    _check_corruption(args)
     if len(args.inference_config) > 1:
         return _main_comparison(args, list(args.inference_config))
     args.inference_config = args.inference_config[0]

@@ -7,7 +7,7 @@ returns an error, a RuntimeError is raised.  Tensors are passed as raw device po
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import Optional
 
 import torch
@@ -36,6 +36,8 @@ POD_REG_LOSS_MOMENTS, POD_REG_LOSS_ENERGY, POD_MAX_REG_SAMPLES = 1, 2, 4096
 POD_FULL_COV_NLL, POD_FULL_COV_MOMENTS, POD_FULL_COV_ENERGY = 1, 2, 3
 POD_SGD_MAX_GROUPS = 8
 POD_PDQ_MAX_SIDE, POD_PDQ_MAX_FRAME = 256, 32768
+(POD_CORRUPT_GAUSSIAN_NOISE, POD_CORRUPT_SPECKLE_NOISE, POD_CORRUPT_IMPULSE_NOISE, POD_CORRUPT_GAUSSIAN_BLUR, POD_CORRUPT_DEFOCUS_BLUR,
+ POD_CORRUPT_BRIGHTNESS, POD_CORRUPT_CONTRAST, POD_CORRUPT_SATURATE, POD_CORRUPT_KINDS) = range(9)
 POD_SGD_CLIP_OFF, POD_SGD_CLIP_VALUE, POD_SGD_CLIP_NORM, POD_SGD_CLIP_FULL_MODEL = 0, 1, 2, 3
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
@@ -58,13 +60,14 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_train_batch_tiles", "pod_train_batch_u8",
            "pod_retinanet_infer_workspace", "pod_retinanet_score", "pod_retinanet_topk", "pod_retinanet_decode", "pod_retinanet_postprocess",
            "pod_retinanet_infer_image", "pod_reg_scores",
-           "pod_pdq_workspace_bytes", "pod_pdq_pairs", "pod_pdq_assign")
+           "pod_pdq_workspace_bytes", "pod_pdq_pairs", "pod_pdq_assign",
+           "pod_corrupt_scratch_bytes", "pod_corrupt_frame_u8")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
                  "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes",
-                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles", "pod_retinanet_infer_workspace", "pod_pdq_workspace_bytes")
+                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles", "pod_retinanet_infer_workspace", "pod_pdq_workspace_bytes", "pod_corrupt_scratch_bytes")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -174,6 +177,12 @@ class PodRetinaNetLayout(Structure):
     """include/pod_mi355x.h: PodRetinaNetLayout (K32, byte offsets into pod_retinanet_infer_image's workspace)."""
     _fields_ = [(n, c_int64) for n in ("cand_keys", "cand_count", "sel_keys", "sel_count", "cat_keys", "cat_level", "n_total", "cand_flat", "cand_level",
                                        "boxes", "scores", "classes", "keep", "n_keep", "nms_scratch", "total")]
+
+
+class PodCorruption(Structure):
+    """include/pod_mi355x.h: PodCorruption (K35, one corruption of pod_corrupt_frame_u8)."""
+    _fields_ = [("kind", c_int32), ("radius", c_int32), ("p0", c_double), ("p1", c_double), ("taps", c_void_p),
+                ("impulse_threshold", c_uint32), ("reserved", c_uint32), ("key", c_uint64)]
 
 
 class PodError(RuntimeError):
@@ -334,6 +343,9 @@ def load() -> ctypes.CDLL:
     lib.pod_pdq_workspace_bytes.restype = c_size_t
     lib.pod_pdq_pairs.argtypes = [P, P, P, P, c_int32, P, P, P, c_int32, P, P, c_double, P, P, P, P, P]      # the first four: host tables
     lib.pod_pdq_assign.argtypes = [P, P, P, c_int32, P, P, P, P, P, P]
+    lib.pod_corrupt_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
+    lib.pod_corrupt_scratch_bytes.restype = c_size_t
+    lib.pod_corrupt_frame_u8.argtypes = [P, c_int32, c_int32, c_int64, P, c_int64, POINTER(PodCorruption), P, c_size_t, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

@@ -25,6 +25,9 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
     train_batch_u8
                  a training batch's network inputs in one launch (K31): decoded (h, w, 3) uint8 frames -> per frame the (3, nh, nw) uint8
                  tensor PIL's bilinear resize at sizes[2 i], sizes[2 i + 1], the flip where hflips[i], BGR and the transpose give
+    corrupt_frame
+                 one of the eight synthetic corruptions (K35; the reference has none: it measures shift with other data sets) of a decoded
+                 (h, w, 3) uint8 RGB frame at severity 1..5, the noise keyed by (seed, index) -> the frame's geometry, corrupted
     retinanet_inference
                  detectron2's RetinaNet.inference + detector_postprocess for one image (K32; what the reference model runs in eval mode,
                  PR:156-166): the eval-mode head output, per level (1, A*K, H, W) / (1, A*4, H, W) -> boxes, scores, classes
@@ -56,6 +59,7 @@ _LIB.define("stem7x7_split(Tensor frame, Tensor Ws, Tensor? bias, Tensor? mean, 
 _LIB.define("maxpool3x3s2_cl(Tensor x, int h, int w) -> Tensor")
 _LIB.define("im2col3x3s2_cl(Tensor x, int h, int w, bool relu=False) -> Tensor")
 _LIB.define("train_batch_u8(Tensor[] frames, int[] sizes, bool[] hflips, bool bgr=True) -> Tensor[]")
+_LIB.define("corrupt_frame(Tensor frame, str name, int severity, int seed, int index) -> Tensor")
 _LIB.define("retinanet_inference(Tensor[] box_cls, Tensor[] box_delta, Tensor[] anchors, int[] image_size, int[] out_size, int num_classes=7, "
             "int topk_candidates=1000, float score_thresh=0.05, float nms_thresh=0.5, int max_detections=100, "
             "float[] box_weights=[1.0, 1.0, 1.0, 1.0]) -> (Tensor, Tensor, Tensor)")
@@ -352,6 +356,12 @@ def _train_batch_u8(frames, sizes, hflips, bgr=True) -> List[torch.Tensor]:
     return train_batch.train_batch_u8(list(frames), pairs, [bool(v) for v in hflips], bgr=bool(bgr))
 
 
+def _corrupt_frame(frame, name, severity, seed, index) -> torch.Tensor:
+    from . import corruptions
+    torch._check(frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3, lambda: "frame: CUDA uint8 (h, w, 3)")
+    return corruptions.corrupt_frame_u8(frame, str(name), int(severity), corruptions.corruption_key(int(seed), int(index)))
+
+
 def _retinanet_inference(box_cls, box_delta, anchors, image_size, out_size, num_classes=7, topk_candidates=1000, score_thresh=0.05,
                          nms_thresh=0.5, max_detections=100, box_weights=(1.0, 1.0, 1.0, 1.0)) -> Tuple[torch.Tensor, ...]:
     from . import retinanet_inference as ri
@@ -389,6 +399,7 @@ def _retinanet_inference(box_cls, box_delta, anchors, image_size, out_size, num_
 _IMPL = torch.library.Library("pod_mi355x", "IMPL")
 _IMPL.impl("retinanet_inference", _retinanet_inference, "CUDA")
 _IMPL.impl("train_batch_u8", _train_batch_u8, "CUDA")
+_IMPL.impl("corrupt_frame", _corrupt_frame, "CUDA")
 _IMPL.impl("im2col3x3s2_cl", _im2col3x3s2_cl, "CUDA")
 _IMPL.impl("conv1x1_filter_split", _conv1x1_filter_split, "CUDA")
 _IMPL.impl("conv1x1_split", _conv1x1_split, "CUDA")
