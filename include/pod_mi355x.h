@@ -1344,6 +1344,70 @@ size_t pod_corrupt_scratch_bytes(int32_t kind, int32_t h, int32_t w);
 int pod_corrupt_frame_u8(const uint8_t* src, int32_t h, int32_t w, int64_t src_row_stride, uint8_t* dst, int64_t dst_row_stride,
                          const PodCorruption* corruption, void* scratch, size_t scratch_bytes, pod_stream_t stream);
 
+/* ---- K36  post-hoc recalibration: one temperature, per-coordinate variance scales (csrc/k36_recalibrate.hip) -------------------
+ * Replaces: nothing in the reference, which measures calibration (CE:86-297) and stops.  Fits a two-parameter-family map on matched
+ * detections and applies it to K7's record table: every probability p -> sigmoid(beta logit p), the xyxy covariance Sigma -> D Sigma D,
+ * D = diag(s).  Six new symbols under POD_ABI_VERSION 18, as for K20 - K35: no entry or structure that existed changed.
+ *
+ * Sums.  No atomics.  Every fp64 sum of this section is added in ONE order, whatever the grid: the values of a sequence (a segment's, in
+ *   index order) are cut into chunks of POD_RECAL_CHUNK = 256 consecutive values, the last one shorter; a chunk's partial is
+ *   ((0.0 + v_0) + v_1) + ... in index order; the sum is ((0.0 + partial_0) + partial_1) + ... in chunk order.  The library is built with
+ *   -ffp-contract=off: a host that adds fp64 values in this order gets the same bits.
+ * pod_recal_workspace_bytes(n, n_seg): bytes of `workspace` (dev, 8-byte aligned) for any call below on n values and up to n_seg
+ *   segments; 0 for n outside [0, 2^31 - 1] or n_seg outside [0, POD_RECAL_MAX_SEGMENTS].
+ * pod_recal_cls_sums: p dev float[n] scores, y dev uint8[n] labels in {0, 1}.  x_i = logit(c_i) = log(c_i / (1 - c_i)),
+ *   c_i = min(max(double(p_i), 2^-30), 1 - 2^-30) (only exact 0 and 1 and scores below 2^-30 move: the largest fp32 below 1 is 1 - 2^-24);
+ *   t_i = beta x_i, e_i = exp(-|t_i|), s_i = 1 / (1 + e_i) for t_i >= 0, else e_i / (1 + e_i).  sums[0 .. 2], dev double:
+ *     L = sum (max(t_i, 0) + log1p(e_i)) - y_i t_i,   g = dL/dbeta = sum (s_i - y_i) x_i,   h = sum (e_i / (1 + e_i)^2) x_i^2.
+ *   x: NULL, or dev double[n] that receives the x_i (x_ready == 0) or holds them from an earlier call on the same p (x_ready != 0: p is
+ *   not read, no logarithm is taken) -- a Newton loop computes them once.  workspace: pod_recal_workspace_bytes(n, 0).  n == 0: three zeros.
+ * pod_recal_reg_z: the n_matched matched rows' xyxy means, (4, 4) covariances and ground-truth boxes, dev fp32.  Value 4 i + d, d < 4:
+ *   z = (double(gt_d) - double(mean_d)) / sqrt(double(cov_dd)) and its segment id seg = d (n_class == 0: global scales) or
+ *   4 det_class[i] + d (n_class >= 1: per-class scales; det_class dev int32[n_matched], the row's class as pod_calib_keys writes it).  A value whose
+ *   cov_dd is not finite or <= 0, whose residual is not finite, or whose class lies outside [0, n_class) is left out: z = 0, seg = -1, and
+ *   it is counted in invalid[d] (dev int64[4]).  z dev double[4 n_matched], seg dev int32[4 n_matched].  Only + - / sqrt: bit-equal to
+ *   the same fp64 expression on a host.  workspace: pod_recal_workspace_bytes(4 n_matched, 0).
+ * pod_recal_moment: n values z with segment ids seg (< 0 or >= n_seg: left out) -> zg dev double[n], the values grouped by segment in
+ *   ascending id, row order kept inside a segment (the left-out tail zeros); seg_off dev int64[n_seg + 1], the segments' offsets in zg;
+ *   count dev int64[n_seg]; sum dev double[n_seg], the sum of z^2 over the segment's values in zg order, added as above.  sum / count is
+ *   the maximum-likelihood variance scale s^2 of the marginal Gaussian; the square root and the empty segment (s = 1) are the caller's.
+ * pod_recal_ece_grid: zg / seg_off as pod_recal_moment wrote them, max_seg the longest segment (from count; a host value).  Each
+ *   segment's values are sorted ascending; for every segment and every grid scale scales[j], j < n_grid (dev double), with m the segment's count,
+ *     obj[s][j] = (sum_{i = 1 .. n_q} (count(z < scales[j] * q[i - 1]) / m - i / (n_q + 1))^2) / n_q
+ *   -- the reference's regression calibration objective (CE:206-261) at variance scale scales[j]: q dev double[n_q] are the caller's
+ *   Phi^-1(i / (n_q + 1)), the counts by binary search, the n_q terms added in i order from 0.0, every operation one fp64 rounding.  An empty
+ *   segment's objectives are 0.  best_j[s]: the arg-min, ties to the smaller |j - j_one|, then to the smaller j (j_one: the grid point of
+ *   scale 1); best_obj[s] = obj[s][best_j[s]], one_obj[s] = obj[s][j_one].  obj dev double[n_seg][n_grid], best_j dev int32[n_seg].
+ *   workspace: pod_recal_workspace_bytes(n, n_seg), as for pod_recal_moment.
+ * pod_recal_apply: records dev float[n_images][max_det][6 + K + 16] (K7's rows: x, y, w, h, score, class, probs[K], C = T Sigma T^T row-major in
+ *   xywh form), counts dev int32[n_images]; out another buffer of the records' shape.  A row behind its image's count is written as zeros.  A
+ *   live row: box and class copied; score and every probability p -> float(s(beta x(p))) with x and s as in pod_recal_cls_sums (beta == 1.0:
+ *   copied bit for bit); C -> M C M^T, M = T diag(s) T^-1 = [[s0,0,0,0],[0,s1,0,0],[s2-s0,0,s2,0],[0,s3-s1,0,s3]], s = scales[0] (n_scale_rows
+ *   == 1) or scales[class] (per class; a class outside [0, n_scale_rows) keeps its covariance): A = M C, A[0][k] = s0 C[0][k],
+ *   A[1][k] = s1 C[1][k], A[2][k] = (s2 - s0) C[0][k] + s2 C[2][k], A[3][k] = (s3 - s1) C[1][k] + s3 C[3][k]; then C'[k][0] = A[k][0] s0,
+ *   C'[k][1] = A[k][1] s1, C'[k][2] = A[k][0] (s2 - s0) + A[k][2] s2, C'[k][3] = A[k][1] (s3 - s1) + A[k][3] s3 -- fp64, each product and
+ *   sum rounded on its own, the result rounded once to fp32.  Four scales of 1.0 copy C bit for bit.  scales dev double[n_scale_rows][4].
+ * POD_E_INVALID before anything is enqueued: a needed pointer NULL, a size negative or above its limit (n > 2^31 - 1, 4 n_matched likewise,
+ *   n_class / n_scale_rows above POD_MAX_CLASSES, n_seg outside [1, POD_RECAL_MAX_SEGMENTS], n_grid outside [1, POD_RECAL_MAX_GRID], j_one
+ *   outside the grid, n_q outside [1, POD_RECAL_MAX_QUANTILES], max_seg outside [0, n], max_det < 1, K outside [1, POD_MAX_CLASSES], n_scale_rows
+ *   < 1), beta NaN (pod_recal_apply: not positive and finite), x_ready without x, records == out, an fp64 / int64 buffer off 8 bytes. */
+#define POD_RECAL_CHUNK          256
+#define POD_RECAL_MAX_SEGMENTS   64      /* 4 POD_MAX_CLASSES */
+#define POD_RECAL_MAX_GRID       4096
+#define POD_RECAL_MAX_QUANTILES  64
+size_t pod_recal_workspace_bytes(int64_t n, int32_t n_seg);
+int pod_recal_cls_sums(const float* p, const uint8_t* y, int64_t n, double beta, double* x, int32_t x_ready, void* workspace, double* sums,
+                       pod_stream_t stream);
+int pod_recal_reg_z(const float* means, const float* covs, const float* gt, const int32_t* det_class, int32_t n_matched, int32_t n_class,
+                    void* workspace, double* z, int32_t* seg, int64_t* invalid, pod_stream_t stream);
+int pod_recal_moment(const double* z, const int32_t* seg, int64_t n, int32_t n_seg, void* workspace, double* zg, int64_t* seg_off,
+                     int64_t* count, double* sum, pod_stream_t stream);
+int pod_recal_ece_grid(const double* zg, const int64_t* seg_off, int64_t n, int32_t n_seg, int32_t max_seg, const double* scales,
+                       int32_t n_grid, int32_t j_one, const double* q, int32_t n_q, void* workspace, double* obj, int32_t* best_j,
+                       double* best_obj, double* one_obj, pod_stream_t stream);
+int pod_recal_apply(const float* records, const int32_t* counts, int32_t n_images, int32_t max_det, int32_t num_classes, double beta,
+                    const double* scales, int32_t n_scale_rows, float* out, pod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,14 +299,17 @@ def has_ground_truth(coco_json: str) -> bool:
 
 def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train", test_dataset: str = "bdd_val", binary: bool = False,
                      min_allowed_score: Optional[float] = None, map_results: str = "", device: str = "cuda", seed: int = 0,
-                     scoring_rules: Sequence[str] = ("nll",), energy_samples: int = 1000, pdq: bool = False, p_min: float = 0.0027) -> dict:
+                     scoring_rules: Sequence[str] = ("nll",), energy_samples: int = 1000, pdq: bool = False, p_min: float = 0.0027,
+                     recalibration=None) -> dict:
     """AN:104-106: the offline chain on a result file, in this process on `device`.  1) AP on K17 (compute_average_precision, its
     default --cat-ids), mAP_res.txt written beside `results`; 2) PM; 3) CE with the calibration pass on the GPU (K18).  Prints the
     three tables the modules print.  The PM / CE threshold: `min_allowed_score`, else `map_results`' (PM:50-65 / CE:47-63), else --
     when the test set is the model's own (bdd_val for a BDD model) -- the threshold the AP step just wrote, else 0.0.  (The reference
     reads the training family's file; its AN:104 has the AP call commented out.)  torch is seeded with `seed` before CE's randperm.
     scoring_rules beside "nll" (energy, crps, brier) and energy_samples go to PM with `seed`: extra columns, nothing else changes.
-    pdq: also PDQ (compute_pdq, K34) on the same detections under the same threshold, its table printed and its dict under "pdq"."""
+    pdq: also PDQ (compute_pdq, K34) on the same detections under the same threshold, its table printed and its dict under "pdq".
+    recalibration: a file `python -m pod_compare_amd.recalibrate fit` wrote (or a recalibration.Recalibration): the detections are
+    transformed on the GPU (K36) after loading and before AP, and the AP step writes mAP_res_recalibrated.txt, never a raw run's file."""
     from . import compute_average_precision as cap
     from . import compute_calibration_errors as cce
     from . import compute_probabilistic_metrics as cpm
@@ -319,10 +322,17 @@ def evaluate_results(results: str, gt_json: str, train_dataset: str = "bdd_train
             predicted = json.load(f)
     with open(gt_json, "r") as f:
         gt = json.load(f)
+    if recalibration is not None:
+        from . import recalibration as rc
+        recal = rc.Recalibration.load(recalibration) if isinstance(recalibration, str) else recalibration
+        ids_of = category_mapping(train_dataset, test_dataset)
+        unique = len(set(ids_of.values())) == len(ids_of)             # else the record's class is the arg-max of its probabilities
+        predicted = rc.apply_to_results(predicted, recal, {v: k for k, v in ids_of.items()} if unique else None, device=device)
+        print("recalibrated: beta %.6f, %s scales %s" % (recal.beta, "per-class" if recal.per_class else "global", recal.scales))
     ap = cap.coco_average_precision(predicted, gt, device=device)
     print(cap.format_summary(ap["stats"]))
     print("Classification Score at Optimal F-1 Score: {}".format(ap["optimal_score_threshold"]))
-    map_path = os.path.join(os.path.dirname(os.path.abspath(results)), "mAP_res.txt")
+    map_path = os.path.join(os.path.dirname(os.path.abspath(results)), "mAP_res.txt" if recalibration is None else "mAP_res_recalibrated.txt")
     cap.write_map_results(map_path, ap["stats"], ap["optimal_score_threshold"])
     if min_allowed_score is not None or map_results:
         thr = cap.resolve_min_allowed_score(min_allowed_score, map_results)
@@ -352,6 +362,23 @@ def _scoring_rule_options(args) -> dict:
     if getattr(args, "pdq", False):
         opts.update(pdq=True, p_min=args.p_min)
     return opts
+
+
+def _recalibration_option(args) -> dict:
+    """One config's --recalibration FILE as evaluate_results takes it; nothing without the flag, so the call is what it was."""
+    return {"recalibration": args.recalibration[0]} if getattr(args, "recalibration", None) else {}
+
+
+def _check_recalibration(args) -> None:
+    """--recalibration FILE [FILE ...]: one file per inference config, in order, for an evaluating run -- refused by name otherwise."""
+    files = getattr(args, "recalibration", None)
+    if not files:
+        return
+    if not (args.eval or args.eval_only):
+        raise SystemExit("--recalibration transforms the detections an evaluation reads: it needs --eval or --eval-only")
+    if len(files) != len(args.inference_config):
+        raise SystemExit("--recalibration takes one file per --inference-config, in order: got %d file(s) for %d config(s)"
+                         % (len(files), len(args.inference_config)))
 
 
 def inference_output_dir(output_dir: str, test_dataset: str, inference_config: str, suffix: str = "") -> str:
@@ -507,13 +534,15 @@ def _main_comparison(args, paths: List[str]):
 
     def evaluate_all(device):
         res = []
-        for name, out, side in zip(names, outputs, sidecars):
+        recal = args.recalibration or [None] * len(names)
+        for name, out, side, rc_file in zip(names, outputs, sidecars, recal):
             print("== %s" % name)
             binary = args.eval_only and bool(side)        # as one config's --eval-only: the sidecar when it is named
+            extra = {} if rc_file is None else {"recalibration": rc_file}
             res.append(evaluate_results(side if binary else out, args.coco_json, args.train_dataset, args.test_dataset, binary=binary,
-                                        min_allowed_score=args.min_allowed_score, map_results=args.map_results, device=device, seed=args.random_seed, **_scoring_rule_options(args)))
+                                        min_allowed_score=args.min_allowed_score, map_results=args.map_results, device=device, seed=args.random_seed, **_scoring_rule_options(args), **extra))
         table = format_comparison_table(names, res)
-        with open(os.path.join(dirs[0], "comparison.txt"), "w") as f:
+        with open(os.path.join(dirs[0], "comparison_recalibrated.txt" if args.recalibration else "comparison.txt"), "w") as f:
             f.write(table + "\n")
         print(table)
         return res
@@ -689,8 +718,13 @@ def main(argv=None):
                          "--resize-on-gpu.  The noise of image i is keyed by (--random-seed, i): the bytes do not depend on ranks or streams.  With "
                          "several --inference-config paths the directories are <test data set>_<NAME>_<N>")
     ap.add_argument("--severity", type=int, default=None, help="--corruption: 1 (mild) to 5")
+    ap.add_argument("--recalibration", nargs="+", default=None, metavar="FILE",
+                    help="--eval / --eval-only: recalibrate the detections on the GPU (K36) with the map `python -m pod_compare_amd.recalibrate fit` "
+                         "wrote, after loading and before AP; one file per --inference-config, in order.  The AP step then writes "
+                         "mAP_res_recalibrated.txt and a comparison pass comparison_recalibrated.txt: a raw run's files are never overwritten")
     args = ap.parse_args(argv)
     _check_corruption(args)
+    _check_recalibration(args)
     if len(args.inference_config) > 1:
         return _main_comparison(args, list(args.inference_config))
     args.inference_config = args.inference_config[0]
@@ -710,7 +744,8 @@ def main(argv=None):
         local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
         return evaluate_results(args.binary_output if binary else (args.output or "coco_instances_results.json"), args.coco_json,
                                 args.train_dataset, args.test_dataset, binary=binary, min_allowed_score=args.min_allowed_score,
-                                map_results=args.map_results, device="cuda:%d" % local_rank, seed=args.random_seed, **_scoring_rule_options(args))
+                                map_results=args.map_results, device="cuda:%d" % local_rank, seed=args.random_seed, **_scoring_rule_options(args),
+                                **_recalibration_option(args))
     if args.output is None:
         args.output = "coco_instances_results.json"
     rank = int(os.environ.get("RANK", "0"))
@@ -832,7 +867,7 @@ def main(argv=None):
     res = None
     if rank == 0 and args.eval:
         res = evaluate_results(args.output, args.coco_json, args.train_dataset, args.test_dataset, min_allowed_score=args.min_allowed_score,
-                               map_results=args.map_results, device=dev, seed=args.random_seed, **_scoring_rule_options(args))
+                               map_results=args.map_results, device=dev, seed=args.random_seed, **_scoring_rule_options(args), **_recalibration_option(args))
     if world > 1:
         dist.destroy_process_group()
     return res

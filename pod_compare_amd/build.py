@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpod_mi355x.so")
 SOURCES = ["k1_mc_merge_score.hip", "k1f_merge_score_fused.hip", "k2_topk_gather.hip", "k3_decode_cov.hip", "k4_nms.hip", "k5_cluster_merge.hip",
-           "k8_model_ops.hip", "k9_eval_match.hip", "k10_debug_dump.hip", "k11_wino_conv.hip", "k12_wino_conv_split.hip", "k13_conv1x1_split.hip", "k14_stem_conv.hip", "k15_sparse_blocks.hip", "k17_coco_eval.hip", "k18_calibration.hip", "k19_vis_render.hip", "k20_resize_u8.hip", "k21_train_loss.hip", "k22_conv3x3_wgrad.hip", "k23_fpn_backward.hip", "k24_resnet_backward.hip", "k25_sgd_step.hip", "k26_grad_bucket.hip", "k27_reg_score_loss.hip", "k28_full_cov_loss.hip", "k29_sgd_solver.hip", "k30_stem_backward.hip", "k31_train_batch.hip", "k32_retinanet_inference.hip", "k33_eval_scores.hip", "k34_pdq.hip", "k35_corrupt_u8.hip", "pod_run.hip"]
+           "k8_model_ops.hip", "k9_eval_match.hip", "k10_debug_dump.hip", "k11_wino_conv.hip", "k12_wino_conv_split.hip", "k13_conv1x1_split.hip", "k14_stem_conv.hip", "k15_sparse_blocks.hip", "k17_coco_eval.hip", "k18_calibration.hip", "k19_vis_render.hip", "k20_resize_u8.hip", "k21_train_loss.hip", "k22_conv3x3_wgrad.hip", "k23_fpn_backward.hip", "k24_resnet_backward.hip", "k25_sgd_step.hip", "k26_grad_bucket.hip", "k27_reg_score_loss.hip", "k28_full_cov_loss.hip", "k29_sgd_solver.hip", "k30_stem_backward.hip", "k31_train_batch.hip", "k32_retinanet_inference.hip", "k33_eval_scores.hip", "k34_pdq.hip", "k35_corrupt_u8.hip", "k36_recalibrate.hip", "pod_run.hip"]
 HEADERS = [os.path.join(CSRC, "pod_device.h"), os.path.join(CSRC, "pod_candidate.h"), os.path.join(CSRC, "pod_merge_score.h"), os.path.join(CSRC, "pod_wino.h"), os.path.join(CSRC, "pod_split_gemm.h"), os.path.join(CSRC, "pod_wgrad.h"), os.path.join(CSRC, "pod_tensor_table.h"), os.path.join(CSRC, "pod_train_loss.h"), os.path.join(CSRC, "pod_reg_sigma.h"), os.path.join(CSRC, "pod_resize_u8.h"), os.path.join(os.path.dirname(HERE), "include", "pod_mi355x.h"),
            os.path.join(os.path.dirname(HERE), "include", "pod_mi355x_test.h"), os.path.join(CSRC, "pod_experiments.h"), os.path.join(CSRC, "pod_segsort.h")]
 # -ffp-contract=off: the CPU reference rounds after every op; index parity needs the same fp32 values.

@@ -38,6 +38,7 @@ POD_SGD_MAX_GROUPS = 8
 POD_PDQ_MAX_SIDE, POD_PDQ_MAX_FRAME = 256, 32768
 (POD_CORRUPT_GAUSSIAN_NOISE, POD_CORRUPT_SPECKLE_NOISE, POD_CORRUPT_IMPULSE_NOISE, POD_CORRUPT_GAUSSIAN_BLUR, POD_CORRUPT_DEFOCUS_BLUR,
  POD_CORRUPT_BRIGHTNESS, POD_CORRUPT_CONTRAST, POD_CORRUPT_SATURATE, POD_CORRUPT_KINDS) = range(9)
+POD_RECAL_CHUNK, POD_RECAL_MAX_SEGMENTS, POD_RECAL_MAX_GRID, POD_RECAL_MAX_QUANTILES = 256, 64, 4096, 64
 POD_SGD_CLIP_OFF, POD_SGD_CLIP_VALUE, POD_SGD_CLIP_NORM, POD_SGD_CLIP_FULL_MODEL = 0, 1, 2, 3
 
 EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_score_maybe", "pod_merge_score_fused", "pod_reset_counters", "pod_level_topk", "pod_gather_candidates", "pod_gather_decode",
@@ -61,13 +62,15 @@ EXPORTS = ("pod_abi_version", "pod_mc_merge_score", "pod_maybe_words", "pod_scor
            "pod_retinanet_infer_workspace", "pod_retinanet_score", "pod_retinanet_topk", "pod_retinanet_decode", "pod_retinanet_postprocess",
            "pod_retinanet_infer_image", "pod_reg_scores",
            "pod_pdq_workspace_bytes", "pod_pdq_pairs", "pod_pdq_assign",
-           "pod_corrupt_scratch_bytes", "pod_corrupt_frame_u8")
+           "pod_corrupt_scratch_bytes", "pod_corrupt_frame_u8",
+           "pod_recal_workspace_bytes", "pod_recal_cls_sums", "pod_recal_reg_z", "pod_recal_moment", "pod_recal_ece_grid", "pod_recal_apply")
 _SIZE_QUERIES = ("pod_abi_version", "pod_nms_scratch_bytes", "pod_coco_eval_scratch_bytes", "pod_coco_accumulate_workspace_bytes", "pod_maybe_words",
                  "pod_wino_filter_split_bytes", "pod_conv1x1_filter_split_bytes", "pod_calib_min_uncertainty_workspace_bytes",
                  "pod_calib_marginal_sort_workspace_bytes", "pod_calib_marginal_error_workspace_bytes", "pod_train_loss_partials",
                  "pod_conv3x3_wgrad_partials", "pod_conv1x1_wgrad_partials", "pod_conv1x1_wgrad_strided_partials", "pod_sgd_chunk_map",
                  "pod_grad_bucket_layout", "pod_reg_score_partials", "pod_full_cov_partials", "pod_sgd_solver_workspace_bytes",
-                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles", "pod_retinanet_infer_workspace", "pod_pdq_workspace_bytes", "pod_corrupt_scratch_bytes")
+                 "pod_stem7x7_wgrad_partials", "pod_train_batch_tiles", "pod_retinanet_infer_workspace", "pod_pdq_workspace_bytes", "pod_corrupt_scratch_bytes",
+                 "pod_recal_workspace_bytes")
 # include/pod_mi355x_test.h: test support (the dumps of the in-kernel draws, the generator and box_muller16 on given inputs, the f16 split) -- exported for tests/ and tools/, not part of the boundary
 TEST_EXPORTS = ("pod_dump_cls_normals", "pod_dump_box_normals", "pod_debug_f16_split2", "pod_debug_philox4x32", "pod_debug_box_muller16")
 POD_MODE_STANDARD_NMS, POD_MODE_BAYES_OD, POD_MODE_ANCHOR_STATISTICS = 0, 1, 2
@@ -346,6 +349,13 @@ def load() -> ctypes.CDLL:
     lib.pod_corrupt_scratch_bytes.argtypes = [c_int32, c_int32, c_int32]
     lib.pod_corrupt_scratch_bytes.restype = c_size_t
     lib.pod_corrupt_frame_u8.argtypes = [P, c_int32, c_int32, c_int64, P, c_int64, POINTER(PodCorruption), P, c_size_t, P]
+    lib.pod_recal_workspace_bytes.argtypes = [c_int64, c_int32]
+    lib.pod_recal_workspace_bytes.restype = c_size_t
+    lib.pod_recal_cls_sums.argtypes = [P, P, c_int64, c_double, P, c_int32, P, P, P]
+    lib.pod_recal_reg_z.argtypes = [P, P, P, P, c_int32, c_int32, P, P, P, P, P]
+    lib.pod_recal_moment.argtypes = [P, P, c_int64, c_int32, P, P, P, P, P, P]
+    lib.pod_recal_ece_grid.argtypes = [P, P, c_int64, c_int32, c_int32, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, P]
+    lib.pod_recal_apply.argtypes = [P, P, c_int32, c_int32, c_int32, c_double, P, c_int32, P, P]
     for name in EXPORTS + TEST_EXPORTS:
         if name not in _SIZE_QUERIES:
             getattr(lib, name).restype = ctypes.c_int

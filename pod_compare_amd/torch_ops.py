@@ -16,6 +16,9 @@ no second implementation and no CPU kernel (calling them with CPU tensors raises
     reg_scores   the per-row energy score and CRPS of the same Gaussians (K33; rules the reference does not define) -> (energy, crps)
     pdq_pairs    PDQ's five per-pair quantities for a batch of images (K34; a metric the reference leaves to a separate CPU tool): host
                  tables (frames, offsets: CPU int32) + packed CUDA detections and ground truths -> (quality (5, n_pairs) fp64, det_invalid)
+    recalibrate_records
+                 a fitted recalibration (K36; the reference has none) applied to K7's record table: records (n_images, max_det, 6 + K + 16),
+                 counts, one temperature beta and xyxy standard-deviation scales (1, 4) or (classes, 4) fp64 -> the recalibrated table
     wino_filter_transform / wino_conv3x3
                  the head's `Conv2d(C, K, 3, padding=1) [+ ReLU + Dropout]` (PR:403-484) for all MC runs and FPN levels in one
                  launch: channels-last activations in, channels-last (trunk) or NCHW planes (predictors) out
@@ -49,6 +52,7 @@ _LIB.define("reg_nll(Tensor means, Tensor covs, Tensor gt) -> Tensor")
 _LIB.define("reg_scores(Tensor means, Tensor covs, Tensor gt, int num_samples=1000, int seed=0) -> (Tensor, Tensor)")
 _LIB.define("pdq_pairs(Tensor frames, Tensor det_off, Tensor gt_off, Tensor means, Tensor covs, Tensor probs, Tensor gt_boxes, Tensor gt_classes, "
             "float p_min=0.0027) -> (Tensor, Tensor)")
+_LIB.define("recalibrate_records(Tensor records, Tensor counts, int num_classes, float beta, Tensor scales) -> Tensor")
 _LIB.define("wino_filter_transform(Tensor weight) -> Tensor")
 _LIB.define("wino_conv3x3(Tensor src, Tensor U, Tensor? bias, Tensor blocks, int K, int out_elements, bool planes=False, bool relu=False, "
             "float dropout_p=0.0, int seed=0, int offset=0) -> Tensor")
@@ -201,6 +205,18 @@ def _pdq_pairs(frames, det_off, gt_off, means, covs, probs, gt_boxes, gt_classes
                  lambda: "gt_classes: CUDA integer ({},)".format(G))
     tables = ev.PdqTables(frames.tolist(), nd, ng, means.device)
     return ev.pdq_pair_quality(tables, means, covs, probs, gt_boxes, gt_classes, float(p_min))
+
+
+def _recalibrate_records(records, counts, num_classes, beta, scales) -> torch.Tensor:
+    from . import recalibration
+    torch._check(1 <= num_classes <= hip.POD_MAX_CLASSES, lambda: "num_classes in [1, {}]".format(hip.POD_MAX_CLASSES))
+    torch._check(records.is_cuda and records.dtype == torch.float32 and records.dim() == 3 and records.shape[2] == 6 + num_classes + 16,
+                 lambda: "records: CUDA fp32 (n_images, max_det, {})".format(6 + num_classes + 16))
+    torch._check(not counts.is_floating_point() and tuple(counts.shape) == (records.shape[0],), lambda: "counts: integer (n_images,)")
+    torch._check(scales.dim() == 2 and scales.shape[1] == 4 and 1 <= scales.shape[0] <= hip.POD_MAX_CLASSES,
+                 lambda: "scales: (1, 4) or (classes, 4), at most {} rows".format(hip.POD_MAX_CLASSES))
+    torch._check(0.0 < beta < float("inf"), lambda: "beta positive and finite")
+    return recalibration.apply_table(records, counts, int(num_classes), float(beta), scales.detach().cpu().to(torch.float64))
 
 
 def _wino_filter_transform(weight) -> torch.Tensor:
@@ -411,5 +427,6 @@ _IMPL.impl("nms_cluster", _nms_cluster, "CUDA")
 _IMPL.impl("reg_nll", _reg_nll, "CUDA")
 _IMPL.impl("reg_scores", _reg_scores, "CUDA")
 _IMPL.impl("pdq_pairs", _pdq_pairs, "CUDA")
+_IMPL.impl("recalibrate_records", _recalibrate_records, "CUDA")
 _IMPL.impl("wino_filter_transform", _wino_filter_transform, "CUDA")
 _IMPL.impl("wino_conv3x3", _wino_conv3x3, "CUDA")
